@@ -100,6 +100,9 @@ def parse():
                     help="comma-separated BASELINE configurations for the other_configs leg ('' = none)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="bodies walked by the CPU baseline (0 = all, i.e. one full step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the timed path left (positions, velocities, caller "
+                         "order; a fixed, seeded sample of rows above 64 MB) as DIR/<name>.npy in float64")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check: parse, (spawn,) join the process group, all-reduce the ranks, print what a real "
                          "run would be launched as -- no device is touched (tests/test_bench_launch_cpu.py)")
@@ -221,6 +224,26 @@ def single_gpu_record(a, n, write=None):
             return json.load(fh)
     except (OSError, ValueError):
         return None
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(dirname, arrays):
+    """Write name -> (n, k) float64 arrays (all of the same n, caller order) as dirname/<name>.npy.  When the whole set is
+    larger than DUMP_MAX_BYTES, every array keeps the same rows: a sorted sample drawn with a fixed seed, which depends on n
+    only, so that two runs of the same arguments write the same rows."""
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_MAX_BYTES:
+        keep = int(n * (DUMP_MAX_BYTES - (1 << 16)) // total)     # (room for the .npy headers)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if rows is None else a[rows], dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def spread(x):
@@ -571,6 +594,24 @@ def main():
         ss = _S
     else:
         pf, vf = eng.download()
+    if a.dump_outputs:
+        # the state the last timed step left, in the caller's order (the LET ranks hold their bodies by id)
+        if use_let:
+            parts = [None] * world
+            if world > 1:
+                dist.all_gather_object(parts, (idf, pf, vf))
+            else:
+                parts[0] = (idf, pf, vf)
+            if rank == 0:
+                ids_all = np.concatenate([p[0] for p in parts])
+                order = np.argsort(ids_all, kind="stable")
+                assert np.array_equal(ids_all[order], np.arange(n)), "the ranks' bodies are not one copy of every id"
+                pd, vd = (np.concatenate([p[k] for p in parts])[order] for k in (1, 2))
+            del parts
+        else:
+            pd, vd = pf, vf                          # replicated: every rank holds the whole state after the exchange
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"positions": pd, "velocities": vd})
     out = None
     if rank == 0:
         if ss is None:

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -54,3 +56,25 @@ def test_one_gpu_runs_directly():
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
     assert j["n_gpus"] == 1 and j["launched_by"] == "direct"
+
+
+def test_dump_outputs_writes_float64_under_64mb_with_the_same_rows_every_time(tmp_path):
+    """--dump-outputs: a set larger than 64 MB keeps one fixed, seeded sample of rows (the same rows in every array and
+    every run); a smaller set is written whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 3 << 20                                              # 2 x (n, 2) float64 = 96 MB
+    pos = np.arange(2 * n, dtype=np.float64).reshape(n, 2)
+    vel = -pos
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"positions": pos, "velocities": vel})
+    sizes = sum(os.path.getsize(tmp_path / "a" / f) for f in ("positions.npy", "velocities.npy"))
+    assert sizes <= 64 << 20
+    pa, va = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "a" / "velocities.npy")
+    assert pa.dtype == va.dtype == np.float64 and len(pa) > n // 2
+    assert np.array_equal(pa, np.load(tmp_path / "b" / "positions.npy")) and np.array_equal(va, -pa)
+    rows = pa[:, 0].astype(np.int64) // 2
+    assert np.all(np.diff(rows) > 0)                         # distinct rows, caller order kept
+    small = pos[:1000]
+    bench.dump_outputs(str(tmp_path / "c"), {"positions": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "positions.npy"), small)
