@@ -50,17 +50,21 @@ struct DevBuf {
 struct bh_ctx {
     bh_config cfg{};
     int Dm = 0;
-    bool exact = true, compat = true;
-    bool exact_thr = false;        // BH_PRECISION_F64_EXACT: nodes carry exact d2 thresholds for the walk's acceptance test (off: BH_FLAG_WALK_PORTABLE)
-    bool fast64 = false;           // BH_PRECISION_F64: the exact mode's tree and state, the throughput walk of bh_walk_f64.hpp
+    // cfg.precision: BH_PRECISION_F64_EXACT, BH_PRECISION_F64 (the exact mode's tree and state, the throughput walk of
+    // bh_walk_f64.hpp), BH_PRECISION_MIXED, BH_PRECISION_F32
+    enum class Mode { Exact, F64, Mixed, F32 };
+    Mode mode = Mode::Exact;
+    // fp64 NodeD / LinkD tree, fp64 forces, state in caller order (else: QuadF tree, accelerations, device order)
+    bool tree64() const { return mode == Mode::Exact || mode == Mode::F64; }
+    bool state64() const { return mode != Mode::F32; }    // fp64 state arrays
+    bool compat = true;
+    bool exact_thresholds = false; // Mode::Exact: nodes carry exact d2 thresholds for the walk's acceptance test (off: BH_FLAG_WALK_PORTABLE)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int64_t n = 0;
     bool uploaded = false, tree_valid = false;
     int64_t internal_cap = 0, node_cap = 0;
-    int sort_passes = 0;
-    bool state64 = false;          // fp64 state arrays: exact and mixed precision
     int64_t bfs_max = 12288;       // bit-exact walk: one wavefront per body (walk_exact_bfs_kernel) for launches up to here (BH_EXACT_BFS_MAX;
                                    // walk ms against the cooperative walk: 0.021 / 0.072 at N = 1,024, 0.042 / 0.108 at 4,096, 0.126 / 0.223
                                    // at 8,192, 0.180 / 0.221 at 12,288, 0.241 / 0.212 at 16,384)
@@ -131,7 +135,6 @@ struct bh_ctx {
     const void **walk_consts = nullptr; // device block {aux, spos, smass, 0} for the assembly walk's bucket path
     bool aux_full = false;              // aux[] holds every node's record (after an export), not only the buckets'
     bool group_cost_valid = false;
-    int64_t group_cost_n = 0;           // number of groups group_cost describes
     uint32_t *body_counts = nullptr;    // BH_FLAG_WALK_STATS: accepted force evaluations per body (device slot order)
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
@@ -155,6 +158,8 @@ struct bh_ctx {
     uint64_t device_bytes = 0;
     std::string err;
 };
+
+using Mode = bh_ctx::Mode;
 
 namespace {
 
@@ -194,6 +199,23 @@ inline void dev_free(bh_ctx *c, void *p)
 }
 
 inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// f(std::bool_constant<b>{}...) for runtime bools b...: every combination is instantiated
+template <typename F>
+void dispatch(F &&f) { f(); }
+template <typename F, typename... B>
+void dispatch(F &&f, bool b, B... rest)
+{
+    if (b) dispatch([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else dispatch([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
+
+// node kernels and the mass pass: one thread per subdivided cell; I <= (n-1)*Dm and <= internal_cap (at least one
+// thread: the root-only case)
+inline int64_t cell_span(const bh_ctx *c)
+{
+    return std::max<int64_t>(1, std::min<int64_t>(c->internal_cap, std::max<int64_t>(c->n - 1, 0) * (int64_t)std::max(1, c->Dm)));
+}
 
 void owned_range(const bh_ctx *c, int64_t *lo, int64_t *hi)
 {
@@ -236,26 +258,19 @@ __global__ __launch_bounds__(kBlock) void reorder_state_kernel(uint32_t *__restr
 // again after the build (export_tree_host).
 static void launch_nodes_fast(bh_ctx *c, bool full_aux, hipStream_t st)
 {
-    const int64_t n = c->n;
-    const int Dm = c->Dm;
-    // one thread per subdivided cell; I <= (n-1)*Dm and <= internal_cap
-    const int64_t span = std::max<int64_t>(1, std::min<int64_t>(c->internal_cap, std::max<int64_t>(n - 1, 0) * (int64_t)std::max(1, Dm)));
-    const unsigned nbc = blocks_for(span, kBlock);
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(nbc), dim3(kBlock), 0, st, c->keys_sorted, c->coarse, c->cnt, c->cell_first,
-                           c->spos, c->smass, c->box, c->terms, n, Dm, c->cfg.theta, c->internal_cap, c->qf, c->aux,
-                           c->ctr);
-    };
-    if (c->compat) { if (full_aux) go(nodes_fast_kernel<true, true>); else go(nodes_fast_kernel<true, false>); }
-    else { if (full_aux) go(nodes_fast_kernel<false, true>); else go(nodes_fast_kernel<false, false>); }
+    dispatch([&](auto compat, auto full) {
+        hipLaunchKernelGGL((nodes_fast_kernel<decltype(compat)::value, decltype(full)::value>), dim3(blocks_for(cell_span(c), kBlock)),
+                           dim3(kBlock), 0, st, c->keys_sorted, c->coarse, c->cnt, c->cell_first, c->spos, c->smass, c->box,
+                           c->terms, c->n, c->Dm, c->cfg.theta, c->internal_cap, c->qf, c->aux, c->ctr);
+    }, c->compat, full_aux);
     c->aux_full = full_aux;
 }
 
-template <bool EXACT, bool STATE64 = EXACT, int ITEMS = kItems>
+template <bool TREE64, bool STATE64 = TREE64, int ITEMS = kItems>
 int enqueue_build_t(bh_ctx *c)
 {
     constexpr int TILE = kBlock * ITEMS;
-    static_assert(!EXACT || STATE64, "exact mode keeps its state in fp64");
+    static_assert(!TREE64 || STATE64, "an fp64 tree is built from fp64 state");
     using Real2 = typename std::conditional<STATE64, double2, float2>::type;   // the state
     using Real = typename std::conditional<STATE64, double, float>::type;
     const int64_t n = c->n;
@@ -303,23 +318,16 @@ int enqueue_build_t(bh_ctx *c)
         c->last_sort_bucket = bucket || single; c->last_sort_packed = pack;
         {
             const unsigned nkb = blocks_for(n, kBlock);
-            auto keys_launch = [&](auto hil, auto pk, auto fs) {
+            auto keys_launch = [&](auto fs, auto pk, auto hil) {
                 constexpr bool H = decltype(hil)::value, P = decltype(pk)::value, F = decltype(fs)::value;
                 const bool smp = P && bucket;                       // (the splitter workgroups go with the packed keys)
                 // samples: the previous build's sorted positions -- the fp32 walk's copy, or through the previous perm in the exact modes
                 hipLaunchKernelGGL((keys_kernel<Real2, H, P, F>), dim3(nkb + (smp ? ns / kWave : 0)), dim3(kBlock), 0, st, pos, c->box,
-                                   c->keys[0], c->vals[0], n, Dm, (smp && !EXACT) ? (const float2 *)c->spos : nullptr, c->splitters, nb, ns,
-                                   slots, c->ctr, smp ? c->bsum_sort : nullptr, smp ? nb : 0, (smp && EXACT) ? c->perm : nullptr);
+                                   c->keys[0], c->vals[0], n, Dm, (smp && !TREE64) ? (const float2 *)c->spos : nullptr, c->splitters, nb, ns,
+                                   slots, c->ctr, smp ? c->bsum_sort : nullptr, smp ? nb : 0, (smp && TREE64) ? c->perm : nullptr);
             };
-            using T = std::true_type; using Fz = std::false_type;
             // (exact mode and BH_HILBERT=0: child-index keys, packed all the same)
-            if (from_slots) {
-                if (pack && c->hilbert) keys_launch(T{}, T{}, T{}); else if (pack) keys_launch(Fz{}, T{}, T{});
-                else if (c->hilbert) keys_launch(T{}, Fz{}, T{}); else keys_launch(Fz{}, Fz{}, T{});
-            } else {
-                if (pack && c->hilbert) keys_launch(T{}, T{}, Fz{}); else if (pack) keys_launch(Fz{}, T{}, Fz{});
-                else if (c->hilbert) keys_launch(T{}, Fz{}, Fz{}); else keys_launch(Fz{}, Fz{}, Fz{});
-            }
+            dispatch(keys_launch, from_slots, pack, c->hilbert);
         }
         if (c->time_groups) (void)hipEventRecord(c->ev_grp[0], st);
         const unsigned nbl = blocks_for(n, ITEMS == kItems ? kSortTile : TILE);
@@ -332,7 +340,7 @@ int enqueue_build_t(bh_ctx *c)
             constexpr int SI = (ITEMS == kItems ? kSortItems : ITEMS);
             auto pass = [&](auto bits_tag) {
                 constexpr int NBITS = decltype(bits_tag)::value;
-                if constexpr (EXACT) {                               // (state in caller order: the pass with its row scan, see radix_scatter_w)
+                if constexpr (TREE64) {                               // (state in caller order: the pass with its row scan, see radix_scatter_w)
                     hipLaunchKernelGGL((radix_hist<SI, NBITS, true>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->radix_counts, n,
                                        0, (int)nbl, c->splitters, c->sort_dig, nullptr);
                     hipLaunchKernelGGL(radix_rowscan, dim3(1 << NBITS), dim3(kBlock), 0, st, c->radix_counts, c->bsum_sort, (int)nbl);
@@ -375,7 +383,7 @@ int enqueue_build_t(bh_ctx *c)
         }
         c->keys_sorted = c->keys[cur];
         c->perm = c->vals[cur];
-        if constexpr (!EXACT) {
+        if constexpr (!TREE64) {
             if (c->reorder_every > 0 && c->builds % c->reorder_every == 0) {
                 hipLaunchKernelGGL((reorder_state_kernel<Real2, Real>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, st,
                                    c->perm, pos, static_cast<const Real2 *>(c->vel), mass,
@@ -394,27 +402,27 @@ int enqueue_build_t(bh_ctx *c)
 
         // 4. cells owned by each sorted neighbour pair (+ fp32: sorted copies and prefix-sum terms),
         // 5. their ranks / the prefix sums
-        using SReal2 = typename std::conditional<EXACT, double2, float2>::type;    // what the walk reads
-        using SReal = typename std::conditional<EXACT, double, float>::type;
+        using SReal2 = typename std::conditional<TREE64, double2, float2>::type;    // what the walk reads
+        using SReal = typename std::conditional<TREE64, double, float>::type;
         // elements per thread in prep / scan_apply2: the sort's tile size, except that between 768k and
         // 2M bodies tiles of 1,024 are still the better choice for these two (a workgroup's rows are a
         // chain of load -> scan -> store; measured at N = 1M: 42.5 -> 33 us for the pair)
         auto scan_part = [&](auto si_tag) {
             constexpr int SI = decltype(si_tag)::value;
             const unsigned nbs = blocks_for(n + 1, kBlock * SI);
-            hipLaunchKernelGGL((prep_kernel<EXACT, SI, Real2, Real, SReal2, SReal>), dim3(nbs), dim3(kBlock), 0, st,
+            hipLaunchKernelGGL((prep_kernel<TREE64, SI, Real2, Real, SReal2, SReal>), dim3(nbs), dim3(kBlock), 0, st,
                                c->keys_sorted, c->perm, pos, mass, c->cnt, c->bsum_u32, (SReal2 *)c->spos,
                                (SReal *)c->smass, c->terms, c->bsum_d3, c->coarse, n, Dm, slots);
-            constexpr bool TSRC = !EXACT && std::is_same<Real2, SReal2>::value;   // fp32 state: terms from the sorted copies
+            constexpr bool TSRC = !TREE64 && std::is_same<Real2, SReal2>::value;   // fp32 state: terms from the sorted copies
             if (nbs <= 8u * kBlock) {
                 // few tiles: every workgroup sums the tile totals before it itself (no scan_top2 launch)
-                hipLaunchKernelGGL((scan_apply2<EXACT, SI, true, TSRC>), dim3(nbs), dim3(kBlock), 0, st, c->cnt, c->bsum_u32,
+                hipLaunchKernelGGL((scan_apply2<TREE64, SI, true, TSRC>), dim3(nbs), dim3(kBlock), 0, st, c->cnt, c->bsum_u32,
                                    c->terms, c->bsum_d3, (int)nbs, n, c->cell_first, c->internal_cap, c->ctr,
                                    (const float2 *)c->spos, (const float *)c->smass);
             } else {
-                hipLaunchKernelGGL(scan_top2, dim3(EXACT ? 1 : 2), dim3(kBlock), 0, st, c->bsum_u32, c->bsum_d3,
+                hipLaunchKernelGGL(scan_top2, dim3(TREE64 ? 1 : 2), dim3(kBlock), 0, st, c->bsum_u32, c->bsum_d3,
                                    (int)nbs, c->ctr);
-                hipLaunchKernelGGL((scan_apply2<EXACT, SI, false, TSRC>), dim3(nbs), dim3(kBlock), 0, st, c->cnt, c->bsum_u32,
+                hipLaunchKernelGGL((scan_apply2<TREE64, SI, false, TSRC>), dim3(nbs), dim3(kBlock), 0, st, c->cnt, c->bsum_u32,
                                    c->terms, c->bsum_d3, (int)nbs, n, c->cell_first, c->internal_cap, c->ctr,
                                    (const float2 *)c->spos, (const float *)c->smass);
             }
@@ -430,21 +438,19 @@ int enqueue_build_t(bh_ctx *c)
     }
 
     // 6. nodes (thread 0 writes the root when nothing is subdivided)
-    if constexpr (EXACT) {
-        // one thread per subdivided cell; I <= (n-1)*Dm and <= internal_cap (at least one thread: the root-only case)
-        const int64_t span = std::max<int64_t>(1, std::min<int64_t>(c->internal_cap, std::max<int64_t>(n - 1, 0) * (int64_t)std::max(1, Dm)));
-        hipLaunchKernelGGL(nodes_exact_kernel, dim3(blocks_for(span, kBlock)), dim3(kBlock), 0, st, c->keys_sorted, c->perm,
+    if constexpr (TREE64) {
+        hipLaunchKernelGGL(nodes_exact_kernel, dim3(blocks_for(cell_span(c), kBlock)), dim3(kBlock), 0, st, c->keys_sorted, c->perm,
                            c->cnt, c->cell_first, pos, mass, c->box, n, Dm, c->internal_cap, c->gd, c->ld, c->self_node,
-                           c->cell_depth, c->com_pending, c->ctr, (c->fast64 || c->exact_thr) ? c->cfg.theta : 0.0,
-                           c->exact_thr ? 1 : 0);
+                           c->cell_depth, c->com_pending, c->ctr, (c->mode == Mode::F64 || c->exact_thresholds) ? c->cfg.theta : 0.0,
+                           c->exact_thresholds ? 1 : 0);
     } else {
         launch_nodes_fast(c, false, st);
     }
     // 7. exact bottom-up mass pass (ComputeMass, project.cu:473-502): ONE launch for small trees (the climb of
     //    com_up_kernel), one launch per depth for large ones, where the climb's coherence traffic costs more
     //    than the launches (measured cross-over ~65k bodies; see com_level_kernel).  Bitwise the same sums.
-    if (EXACT && n > 1 && c->internal_cap > 0) {
-        const int64_t span = std::min<int64_t>(c->internal_cap, std::max<int64_t>(1, (n - 1) * (int64_t)std::max(1, Dm)));
+    if (TREE64 && n > 1 && c->internal_cap > 0) {
+        const int64_t span = cell_span(c);
         if (n <= kComClimbMaxBodies) {
             hipLaunchKernelGGL(com_up_kernel, dim3(blocks_for(span, kBlock)), dim3(kBlock), 0, st, c->gd, c->ld,
                                c->self_node, c->com_pending, c->ctr, c->internal_cap);
@@ -462,8 +468,8 @@ int enqueue_build_t(bh_ctx *c)
 template <int ITEMS>
 static int enqueue_build_items(bh_ctx *c)
 {
-    if (c->exact) return enqueue_build_t<true, true, ITEMS>(c);
-    return c->state64 ? enqueue_build_t<false, true, ITEMS>(c) : enqueue_build_t<false, false, ITEMS>(c);
+    if (c->tree64()) return enqueue_build_t<true, true, ITEMS>(c);
+    return c->state64() ? enqueue_build_t<false, true, ITEMS>(c) : enqueue_build_t<false, false, ITEMS>(c);
 }
 
 int enqueue_build(bh_ctx *c)
@@ -480,6 +486,9 @@ int enqueue_build(bh_ctx *c)
     }
 }
 
+// records in `partial`: one per workgroup of the walk that fills it
+inline int64_t partial_room(const bh_ctx *c) { return std::max<int64_t>(1024, (c->cfg.capacity + kWave - 1) / kWave); }
+
 // fp64 walks (exact and throughput): bodies per wavefront for a launch of `cnt` bodies.  A wave's walk is one dependent chain
 // over the union of its bodies' walks (~900 node visits for 64 bodies, ~150 for one), and up to ~130k bodies the launch cannot
 // fill the GPU's 8,192 wave slots with 64-body waves anyway.  Measured (scripts/bpw_ab.py, profiles/r04_f64/bpw_sweep.txt): the
@@ -488,200 +497,235 @@ int enqueue_build(bh_ctx *c)
 // per wave up to 4,096 bodies, from there 16 bodies per wave or what keeps the launch within ~2,048 waves (more waves than that
 // cost more vector work than the shorter chains return).  Always within what `partial` holds (one record per workgroup).  The
 // bit-exact mode's results do not depend on it, bit for bit.
-static int exact_bodies_per_wave(const bh_ctx *c, int64_t cnt)
+static int fp64_bodies_per_wave(const bh_ctx *c, int64_t cnt)
 {
     // (the throughput walk adds a lane's terms in the order its WAVE meets them: its last bits depend on who shares the wave, like
     // the fp32 split walk's -- BH_FLAG_WALK_NO_SPLIT pins 64 bodies per wave for callers that need launch-size independence)
-    if (c->fast64 && (c->cfg.flags & BH_FLAG_WALK_NO_SPLIT)) return kWave;
+    if (c->mode == Mode::F64 && (c->cfg.flags & BH_FLAG_WALK_NO_SPLIT)) return kWave;
     int b = 1;
     if (c->exact_bpw > 0) b = c->exact_bpw;
-    else if (c->fast64) {
+    else if (c->mode == Mode::F64) {
         while (b < kWave && (int64_t)b * 4096 < cnt) b <<= 1;
     } else if (cnt > 4096) {
         b = 16;
         while (b < kWave && (int64_t)b * 2048 < cnt) b <<= 1;
     }
-    const int64_t room = std::max<int64_t>(1024, (c->cfg.capacity + kWave - 1) / kWave);      // records in `partial`
-    while (b < kWave && (cnt + (int64_t)kWavesPerBlock * b - 1) / ((int64_t)kWavesPerBlock * b) > room) b <<= 1;
+    while (b < kWave && (cnt + (int64_t)kWavesPerBlock * b - 1) / ((int64_t)kWavesPerBlock * b) > partial_room(c)) b <<= 1;
     return b;
 }
 
-int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
+// What the launches of one enqueue_walk share
+struct WalkRange {
+    int64_t lo, hi;            // the owned sorted range
+    int64_t pass;              // bodies per launch (hi - lo: one launch)
+    bool integrate, to_sorted, stats;
+    int part;                  // LET mode: 1 = local tree only, 2 = received trees only, 0 = both
+    double *partial;           // per-workgroup min/max of the new positions, may be null
+    double *slots;             // bounds slot records for the next keys_kernel (bh_bounds.hpp), may be null
+};
+
+enum class WalkKind { F64, ExactBfs, Exact, F32 };
+
+struct WalkChoice {
+    WalkKind kind;
+    bool use_asm;              // the hand-written loop instead of the C++ statement of the same walk
+    int bpw;                   // fp64 cooperative walks: bodies per wavefront
+};
+
+// Which walk a launch of this context runs
+WalkChoice choose_walk(const bh_ctx *c, const WalkRange &w)
 {
-    int64_t lo, hi;
-    owned_range(c, &lo, &hi);
-    if (hi <= lo) return BH_OK;
-    const bool stats = (c->cfg.flags & BH_FLAG_WALK_STATS) != 0;
-    if (part != 2) c->walk_launches = 0;
-    if (integrate) c->slots_valid = false;                         // (the positions change; the fp32 branch may set it again)
-    // a full-range integrating walk also leaves the min/max of the NEW positions per workgroup
-    const bool want_partial = integrate && !to_sorted && lo == 0 && hi == c->n;
-    double *partial = want_partial ? c->partial : nullptr;
-    int per_partial = kBlock;
-    int partial_records = -1;                                      // (a walk whose workgroups do not take a fixed number of bodies says so itself)
-    // N_THREADS (project.cu:5-7, 703: `body_i += N_THREADS`): at most that many bodies are walked at a time -- the
-    // range is taken in passes of n_threads bodies, rounded up to whole 256-thread workgroups, one launch after the
-    // other on the stream, as the reference's threads take their bodies one after the other.  0 (the default):
-    // one pass.  It gives the thread axis of the reference's first scaling experiment (first_scaling_script.sh:
-    // 17-36) a meaning on this hardware: n_threads = 1 is one workgroup at a time.
-    const int64_t pass = c->cfg.n_threads > 0 ? ((int64_t)c->cfg.n_threads + kBlock - 1) / kBlock * kBlock : hi - lo;
-    // one launch over all bodies that integrates: the workgroups also fold their bounds into the slot records the
-    // next keys_kernel reduces (bh_bounds.hpp) -- that build then needs no bounds_final launch
-    const bool want_slots = want_partial && pass == hi - lo && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
-    double *slots = nullptr;
-    if (want_slots) {
-        if (c->slots_dirty)
-            hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
-        slots = c->bslots; c->slots_dirty = true;
-    }
-    if (integrate) c->slots_valid = want_slots;
-    if (c->exact && c->fast64) {
-        if (stats) {
-            if (!c->body_counts) { int rc = dev_alloc(c, &c->body_counts, (size_t)std::max<int64_t>(c->cfg.capacity, 1)); if (rc) return rc; }
-            // (a launch writes the slots of the bodies it walks: an owned range smaller than n, or a walk that returned
-            // early on an overflowed tree, must not leave the others uninitialised)
-            BH_HIP(c, hipMemsetAsync(c->body_counts, 0, (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t), c->stream));
-        }
-        // hand-written loop (walk64_asm): 32-bit byte offsets into the node array; the counting variant and
-        // BH_FLAG_WALK_PORTABLE run the C++ statement of the same loop (same operations, same order, same bits)
-        const bool use_asm = c->walk_asm && !stats && !(c->cfg.flags & BH_FLAG_WALK_PORTABLE) &&
-                             c->node_cap * (int64_t)sizeof(NodeD) < (1ll << 32);
-        const bool deep = 3 * c->Dm + 1 > kWave;                 // (deeper than 21 levels: the two-tier stack)
-        const int bpw = exact_bodies_per_wave(c, std::min(pass, hi - lo));
-        const int per_block = (kF64Block / kWave) * bpw;         // bodies per workgroup
-        for (int64_t plo = lo; plo < hi; plo += pass) {
-            const int64_t phi = std::min(hi, plo + pass);
-            double *pp = partial ? partial + 4 * ((plo - lo) / per_block) : nullptr;
-            WalkF64Args wa{};
-            wa.gd = c->gd; wa.ld = c->ld; wa.perm = c->perm; wa.pos = (double2 *)c->pos; wa.vel = (double2 *)c->vel;
-            wa.mass = (const double *)c->mass; wa.force_out = (double2 *)c->force; wa.lo = plo; wa.hi = phi;
-            wa.G = c->cfg.G; wa.dt = c->cfg.dt; wa.integrate = integrate ? 1 : 0; wa.ctr = c->ctr; wa.partial = pp;
-            wa.body_counts = stats ? c->body_counts : nullptr; wa.slots = slots; wa.bpw = bpw;
-            auto args = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(blocks_for(phi - plo, per_block)), dim3(kF64Block), 0, c->stream, wa);
-                c->walk_launches += 1;
-            };
-            auto pick = [&](auto compat_tag, auto deep_tag) {
-                constexpr bool CP = decltype(compat_tag)::value, DP = decltype(deep_tag)::value;
-                if (stats) args(walk_f64_kernel<CP, true, DP, false>);
-                else if (use_asm) args(walk_f64_kernel<CP, false, DP, true>);
-                else args(walk_f64_kernel<CP, false, DP, false>);
-            };
-            using T = std::true_type; using Fz = std::false_type;
-            if (c->compat) { if (deep) pick(T{}, T{}); else pick(T{}, Fz{}); }
-            else           { if (deep) pick(Fz{}, T{}); else pick(Fz{}, Fz{}); }
-        }
-        per_partial = per_block;
-        BH_HIP(c, hipGetLastError());
-    } else if (c->exact && c->exact_thr && !stats && c->exact_bpw == 0 && pass == hi - lo && hi - lo <= c->bfs_max &&
-               c->node_cap * (int64_t)sizeof(NodeD) < (1ll << 32)) {
+    const bool portable = (c->cfg.flags & BH_FLAG_WALK_PORTABLE) != 0;
+    // the fp64 hand-written loops and the breadth-first walk address the node array with 32-bit byte offsets
+    const bool nodes32 = c->node_cap * (int64_t)sizeof(NodeD) < (1ll << 32);
+    const int64_t cnt = std::min(w.pass, w.hi - w.lo);
+    switch (c->mode) {
+    case Mode::F64:
+        // hand-written loop (walk64_asm); the counting variant and BH_FLAG_WALK_PORTABLE run the C++ statement of the same
+        // loop (same operations, same order, same bits)
+        return {WalkKind::F64, c->walk_asm && !w.stats && !portable && nodes32, fp64_bodies_per_wave(c, cnt)};
+    case Mode::Exact:
         // launches of a few thousand bodies: one wavefront per BODY, its tree breadth-first (walk_exact_bfs_kernel) -- the same
-        // bits as the cooperative walk below, which an explicit BH_EXACT_BPW, the counting variant and the portable walk keep using
-        // a workgroup = four wavefronts, each taking bodies (turn * grid + workgroup) * 4 + wave one after the other; as many
-        // workgroups as `partial` has records (at least 1,024), every wave at most 64 bodies
-        const int64_t cnt = std::min(pass, hi - lo);
-        const int64_t room = std::max<int64_t>(1024, (c->cfg.capacity + kWave - 1) / kWave);
-        const int64_t grid = std::max<int64_t>(std::min<int64_t>(blocks_for(cnt, kWavesPerBlock), room),
-                                               blocks_for(cnt, kWavesPerBlock * kBfsBodiesPerWave));
-        {
-            auto args = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, (double2 *)c->pos,
-                                   (double2 *)c->vel, (const double *)c->mass, (double2 *)c->force, lo, hi, c->cfg.G, c->cfg.dt,
-                                   integrate ? 1 : 0, c->ctr, partial, slots, c->box);
-                c->walk_launches += 1;
-            };
-            const bool big = cnt > 4096;                         // (more interactions per body in larger trees: 384 terms per walk -- 52 KB of LDS per workgroup, three per CU; 512 would leave two)
-            if (c->compat) { if (big) args(walk_exact_bfs_kernel<true, 384>); else args(walk_exact_bfs_kernel<true, 256>); }
-            else           { if (big) args(walk_exact_bfs_kernel<false, 384>); else args(walk_exact_bfs_kernel<false, 256>); }
-        }
-        partial_records = (int)grid;
-        BH_HIP(c, hipGetLastError());
-    } else if (c->exact) {
-        const int bpw = exact_bodies_per_wave(c, std::min(pass, hi - lo));
-        const int per_block = kWavesPerBlock * bpw;              // bodies per workgroup
-        for (int64_t plo = lo; plo < hi; plo += pass) {
-            const int64_t phi = std::min(hi, plo + pass);
-            double *pp = partial ? partial + 4 * ((plo - lo) / per_block) : nullptr;
-            auto args = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(blocks_for(phi - plo, per_block)), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm,
-                                   (double2 *)c->pos, (double2 *)c->vel, (const double *)c->mass,
-                                   (double2 *)c->force, plo, phi, c->cfg.theta, c->cfg.G, c->cfg.dt,
-                                   integrate ? 1 : 0, c->ctr, pp, slots, bpw, c->box);
-                c->walk_launches += 1;
-            };
-            // (the node kernel stored what this walk reads in the size slot: exact thresholds, or the sizes for the portable
-            // walk; the hand-written loop uses 32-bit byte offsets into the node array and carries no counters)
-            const bool use_asm = c->exact_thr && !stats && c->node_cap * (int64_t)sizeof(NodeD) < (1ll << 32);
-            auto pick = [&](auto compat_tag) {
-                constexpr bool CP = decltype(compat_tag)::value;
-                if (!c->exact_thr) { if (stats) args(walk_exact_kernel<CP, true, false, false>); else args(walk_exact_kernel<CP, false, false, false>); }
-                else if (stats) args(walk_exact_kernel<CP, true, true, false>);
-                else if (use_asm) args(walk_exact_kernel<CP, false, true, true>);
-                else args(walk_exact_kernel<CP, false, true, false>);
-            };
-            if (c->compat) pick(std::true_type{}); else pick(std::false_type{});
-        }
-        per_partial = per_block;
-        BH_HIP(c, hipGetLastError());
-    } else {
-        WalkFastArgs a{};
-        a.quads = c->qf; a.aux = c->aux; a.partial = partial; a.spos = c->spos; a.smass = c->smass; a.perm = c->perm;
-        a.pos = (float2 *)c->pos; a.vel = (float2 *)c->vel;
-        a.state64 = c->state64 ? 1 : 0;               // mixed precision: pos/vel point at double2 arrays
-        a.sstate = c->sstate;
-        a.acc_out = (float2 *)c->force; a.ctr = c->ctr;
-        a.lo = lo; a.hi = hi; a.G = (float)c->cfg.G; a.dt = (float)c->cfg.dt;
-        a.integrate = integrate ? 1 : 0; a.to_sorted = to_sorted ? 1 : 0;
-        a.n_trees = c->let_mode ? c->world : 0; a.self_rank = c->let_mode ? c->rank : -1;
-        a.part = part; a.acc_part = c->acc_part;
-        a.forest_base = c->forest_base; a.let_cap = c->let_cap;
-        c->exp.walk_args(a);
-        a.group_cost = (lo == 0 && hi == c->n) ? c->group_cost : nullptr;
-        a.bucket_consts = c->walk_consts;
-        a.body_counts = nullptr;
-        a.slots = slots;
-        if (stats) {
-            if (!c->body_counts) { int rc = dev_alloc(c, &c->body_counts, (size_t)std::max<int64_t>(c->cfg.capacity, 1)); if (rc) return rc; }
-            if (part != 2) BH_HIP(c, hipMemsetAsync(c->body_counts, 0, (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t), c->stream));
-            a.body_counts = c->body_counts;
-        }
-        // the register-lane stack holds 128 entries and pairs entries only while the bound of
-        // walk_tree_asm allows it, so it serves every max_depth <= 32; the LDS stack is the flag's variant
-        const bool lds = (c->cfg.flags & BH_FLAG_LDS_STACK) != 0;
-        a.pair_limit = std::max(0, 116 - 3 * c->Dm);   // the stack bound of walk_tree_asm2 (bh_walk_fast.hip)
-        // few bodies: several waves per 64-body group (bh_walk_fast.hip).  Measured best factor
-        // (scripts/split_ab.sh): 8 up to 32k bodies per launch, 4 up to ~100k, one wave
-        // per group -- the hand-scheduled loop with two quads in flight -- beyond (round 1's compiled loop
-        // lost to the split walk up to 192k; at 131k: 0.097 against 0.102 ms).  BH_WALK_SPLIT overrides (1 = off).
-        int split = (c->cfg.flags & BH_FLAG_WALK_NO_SPLIT) || c->cfg.n_threads > 0 ? 1 : c->walk_split;   // (n_threads: one thread per body)
-        if (split <= 0) {
-            const int64_t groups = (hi - lo + kWave - 1) / kWave;
-            // (a forest walk keeps the split longer: the level-synchronous walk seeds its first frontier with
-            // all the roots, the one-wave loop walks tree after tree -- 8 ranks x 135k bodies: 0.270 vs 0.293 ms;
-            // 4 ranks x 268k: 0.346 vs 0.298)
-            // (measured with the hand-scheduled chunk loop, Plummer, walk ms for split 1 / 2 / 4 / 8 --
-            //  768 groups: .089 .061 .042 .040; 1,536: .094 .073 .059 .074; 2,048: .098 .074 .078 .100;
-            //  3,072: .108 .115 .102 .136; 3,584: .115 .127 .118 .157; profiles/r02_final/split_sweep.txt)
-            split = groups <= (c->let_mode ? 512 : 768) ? 8 : groups <= 3072 ? 4 : 1;
-        }
-        if (3 * c->Dm + 2 > kWave) split = 1;        // the level-synchronous walk's depth-first fallback has 64 entries
+        // bits as the cooperative walk, which an explicit BH_EXACT_BPW, the counting variant and the portable walk keep using
+        if (c->exact_thresholds && !w.stats && c->exact_bpw == 0 && w.pass == w.hi - w.lo && w.hi - w.lo <= c->bfs_max && nodes32)
+            return {WalkKind::ExactBfs, false, 0};
+        // (the node kernel stored what the cooperative walk reads in the size slot: exact thresholds, or the sizes for the
+        // portable walk; the hand-written loop carries no counters)
+        return {WalkKind::Exact, c->exact_thresholds && !w.stats && nodes32, fp64_bodies_per_wave(c, cnt)};
+    default: {
         // hand-scheduled loop: byte offsets into the quad array and the sorted bodies are 32-bit there, and the SGPR
         // offset of s_load is an UNSIGNED 32-bit value on gfx950 (scripts/calib/soffset_calib.hip, profiles/r03_final/
         // soffset_calib.txt: offsets up to 0xf0000100 read base + offset): 4 GiB of quads = 53.6 M.  (Round 2 stopped at
         // 2 GiB, so BASELINE config 5 -- capacity 33.5 M quads -- ran the C++ loop.)
         const int64_t forest_quads = c->let_mode ? c->forest_base + (int64_t)c->world * c->let_cap : c->internal_cap + 1;
-        const bool use_asm = c->walk_asm && !(c->cfg.flags & BH_FLAG_WALK_PORTABLE) &&
-                             forest_quads * (int64_t)sizeof(QuadF) < (1ll << 32) && c->n < (1ll << 28);
-        if (walk_fast_split_effective(a, lds, split)) per_partial = kWave;
-        for (int64_t plo = lo; plo < hi; plo += pass) {
-            a.lo = plo; a.hi = std::min(hi, plo + pass);
-            a.partial = partial ? partial + 4 * ((plo - lo) / per_partial) : nullptr;
-            BH_HIP(c, launch_walk_fast(a, lds, stats, split, use_asm, c->stream));
-            c->walk_launches += 1;
-        }
+        return {WalkKind::F32, c->walk_asm && !portable && forest_quads * (int64_t)sizeof(QuadF) < (1ll << 32) && c->n < (1ll << 28), 0};
     }
-    if (want_partial) c->partial_count = partial_records >= 0 ? partial_records : (int)blocks_for(hi - lo, per_partial);
-    if (!c->exact && lo == 0 && hi == c->n) c->group_cost_valid = true;
+    }
+}
+
+// The launchers, one per walk family: each returns how many `partial` records its workgroups write, or a BH_ERR_* code.
+
+// One launch per pass of w.pass bodies, per_record bodies per `partial` record: launch(lo, hi, workgroups of per_record bodies,
+// the pass's records) returns BH_OK or a BH_ERR_* code
+template <typename Launch>
+int each_pass(bh_ctx *c, const WalkRange &w, int per_record, Launch launch)
+{
+    for (int64_t plo = w.lo; plo < w.hi; plo += w.pass) {
+        const int64_t phi = std::min(w.hi, plo + w.pass);
+        if (int rc = launch(plo, phi, blocks_for(phi - plo, per_record), w.partial ? w.partial + 4 * ((plo - w.lo) / per_record) : nullptr))
+            return rc;
+        c->walk_launches += 1;
+    }
+    return (int)blocks_for(w.hi - w.lo, per_record);
+}
+
+int launch_walk_f64(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
+{
+    const bool deep = 3 * c->Dm + 1 > kWave;                 // (deeper than 21 levels: the two-tier stack)
+    return each_pass(c, w, (kF64Block / kWave) * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid, double *pp) {
+        WalkF64Args wa{};
+        wa.gd = c->gd; wa.ld = c->ld; wa.perm = c->perm; wa.pos = (double2 *)c->pos; wa.vel = (double2 *)c->vel;
+        wa.mass = (const double *)c->mass; wa.force_out = (double2 *)c->force; wa.lo = plo; wa.hi = phi;
+        wa.G = c->cfg.G; wa.dt = c->cfg.dt; wa.integrate = w.integrate ? 1 : 0; wa.ctr = c->ctr; wa.partial = pp;
+        wa.body_counts = w.stats ? c->body_counts : nullptr; wa.slots = w.slots; wa.bpw = k.bpw;
+        dispatch([&](auto compat, auto deep_stack) {
+            constexpr bool CP = decltype(compat)::value, DP = decltype(deep_stack)::value;
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kF64Block), 0, c->stream, wa); };
+            if (w.stats) go(walk_f64_kernel<CP, true, DP, false>);
+            else if (k.use_asm) go(walk_f64_kernel<CP, false, DP, true>);
+            else go(walk_f64_kernel<CP, false, DP, false>);
+        }, c->compat, deep);
+        return BH_OK;
+    });
+}
+
+// a workgroup = four wavefronts, each taking bodies (turn * grid + workgroup) * 4 + wave one after the other; as many
+// workgroups as `partial` has records (at least 1,024), every wave at most 64 bodies
+int launch_walk_exact_bfs(bh_ctx *c, const WalkRange &w)
+{
+    const int64_t cnt = w.hi - w.lo;
+    const int64_t grid = std::max<int64_t>(std::min<int64_t>(blocks_for(cnt, kWavesPerBlock), partial_room(c)),
+                                           blocks_for(cnt, kWavesPerBlock * kBfsBodiesPerWave));
+    // (more interactions per body in larger trees: 384 terms per walk -- 52 KB of LDS per workgroup, three per CU; 512 would leave two)
+    dispatch([&](auto compat, auto big) {
+        hipLaunchKernelGGL((walk_exact_bfs_kernel<decltype(compat)::value, decltype(big)::value ? 384 : 256>), dim3((unsigned)grid),
+                           dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, (double2 *)c->pos, (double2 *)c->vel,
+                           (const double *)c->mass, (double2 *)c->force, w.lo, w.hi, c->cfg.G, c->cfg.dt, w.integrate ? 1 : 0,
+                           c->ctr, w.partial, w.slots, c->box);
+    }, c->compat, cnt > 4096);
+    c->walk_launches += 1;
+    return (int)grid;
+}
+
+int launch_walk_exact(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
+{
+    return each_pass(c, w, kWavesPerBlock * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid, double *pp) {
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, (double2 *)c->pos,
+                               (double2 *)c->vel, (const double *)c->mass, (double2 *)c->force, plo, phi, c->cfg.theta, c->cfg.G,
+                               c->cfg.dt, w.integrate ? 1 : 0, c->ctr, pp, w.slots, k.bpw, c->box);
+        };
+        dispatch([&](auto compat) {
+            constexpr bool CP = decltype(compat)::value;
+            if (!c->exact_thresholds) { if (w.stats) go(walk_exact_kernel<CP, true, false, false>); else go(walk_exact_kernel<CP, false, false, false>); }
+            else if (w.stats) go(walk_exact_kernel<CP, true, true, false>);
+            else if (k.use_asm) go(walk_exact_kernel<CP, false, true, true>);
+            else go(walk_exact_kernel<CP, false, true, false>);
+        }, c->compat);
+        return BH_OK;
+    });
+}
+
+int launch_walk_f32(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
+{
+    WalkFastArgs a{};
+    a.quads = c->qf; a.aux = c->aux; a.partial = w.partial; a.spos = c->spos; a.smass = c->smass; a.perm = c->perm;
+    a.pos = (float2 *)c->pos; a.vel = (float2 *)c->vel;
+    a.state64 = c->state64() ? 1 : 0;             // mixed precision: pos/vel point at double2 arrays
+    a.sstate = c->sstate;
+    a.acc_out = (float2 *)c->force; a.ctr = c->ctr;
+    a.lo = w.lo; a.hi = w.hi; a.G = (float)c->cfg.G; a.dt = (float)c->cfg.dt;
+    a.integrate = w.integrate ? 1 : 0; a.to_sorted = w.to_sorted ? 1 : 0;
+    a.n_trees = c->let_mode ? c->world : 0; a.self_rank = c->let_mode ? c->rank : -1;
+    a.part = w.part; a.acc_part = c->acc_part;
+    a.forest_base = c->forest_base; a.let_cap = c->let_cap;
+    c->exp.walk_args(a);
+    a.group_cost = (w.lo == 0 && w.hi == c->n) ? c->group_cost : nullptr;
+    a.bucket_consts = c->walk_consts;
+    a.slots = w.slots;
+    a.body_counts = w.stats ? c->body_counts : nullptr;
+    // the register-lane stack holds 128 entries and pairs entries only while the bound of
+    // walk_tree_asm allows it, so it serves every max_depth <= 32; the LDS stack is the flag's variant
+    const bool lds = (c->cfg.flags & BH_FLAG_LDS_STACK) != 0;
+    a.pair_limit = std::max(0, 116 - 3 * c->Dm);   // the stack bound of walk_tree_asm2 (bh_walk_fast.hip)
+    // few bodies: several waves per 64-body group (bh_walk_fast.hip).  Measured best factor
+    // (scripts/split_ab.sh): 8 up to 32k bodies per launch, 4 up to ~100k, one wave
+    // per group -- the hand-scheduled loop with two quads in flight -- beyond (round 1's compiled loop
+    // lost to the split walk up to 192k; at 131k: 0.097 against 0.102 ms).  BH_WALK_SPLIT overrides (1 = off).
+    int split = (c->cfg.flags & BH_FLAG_WALK_NO_SPLIT) || c->cfg.n_threads > 0 ? 1 : c->walk_split;   // (n_threads: one thread per body)
+    if (split <= 0) {
+        const int64_t groups = (w.hi - w.lo + kWave - 1) / kWave;
+        // (a forest walk keeps the split longer: the level-synchronous walk seeds its first frontier with
+        // all the roots, the one-wave loop walks tree after tree -- 8 ranks x 135k bodies: 0.270 vs 0.293 ms;
+        // 4 ranks x 268k: 0.346 vs 0.298)
+        // (measured with the hand-scheduled chunk loop, Plummer, walk ms for split 1 / 2 / 4 / 8 --
+        //  768 groups: .089 .061 .042 .040; 1,536: .094 .073 .059 .074; 2,048: .098 .074 .078 .100;
+        //  3,072: .108 .115 .102 .136; 3,584: .115 .127 .118 .157; profiles/r02_final/split_sweep.txt)
+        split = groups <= (c->let_mode ? 512 : 768) ? 8 : groups <= 3072 ? 4 : 1;
+    }
+    if (3 * c->Dm + 2 > kWave) split = 1;        // the level-synchronous walk's depth-first fallback has 64 entries
+    const int per_record = walk_fast_split_effective(a, lds, split) ? kWave : kBlock;
+    return each_pass(c, w, per_record, [&](int64_t plo, int64_t phi, unsigned, double *pp) -> int {
+        a.lo = plo; a.hi = phi; a.partial = pp;
+        BH_HIP(c, launch_walk_fast(a, lds, w.stats, split, k.use_asm, c->stream));
+        return BH_OK;
+    });
+}
+
+int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
+{
+    WalkRange w{};
+    owned_range(c, &w.lo, &w.hi);
+    if (w.hi <= w.lo) return BH_OK;
+    w.integrate = integrate; w.to_sorted = to_sorted; w.part = part;
+    w.stats = (c->cfg.flags & BH_FLAG_WALK_STATS) != 0;
+    if (part != 2) c->walk_launches = 0;
+    // a full-range integrating walk also leaves the min/max of the NEW positions per workgroup
+    if (integrate && !to_sorted && w.lo == 0 && w.hi == c->n) w.partial = c->partial;
+    // N_THREADS (project.cu:5-7, 703: `body_i += N_THREADS`): at most that many bodies are walked at a time -- the
+    // range is taken in passes of n_threads bodies, rounded up to whole 256-thread workgroups, one launch after the
+    // other on the stream, as the reference's threads take their bodies one after the other.  0 (the default):
+    // one pass.  It gives the thread axis of the reference's first scaling experiment (first_scaling_script.sh:
+    // 17-36) a meaning on this hardware: n_threads = 1 is one workgroup at a time.
+    w.pass = c->cfg.n_threads > 0 ? ((int64_t)c->cfg.n_threads + kBlock - 1) / kBlock * kBlock : w.hi - w.lo;
+    // one launch over all bodies that integrates: the workgroups also fold their bounds into the slot records the
+    // next keys_kernel reduces (bh_bounds.hpp) -- that build then needs no bounds_final launch
+    const bool want_slots = w.partial && w.pass == w.hi - w.lo && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
+    if (want_slots) {
+        if (c->slots_dirty)
+            hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
+        w.slots = c->bslots; c->slots_dirty = true;
+    }
+    if (integrate) c->slots_valid = want_slots;                    // (the positions change)
+
+    const WalkChoice k = choose_walk(c, w);
+    if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
+        if (!c->body_counts) { int rc = dev_alloc(c, &c->body_counts, (size_t)std::max<int64_t>(c->cfg.capacity, 1)); if (rc) return rc; }
+        // (a launch writes the slots of the bodies it walks: an owned range smaller than n, or a walk that returned
+        // early on an overflowed tree, must not leave the others uninitialised; part 2 adds to the counts of part 1)
+        if (part != 2) BH_HIP(c, hipMemsetAsync(c->body_counts, 0, (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t), c->stream));
+    }
+    int records = 0;
+    switch (k.kind) {
+    case WalkKind::F64: records = launch_walk_f64(c, w, k); break;
+    case WalkKind::ExactBfs: records = launch_walk_exact_bfs(c, w); break;
+    case WalkKind::Exact: records = launch_walk_exact(c, w, k); break;
+    case WalkKind::F32: records = launch_walk_f32(c, w, k); break;
+    }
+    if (records < 0) return records;
+    BH_HIP(c, hipGetLastError());
+    if (w.partial) c->partial_count = records;
+    if (!c->tree64() && w.lo == 0 && w.hi == c->n) c->group_cost_valid = true;
     return BH_OK;
 }
 
@@ -693,6 +737,25 @@ int check_overflow(bh_ctx *c)
     if (h.overflow || (int64_t)h.n_internal > c->internal_cap)
         return fail(c, BH_ERR_CAPACITY, "tree needs " + std::to_string(1 + 4 * (int64_t)h.n_internal) +
                                         " nodes, node_capacity is " + std::to_string(c->node_cap));
+    return BH_OK;
+}
+
+// bh_upload / bh_initialize: the state arrays hold n new bodies in caller order
+int new_bodies(bh_ctx *c, int64_t n)
+{
+    c->n = n;
+    c->partial_count = 0; c->slots_valid = false;
+    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
+    c->uploaded = true;
+    c->tree_valid = false;
+    c->steps_done = 0;
+    c->orig_identity = true;
+    c->builds = 0;
+    c->group_cost_valid = false;
+    if (c->gid && n > 0) {
+        hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
+        BH_HIP(c, hipGetLastError());
+    }
     return BH_OK;
 }
 
@@ -734,23 +797,22 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     bh_ctx *c = new bh_ctx();
     c->cfg = *cfg;
     c->Dm = cfg->max_depth - 1;
-    c->fast64 = cfg->precision == BH_PRECISION_F64;
-    c->exact = cfg->precision == BH_PRECISION_F64_EXACT || c->fast64;   // (same state, same build)
-    c->state64 = c->exact || cfg->precision == BH_PRECISION_MIXED;
+    c->mode = cfg->precision == BH_PRECISION_F64_EXACT ? Mode::Exact
+            : cfg->precision == BH_PRECISION_F64       ? Mode::F64
+            : cfg->precision == BH_PRECISION_MIXED     ? Mode::Mixed : Mode::F32;
     c->compat = cfg->reference_compat != 0;
     c->device = cfg->device;
-    c->sort_passes = (2 * c->Dm + kRadixBits - 1) / kRadixBits;
     if (const char *e = std::getenv("BH_WALK_SPLIT")) c->walk_split = std::atoi(e);
     if (const char *e = std::getenv("BH_EXACT_BPW")) { const int b = std::atoi(e); c->exact_bpw = (b >= 1 && b <= kWave && (b & (b - 1)) == 0) ? b : 0; }
     if (const char *e = std::getenv("BH_WALK_ASM")) c->walk_asm = std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_EXACT_BFS_MAX")) c->bfs_max = std::max(0, std::atoi(e));
-    c->exact_thr = c->exact && !c->fast64 && c->walk_asm && !(cfg->flags & BH_FLAG_WALK_PORTABLE);
+    c->exact_thresholds = c->mode == Mode::Exact && c->walk_asm && !(cfg->flags & BH_FLAG_WALK_PORTABLE);
     if (const char *e = std::getenv("BH_SORT_PACK")) c->sort_pack = std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_SORT_BUCKET")) c->sort_bucket = std::atoi(e);
     if (const char *e = std::getenv("BH_BUILD_ITEMS")) c->build_items = std::atoi(e);
     if (const char *e = std::getenv("BH_REORDER_EVERY")) c->reorder_every = std::max(0, std::atoi(e));
-    c->hilbert = !c->exact;
-    if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->exact && std::atoi(e) != 0;
+    c->hilbert = !c->tree64();
+    if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
     auto bail = [&](int rc) { g_create_error = c->err; bh_destroy(c); return rc; };
 
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(BH_ERR_DEVICE); }
@@ -769,14 +831,14 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     }
     c->internal_cap = (c->node_cap - 1) / 4;
 
-    const size_t rs = c->state64 ? sizeof(double) : sizeof(float);
+    const size_t rs = c->state64() ? sizeof(double) : sizeof(float);
     int rc = 0;
     auto A = [&](auto **pp, size_t count) { if (!rc) rc = dev_alloc(c, pp, count); };
     { char *t; A(&t, cap * 2 * rs); c->pos = t; }
     { char *t; A(&t, cap * 2 * rs); c->vel = t; }
     { char *t; A(&t, cap * rs); c->mass = t; }
-    { char *t; A(&t, cap * 2 * (c->exact ? sizeof(double) : sizeof(float))); c->force = t; }
-    if (!c->exact) {
+    { char *t; A(&t, cap * 2 * (c->tree64() ? sizeof(double) : sizeof(float))); c->force = t; }
+    if (!c->tree64()) {
         { char *t; A(&t, cap * 2 * rs); c->pos2 = t; }
         { char *t; A(&t, cap * 2 * rs); c->vel2 = t; }
         { char *t; A(&t, cap * rs); c->mass2 = t; }
@@ -795,10 +857,12 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
       A(&c->splitters, kBucketsBig);
       A(&c->sort_dig, (size_t)std::min<int64_t>(cap, kBucketMaxNBig) + 16);
     }
-    A(&c->bsum_u32, std::max<size_t>(blocks_for(cap + 1, kTile), blocks_for(std::min<int64_t>(cap, 1 << 22) + 1, kBlock * kSmallItems)) + 8);
+    // scan scratch (bsum_u32, bsum_d3): one record per scan tile, sized for the smallest tile
+    const size_t scan_tiles = std::max<size_t>(blocks_for(cap + 1, kTile), blocks_for(std::min<int64_t>(cap, 1 << 22) + 1, kBlock * kSmallItems)) + 8;
+    A(&c->bsum_u32, scan_tiles);
     A(&c->partial, 4 * (std::max<size_t>(1024, blocks_for(cap, kWave)) + 2)); A(&c->box, 8); A(&c->bslots, 4 * kBoundSlots);
     A(&c->ctr, 1);
-    if (c->exact) {
+    if (c->tree64()) {
         // (node 0 is the root, the four children of cell r are nodes 1 + 4 r ..: the arrays start three records into their
         // allocations, so that a sibling quad -- 128 bytes of NodeD, 32 of LinkD, what one visit of the fp64 walks loads -- is ONE
         // aligned 128-byte line and half a 64-byte line instead of straddling two and two: profiles/r04_f64/walk_traffic.json
@@ -813,19 +877,19 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
         A(&c->gid, cap); A(&c->group_cost, cap / kWave + 2); A(&c->walk_consts, 4);
         A(&c->coarse, cap / 256 + 2);
         A(&c->spos, cap); A(&c->sstate, cap + 64 * kBlock + 1024); A(&c->smass, cap);
-        A(&c->terms, cap + 1); A(&c->bsum_d3, std::max<size_t>(blocks_for(cap + 1, kTile), blocks_for(std::min<int64_t>(cap, 1 << 22) + 1, kBlock * kSmallItems)) + 8);
+        A(&c->terms, cap + 1); A(&c->bsum_d3, scan_tiles);
     }
     if (rc) return bail(rc);
     if (hipMemset(c->ctr, 0, sizeof(TreeCounters)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
-    if (!c->exact) {
+    if (!c->tree64()) {
         const void *wc[4] = {c->aux, c->spos, c->smass, nullptr};
         if (hipMemcpy(c->walk_consts, wc, sizeof(wc), hipMemcpyHostToDevice) != hipSuccess) { c->err = "hipMemcpy failed"; return bail(BH_ERR_DEVICE); }
     }
-    if (!c->exact && c->exp.create(cap) != hipSuccess) { c->err = "experiment hooks: allocation failed"; return bail(BH_ERR_DEVICE); }
-    for (auto &e : c->ev_step) if (hipEventCreate(&e) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(BH_ERR_DEVICE); }
-    for (auto &e : c->ev_build) if (hipEventCreate(&e) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(BH_ERR_DEVICE); }
-    for (auto &e : c->ev_grp) if (hipEventCreate(&e) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(BH_ERR_DEVICE); }
-    for (auto &e : c->ev_let) if (hipEventCreate(&e) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(BH_ERR_DEVICE); }
+    if (!c->tree64() && c->exp.create(cap) != hipSuccess) { c->err = "experiment hooks: allocation failed"; return bail(BH_ERR_DEVICE); }
+    auto create = [](auto &evs) { for (auto &e : evs) if (hipEventCreate(&e) != hipSuccess) return false; return true; };
+    if (!create(c->ev_step) || !create(c->ev_build) || !create(c->ev_grp) || !create(c->ev_let)) {
+        c->err = "hipEventCreate failed"; return bail(BH_ERR_DEVICE);
+    }
     *out = c;
     return BH_OK;
 }
@@ -837,11 +901,8 @@ void bh_destroy(bh_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->exp.destroy(c->n);
     for (void *p : c->allocs) (void)hipFree(p);
-    for (auto e : c->ev) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_step) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_build) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_grp) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_let) if (e) (void)hipEventDestroy(e);
+    auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
+    destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -864,7 +925,7 @@ int bh_upload(bh_ctx *c, const double *pos, const double *vel, const double *mas
         return fail(c, BH_ERR_ARG, "Requested number of bodies exceeds N_BODIES.");   // project.cu:110-112
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->state64) {
+    if (c->state64()) {
         BH_HIP(c, hipMemcpy(c->pos, pos, n * 2 * sizeof(double), hipMemcpyHostToDevice));
         BH_HIP(c, hipMemcpy(c->vel, vel, n * 2 * sizeof(double), hipMemcpyHostToDevice));
         BH_HIP(c, hipMemcpy(c->mass, mass, n * sizeof(double), hipMemcpyHostToDevice));
@@ -877,21 +938,8 @@ int bh_upload(bh_ctx *c, const double *pos, const double *vel, const double *mas
         for (int64_t i = 0; i < n; ++i) t[i] = (float)mass[i];
         BH_HIP(c, hipMemcpy(c->mass, t.data(), n * sizeof(float), hipMemcpyHostToDevice));
     }
-    BH_HIP(c, hipMemset(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->exact ? sizeof(double) : sizeof(float))));
-    c->n = n;
-    c->partial_count = 0; c->slots_valid = false;
-    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
-    c->uploaded = true;
-    c->tree_valid = false;
-    c->steps_done = 0;
-    c->orig_identity = true;
-    c->builds = 0;
-    c->group_cost_valid = false;
-    if (c->gid && n > 0) {
-        hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
-        BH_HIP(c, hipGetLastError());
-    }
-    return BH_OK;
+    BH_HIP(c, hipMemset(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->tree64() ? sizeof(double) : sizeof(float))));
+    return new_bodies(c, n);
 }
 
 static int download_pairs(bh_ctx *c, const void *dev, double *host, int64_t count, bool is64)
@@ -909,7 +957,7 @@ static int download_pairs(bh_ctx *c, const void *dev, double *host, int64_t coun
 // host array with `per` doubles per body, read from the device in DEVICE order -> caller order
 static int to_caller_order(bh_ctx *c, double *host, int per)
 {
-    if (c->exact || c->orig_identity || c->n == 0) return BH_OK;
+    if (c->tree64() || c->orig_identity || c->n == 0) return BH_OK;
     const int64_t n = c->n;
     std::vector<uint32_t> o(n);
     BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -917,6 +965,13 @@ static int to_caller_order(bh_ctx *c, double *host, int per)
     for (int64_t i = 0; i < n; ++i)
         for (int k = 0; k < per; ++k) host[(size_t)per * o[i] + k] = t[(size_t)per * i + k];
     return BH_OK;
+}
+
+// a state array (`per` values per body) -> host, caller order
+static int download_state(bh_ctx *c, const void *dev, double *host, int per)
+{
+    int rc = download_pairs(c, dev, host, per * c->n, c->state64());
+    return rc ? rc : to_caller_order(c, host, per);
 }
 
 int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lower_m, double higher_m,
@@ -929,7 +984,7 @@ int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lowe
     BH_HIP(c, hipSetDevice(c->device));
     if (n > 0) {
         const unsigned g = blocks_for(n, kBlock);
-        if (c->state64)
+        if (c->state64())
             hipLaunchKernelGGL((init_bodies_kernel<double2, double>), dim3(g), dim3(kBlock), 0, c->stream,
                                (double2 *)c->pos, (double2 *)c->vel, (double *)c->mass, n, seed, kind, lower_m,
                                higher_m, lower_p, higher_p, lower_v, higher_v);
@@ -939,21 +994,8 @@ int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lowe
                                higher_m, lower_p, higher_p, lower_v, higher_v);
         BH_HIP(c, hipGetLastError());
     }
-    BH_HIP(c, hipMemsetAsync(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->exact ? sizeof(double) : sizeof(float)), c->stream));
-    c->n = n;
-    c->partial_count = 0; c->slots_valid = false;
-    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
-    c->uploaded = true;
-    c->tree_valid = false;
-    c->steps_done = 0;
-    c->orig_identity = true;
-    c->builds = 0;
-    c->group_cost_valid = false;
-    if (c->gid && n > 0) {
-        hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
-        BH_HIP(c, hipGetLastError());
-    }
-    return BH_OK;
+    BH_HIP(c, hipMemsetAsync(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->tree64() ? sizeof(double) : sizeof(float)), c->stream));
+    return new_bodies(c, n);
 }
 
 int bh_download_masses(bh_ctx *c, double *mass)
@@ -962,8 +1004,7 @@ int bh_download_masses(bh_ctx *c, double *mass)
     if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_download_masses before bh_upload/bh_initialize");
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = download_pairs(c, c->mass, mass, c->n, c->state64);
-    return rc ? rc : to_caller_order(c, mass, 1);
+    return download_state(c, c->mass, mass, 1);
 }
 
 int bh_sync(bh_ctx *c)
@@ -985,14 +1026,8 @@ int bh_download(bh_ctx *c, double *pos, double *vel)
     int rc = c->tree_valid ? check_overflow(c) : BH_OK;
     if (rc) return rc;
     BH_HIP(c, hipStreamSynchronize(c->stream));
-    rc = download_pairs(c, c->pos, pos, 2 * c->n, c->state64);
-    if (!rc) rc = to_caller_order(c, pos, 2);
-    if (rc) return rc;
-    if (vel) {
-        rc = download_pairs(c, c->vel, vel, 2 * c->n, c->state64);
-        if (!rc) rc = to_caller_order(c, vel, 2);
-    }
-    return rc;
+    rc = download_state(c, c->pos, pos, 2);
+    return rc || !vel ? rc : download_state(c, c->vel, vel, 2);
 }
 
 int bh_build_tree(bh_ctx *c)
@@ -1050,41 +1085,39 @@ int bh_step(bh_ctx *c, int32_t nsteps)
     return BH_OK;
 }
 
+// The device holds forces (fp64 tree) or accelerations (fp32 / mixed); the other is converted with the masses
+// (a = F / m_i: updateAccelerations, project.cu:795-801)
+static int forces_or_accels(bh_ctx *c, double *out, bool forces)
+{
+    BH_HIP(c, hipSetDevice(c->device));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    int rc = download_pairs(c, c->force, out, 2 * c->n, c->tree64());
+    if (rc) return rc;
+    if (forces != c->tree64()) {
+        std::vector<double> m(std::max<int64_t>(c->n, 1));
+        rc = download_pairs(c, c->mass, m.data(), c->n, c->state64());
+        if (rc) return rc;
+        for (int64_t i = 0; i < 2 * c->n; ++i) out[i] = forces ? out[i] * m[i / 2] : out[i] / m[i / 2];
+    }
+    return to_caller_order(c, out, 2);
+}
+
 int bh_get_forces(bh_ctx *c, double *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_get_forces: null array");
-    BH_HIP(c, hipSetDevice(c->device));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = download_pairs(c, c->force, out, 2 * c->n, c->exact);
-    if (rc) return rc;
-    if (!c->exact) {   // fp32 / mixed mode store accelerations; force = a * m_i
-        std::vector<double> m(std::max<int64_t>(c->n, 1));
-        rc = download_pairs(c, c->mass, m.data(), c->n, c->state64);
-        if (rc) return rc;
-        for (int64_t i = 0; i < c->n; ++i) { out[2 * i] *= m[i]; out[2 * i + 1] *= m[i]; }
-    }
-    return to_caller_order(c, out, 2);
+    return forces_or_accels(c, out, true);
 }
 
 int bh_get_accel(bh_ctx *c, double *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_get_accel: null array");
-    BH_HIP(c, hipSetDevice(c->device));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = download_pairs(c, c->force, out, 2 * c->n, c->exact);
-    if (rc) return rc;
-    if (c->exact) {    // exact mode stores forces; a = F / m_i (updateAccelerations, project.cu:795-801)
-        std::vector<double> m(std::max<int64_t>(c->n, 1));
-        BH_HIP(c, hipMemcpy(m.data(), c->mass, c->n * sizeof(double), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < c->n; ++i) { out[2 * i] /= m[i]; out[2 * i + 1] /= m[i]; }
-    }
-    return to_caller_order(c, out, 2);
+    return forces_or_accels(c, out, false);
 }
 
 int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_get_interaction_counts: null array");
-    if ((c->exact && !c->fast64) || !(c->cfg.flags & BH_FLAG_WALK_STATS) || !c->body_counts)
+    if (c->mode == Mode::Exact || !(c->cfg.flags & BH_FLAG_WALK_STATS) || !c->body_counts)
         return fail(c, BH_ERR_STATE, "bh_get_interaction_counts: fp32 / mixed / BH_PRECISION_F64 with BH_FLAG_WALK_STATS, after a walk");
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
@@ -1117,12 +1150,12 @@ static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vect
     std::vector<NodeAux> aux;
     std::vector<uint32_t> perm(std::max<int64_t>(c->n, 1));
     if (c->n > 0) BH_HIP(c, hipMemcpy(perm.data(), c->perm, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (!c->exact && !c->orig_identity && c->n > 0) {          // slots -> the caller's body indices
+    if (!c->tree64() && !c->orig_identity && c->n > 0) {          // slots -> the caller's body indices
         std::vector<uint32_t> o(c->n);
         BH_HIP(c, hipMemcpy(o.data(), c->orig, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (auto &b : perm) b = o[b];
     }
-    if (c->exact) {
+    if (c->tree64()) {
         gd.resize(nn); ld.resize(nn);
         BH_HIP(c, hipMemcpy(gd.data(), c->gd, nn * sizeof(NodeD), hipMemcpyDeviceToHost));
         BH_HIP(c, hipMemcpy(ld.data(), c->ld, nn * sizeof(LinkD), hipMemcpyDeviceToHost));
@@ -1145,11 +1178,11 @@ static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vect
     while (!stack.empty()) {
         const Item it = stack.back();
         stack.pop_back();
-        const int64_t node_limit = c->exact ? nn : 4 * ((int64_t)h.n_internal + 1);
+        const int64_t node_limit = c->tree64() ? nn : 4 * ((int64_t)h.n_internal + 1);
         if (it.node < 0 || it.node >= node_limit) return fail(c, BH_ERR_DEVICE, "corrupt child link in device tree");
         bh_tree_node q{};
         int32_t child;       // id of child 0, or -1
-        if (c->exact) {
+        if (c->tree64()) {
             q.comx = gd[it.node].cx; q.comy = gd[it.node].cy; q.mass = gd[it.node].m;
             q.particle = (double)ld[it.node].occ;
             child = ld[it.node].child;
@@ -1209,8 +1242,7 @@ int bh_write_quadtree_file(bh_ctx *c, const char *path)
     int rc = export_tree_host(c, out, dep);
     if (rc) return rc;
     std::vector<double> pos(std::max<int64_t>(2 * c->n, 2));
-    rc = download_pairs(c, c->pos, pos.data(), 2 * c->n, c->state64);
-    if (!rc) rc = to_caller_order(c, pos.data(), 2);
+    rc = download_state(c, c->pos, pos.data(), 2);
     if (rc) return rc;
     FILE *fp = std::fopen(path, "w");
     if (!fp) return fail(c, BH_ERR_IO, std::string("cannot open ") + path);
@@ -1241,15 +1273,11 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
     out->steps_done = c->steps_done;
     out->walk_launches = (uint64_t)c->walk_launches;
     out->device_bytes = c->device_bytes;
-    {
-        TreeCounters h{};
-        BH_HIP(c, hipMemcpy(&h, c->ctr, sizeof(h), hipMemcpyDeviceToHost));
-        out->sort_spill_buckets = h.sort_spills;
-        out->sort_rerun_buckets = h.sort_reruns;
-    }
+    TreeCounters h{};
+    BH_HIP(c, hipMemcpy(&h, c->ctr, sizeof(h), hipMemcpyDeviceToHost));
+    out->sort_spill_buckets = h.sort_spills;
+    out->sort_rerun_buckets = h.sort_reruns;
     if (c->tree_valid) {
-        TreeCounters h{};
-        BH_HIP(c, hipMemcpy(&h, c->ctr, sizeof(h), hipMemcpyDeviceToHost));
         out->n_internal = h.n_internal;
         out->n_nodes = 1 + 4 * (int64_t)h.n_internal;
         out->visits = h.visits;
@@ -1286,9 +1314,9 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
         // state is fp64); scans: counts in and out, cell starts, terms -> prefix sums; nodes: ~0.72 cells per body,
         // each reading its key window share, ranks and five prefix sums and writing an 80-byte quad
         const int passes = (2 * c->Dm + kSortBits - 1) / kSortBits;
-        const uint64_t keys_b = (c->state64 ? 24u : 16u) + (c->last_sort_packed ? 0u : 4u);
+        const uint64_t keys_b = (c->state64() ? 24u : 16u) + (c->last_sort_packed ? 0u : 4u);
         const uint64_t sort_b = c->last_sort_bucket ? 46u : (uint64_t)passes * (c->last_sort_packed ? 24u : 32u);
-        const uint64_t prep_b = c->state64 ? 76u : 40u, scan_b = c->state64 ? 59u : 47u, nodes_b = c->exact ? 140u : 117u;
+        const uint64_t prep_b = c->state64() ? 76u : 40u, scan_b = c->state64() ? 59u : 47u, nodes_b = c->tree64() ? 140u : 117u;
         out->build_bytes = (uint64_t)c->n * (keys_b + sort_b + prep_b + scan_b + nodes_b);
         out->walk_bytes = out->wave_nodes ? (uint64_t)c->n * 44u + out->wave_nodes * 20u : 0u;
     }
@@ -1335,14 +1363,14 @@ int bh_device_state(bh_ctx *c, void **pos, void **vel, void **mass, int64_t *n, 
     if (vel) *vel = c->vel;
     if (mass) *mass = c->mass;
     if (n) *n = c->n;
-    if (elem_bytes) *elem_bytes = c->state64 ? 8 : 4;
+    if (elem_bytes) *elem_bytes = c->state64() ? 8 : 4;
     return BH_OK;
 }
 
 int bh_device_sorted(bh_ctx *c, void **sorted_state)
 {
     if (!c) return BH_ERR_ARG;
-    if (c->state64) return fail(c, BH_ERR_STATE, "the sorted exchange buffer exists in fp32 mode only");
+    if (c->state64()) return fail(c, BH_ERR_STATE, "the sorted exchange buffer exists in fp32 mode only");
     if (sorted_state) *sorted_state = c->sstate;
     return BH_OK;
 }
@@ -1370,7 +1398,7 @@ int bh_step_local(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
     if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_step_local before bh_upload");
-    if (c->state64) return fail(c, BH_ERR_STATE, "bh_step_local: fp32 mode only");
+    if (c->state64()) return fail(c, BH_ERR_STATE, "bh_step_local: fp32 mode only");
     BH_HIP(c, hipSetDevice(c->device));
     int rc = enqueue_build(c);
     if (rc) return rc;
@@ -1380,7 +1408,7 @@ int bh_step_local(bh_ctx *c)
 int bh_scatter_sorted(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
-    if (c->state64) return fail(c, BH_ERR_STATE, "bh_scatter_sorted: fp32 mode only");
+    if (c->state64()) return fail(c, BH_ERR_STATE, "bh_scatter_sorted: fp32 mode only");
     BH_HIP(c, hipSetDevice(c->device));
     if (c->n > 0) {
         hipLaunchKernelGGL(scatter_sorted_kernel, dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream,
@@ -1409,7 +1437,7 @@ int bh_let_configure(bh_ctx *c, int32_t rank, int32_t world, int64_t let_cap, in
                                    "(a sender writes child links in the receiver's index space)");
     if (forest_base + (int64_t)world * let_cap > 0x7fffffffLL)
         return fail(c, BH_ERR_ARG, "bh_let_configure: forest too large for 32-bit quad indices");
-    if (c->exact) return fail(c, BH_ERR_STATE, "bh_let_configure: fp32 and mixed precision only");
+    if (c->tree64()) return fail(c, BH_ERR_STATE, "bh_let_configure: fp32 and mixed precision only");
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     int rc = 0;
@@ -1453,7 +1481,7 @@ int bh_let_bounds(bh_ctx *c)
     BH_HIP(c, hipSetDevice(c->device));
     if (c->partial_count <= 0) {
         const unsigned nbb = kLetBoxes * kLetBoxParts;
-        if (c->state64)
+        if (c->state64())
             hipLaunchKernelGGL((let_slice_bounds_kernel<double2>), dim3(nbb), dim3(kBlock), 0, c->stream,
                                (const double2 *)c->pos, c->n, c->partial);
         else
@@ -1571,7 +1599,7 @@ int bh_get_ids(bh_ctx *c, int64_t *ids)
 static int check_cuts(bh_ctx *c, const bh_orb_cuts *cuts, const char *who)
 {
     if (!c || !cuts) return fail(c, BH_ERR_ARG, std::string(who) + ": null argument");
-    if (c->exact) return fail(c, BH_ERR_STATE, std::string(who) + ": fp32 and mixed precision only");
+    if (c->tree64()) return fail(c, BH_ERR_STATE, std::string(who) + ": fp32 and mixed precision only");
     if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
     if (cuts->world < 1 || cuts->world > kMaxWorld || cuts->n_cuts != cuts->world - 1)
         return fail(c, BH_ERR_ARG, std::string(who) + ": world must be 1..64 and n_cuts = world - 1");
@@ -1597,7 +1625,7 @@ int bh_orb_histogram(bh_ctx *c, const bh_orb_cuts *cuts, int32_t level, void **h
         const uint32_t *perm = weighted ? c->perm : nullptr;
         const uint32_t *cost = weighted ? c->group_cost : nullptr;
         const unsigned g = blocks_for(c->n, kBlock);
-        if (c->state64)
+        if (c->state64())
             hipLaunchKernelGGL((orb_hist_kernel<double2>), dim3(g), dim3(kBlock), 0, c->stream, (const double2 *)c->pos,
                                perm, cost, c->n, *cuts, (int)level, c->orb_hist);
         else
@@ -1634,7 +1662,7 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
     if (n == 0) { BH_HIP(c, hipStreamSynchronize(c->stream)); return BH_OK; }
     hipStream_t st = c->stream;
     const unsigned g = blocks_for(n, kBlock);
-    if (c->state64)
+    if (c->state64())
         hipLaunchKernelGGL((migrate_classify_kernel<double2>), dim3(g), dim3(kBlock), 0, st, (const double2 *)c->pos, n,
                            *cuts, c->keys[0], c->vals[0]);
     else
@@ -1648,7 +1676,7 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
     hipLaunchKernelGGL((radix_scatter_w<kSortItems, kSortBits>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->vals[0],
                        c->keys[1], c->vals[1], c->radix_counts, c->bsum_sort, n, 0, (int)nbl);
     const uint32_t *orig = c->orig_identity ? nullptr : c->orig;
-    if (c->state64)
+    if (c->state64())
         hipLaunchKernelGGL((migrate_pack_kernel<double2, double>), dim3(g), dim3(kBlock), 0, st, c->vals[1],
                            (const double2 *)c->pos, (const double2 *)c->vel, (const double *)c->mass, orig, c->gid, n,
                            c->mig_send);
@@ -1669,7 +1697,7 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
 int bh_migrate_pointers(bh_ctx *c, void **send, void **recv, int64_t *capacity_records)
 {
     if (!c) return BH_ERR_ARG;
-    if (c->exact) return fail(c, BH_ERR_STATE, "bh_migrate_pointers: fp32 and mixed precision only");
+    if (c->tree64()) return fail(c, BH_ERR_STATE, "bh_migrate_pointers: fp32 and mixed precision only");
     BH_HIP(c, hipSetDevice(c->device));
     int rc = migrate_buffers(c);
     if (rc) return rc;
@@ -1682,14 +1710,14 @@ int bh_migrate_pointers(bh_ctx *c, void **send, void **recv, int64_t *capacity_r
 int bh_migrate_unpack(bh_ctx *c, int64_t n_new)
 {
     if (!c) return BH_ERR_ARG;
-    if (c->exact || !c->mig_recv) return fail(c, BH_ERR_STATE, "bh_migrate_unpack before bh_migrate_pack");
+    if (c->tree64() || !c->mig_recv) return fail(c, BH_ERR_STATE, "bh_migrate_unpack before bh_migrate_pack");
     if (n_new < 0 || n_new > c->cfg.capacity)
         return fail(c, BH_ERR_CAPACITY, "bh_migrate_unpack: " + std::to_string(n_new) + " bodies arrive, capacity is " +
                                         std::to_string(c->cfg.capacity));
     BH_HIP(c, hipSetDevice(c->device));
     if (n_new > 0) {
         const unsigned g = blocks_for(n_new, kBlock);
-        if (c->state64)
+        if (c->state64())
             hipLaunchKernelGGL((migrate_unpack_kernel<double2, double>), dim3(g), dim3(kBlock), 0, c->stream, c->mig_recv,
                                n_new, (double2 *)c->pos, (double2 *)c->vel, (double *)c->mass, (float2 *)c->force, c->gid);
         else
