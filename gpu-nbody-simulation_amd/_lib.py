@@ -55,6 +55,17 @@ class bh_stats_t(C.Structure):
     ]
 
 
+class bh_energy_t(C.Structure):
+    _fields_ = [
+        ("kinetic", C.c_double), ("potential", C.c_double), ("total", C.c_double),
+        ("momentum", C.c_double * 2),
+        ("angular_momentum", C.c_double),
+        ("com", C.c_double * 2),
+        ("mass", C.c_double),
+        ("n_bodies", C.c_int64),
+    ]
+
+
 ORB_BINS = 4096
 ORB_MAX_CUTS = 63
 
@@ -91,6 +102,9 @@ SIGNATURES = {
     "bh_get_interaction_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint32)]),
     "bh_build_info": (C.c_char_p, []),
     "bh_step_times": (C.c_int, [_ctx, _dp, _dp, C.c_int32, C.POINTER(C.c_int32)]),
+    "bh_compute_potential": (C.c_int, [_ctx]),
+    "bh_get_potential": (C.c_int, [_ctx, _dp, C.POINTER(C.c_uint32)]),
+    "bh_energy": (C.c_int, [_ctx, C.POINTER(bh_energy_t)]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

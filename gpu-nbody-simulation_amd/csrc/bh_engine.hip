@@ -17,6 +17,7 @@
 #include "bh_tree.hpp"
 #include "bh_walk_exact.hpp"
 #include "bh_walk_f64.hpp"
+#include "bh_diag.hpp"
 #include "bh_init.hpp"
 #include "bh_let.hpp"
 #include "bh_migrate.hpp"
@@ -136,6 +137,11 @@ struct bh_ctx {
     bool aux_full = false;              // aux[] holds every node's record (after an export), not only the buckets'
     bool group_cost_valid = false;
     uint32_t *body_counts = nullptr;    // BH_FLAG_WALK_STATS: accepted force evaluations per body (device slot order)
+    // diagnostics (bh_diag.hpp), allocated on first use: potential and terms per body (state order), reduction records
+    double *phi = nullptr;
+    uint32_t *phi_counts = nullptr;
+    double *diag_part = nullptr, *diag_out = nullptr, *slots_save = nullptr;
+    bool phi_current = false;           // phi holds the potential of the current state
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -706,9 +712,14 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
             hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
         w.slots = c->bslots; c->slots_dirty = true;
     }
-    if (integrate) c->slots_valid = want_slots;                    // (the positions change)
+    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; }    // (the positions change)
 
     const WalkChoice k = choose_walk(c, w);
+    // the fp64 cooperative walks size bodies per wave by ONE pass: over all passes of n_threads their workgroups can be more
+    // than `partial` has records -- then no records are written and the next build takes the bounds pass
+    if (w.partial && (k.kind == WalkKind::F64 || k.kind == WalkKind::Exact) &&
+        (int64_t)blocks_for(w.hi - w.lo, (k.kind == WalkKind::F64 ? kF64Block / kWave : kWavesPerBlock) * k.bpw) > partial_room(c))
+        w.partial = nullptr;
     if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
         if (!c->body_counts) { int rc = dev_alloc(c, &c->body_counts, (size_t)std::max<int64_t>(c->cfg.capacity, 1)); if (rc) return rc; }
         // (a launch writes the slots of the bodies it walks: an owned range smaller than n, or a walk that returned
@@ -752,6 +763,7 @@ int new_bodies(bh_ctx *c, int64_t n)
     c->orig_identity = true;
     c->builds = 0;
     c->group_cost_valid = false;
+    c->phi_current = false;
     if (c->gid && n > 0) {
         hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
         BH_HIP(c, hipGetLastError());
@@ -1132,6 +1144,140 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
     return BH_OK;
 }
 
+// ---- diagnostics (bh_diag.hpp): potential walk and reductions
+// A tree of the current state is built for the potential walk without perturbing the run: the build runs as a step's build
+// would, except that it never re-orders the state, and afterwards everything a later build reads from an earlier one is put
+// back -- the build count (re-order cadence), samples_n (whether the next sort takes the bucket path), the bounds slot
+// records the last walk folded (copied aside on the device and back) and partial_count.  What the build leaves otherwise --
+// the sorted copies and splitter samples of THIS state, the tree itself -- only changes the splitters of the next bucket
+// sort, whose result is the same permutation whatever the splitters (the keys carry the body index, so there are no ties).
+// The walk writes phi and its own term counts only: force, body_counts, group_cost, partial, the event timings and
+// walk_launches are not touched.
+static int diag_check(bh_ctx *c, const char *what)
+{
+    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(what) + " before bh_upload");
+    if (c->let_mode || c->world > 1)
+        return fail(c, BH_ERR_STATE, std::string(what) + ": the distributed schemes (LET mode, world > 1) have no potential / energy");
+    return BH_OK;
+}
+
+static int diag_alloc(bh_ctx *c)
+{
+    if (c->phi) return BH_OK;
+    const size_t cap = (size_t)std::max<int64_t>(c->cfg.capacity, 1);
+    int rc = dev_alloc(c, &c->phi, cap);
+    if (!rc) rc = dev_alloc(c, &c->phi_counts, cap);
+    if (!rc) rc = dev_alloc(c, &c->diag_part, (size_t)kDiagParts * 2 * kDiagQuantities);
+    if (!rc) rc = dev_alloc(c, &c->diag_out, (size_t)kDiagQuantities);
+    if (!rc) rc = dev_alloc(c, &c->slots_save, (size_t)4 * kBoundSlots);
+    if (rc) { for (void *p : {(void *)c->phi, (void *)c->phi_counts, (void *)c->diag_part, (void *)c->diag_out, (void *)c->slots_save}) dev_free(c, p);
+              c->phi = nullptr; c->phi_counts = nullptr; c->diag_part = c->diag_out = c->slots_save = nullptr; }
+    return rc;
+}
+
+static int enqueue_potential(bh_ctx *c)
+{
+    const int64_t builds = c->builds, samples_n = c->samples_n;
+    const int partial_count = c->partial_count, reorder_every = c->reorder_every;
+    const bool slots_valid = c->slots_valid, slots_dirty = c->slots_dirty;
+    const size_t slot_bytes = (size_t)4 * kBoundSlots * sizeof(double);
+    BH_HIP(c, hipMemcpyAsync(c->slots_save, c->bslots, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
+    c->reorder_every = 0;
+    int rc = enqueue_build(c);
+    c->reorder_every = reorder_every;
+    c->builds = builds; c->samples_n = samples_n; c->partial_count = partial_count;
+    c->slots_valid = slots_valid; c->slots_dirty = slots_dirty;
+    BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (rc) return rc;
+    if (c->n == 0) return BH_OK;
+    const unsigned grid = blocks_for(c->n, kBlock);
+    if (c->tree64()) {
+        const double2 *pos = static_cast<const double2 *>(c->pos);
+        const int accept = c->mode == Mode::F64 ? kAcceptThr : c->exact_thresholds ? kAcceptExactThr : kAcceptSize;
+        dispatch([&](auto compat) {
+            constexpr bool CP = decltype(compat)::value;
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, pos, c->n, c->cfg.theta,
+                                   c->cfg.G, c->ctr, c->phi, c->phi_counts);
+            };
+            if (accept == kAcceptThr) go(potential_f64_kernel<CP, kAcceptThr>);
+            else if (accept == kAcceptExactThr) go(potential_f64_kernel<CP, kAcceptExactThr>);
+            else go(potential_f64_kernel<CP, kAcceptSize>);
+        }, c->compat);
+    } else {
+        hipLaunchKernelGGL(potential_f32_kernel, dim3(grid), dim3(kBlock), 0, c->stream, c->qf, c->aux, c->spos, c->smass, c->perm,
+                           c->n, c->cfg.G, c->ctr, c->phi, c->phi_counts);
+    }
+    BH_HIP(c, hipGetLastError());
+    return BH_OK;
+}
+
+int bh_compute_potential(bh_ctx *c)
+{
+    if (!c) return BH_ERR_ARG;
+    if (int rc = diag_check(c, "bh_compute_potential")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    int rc = diag_alloc(c);
+    if (!rc) rc = enqueue_potential(c);
+    if (!rc) rc = check_overflow(c);
+    c->phi_current = rc == BH_OK;
+    return rc;
+}
+
+int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
+{
+    if (!c || !phi) return fail(c, BH_ERR_ARG, "bh_get_potential: null array");
+    if (int rc = diag_check(c, "bh_get_potential")) return rc;
+    if (!c->phi_current) return fail(c, BH_ERR_STATE, "bh_get_potential: no potential of the current state (bh_compute_potential)");
+    BH_HIP(c, hipSetDevice(c->device));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    const int64_t n = c->n;
+    if (n == 0) return BH_OK;
+    BH_HIP(c, hipMemcpy(phi, c->phi, n * sizeof(double), hipMemcpyDeviceToHost));
+    int rc = to_caller_order(c, phi, 1);
+    if (rc || !counts) return rc;
+    std::vector<uint32_t> t(n);
+    BH_HIP(c, hipMemcpy(t.data(), c->phi_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (c->tree64() || c->orig_identity) { std::memcpy(counts, t.data(), n * sizeof(uint32_t)); return BH_OK; }
+    std::vector<uint32_t> o(n);
+    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) counts[o[i]] = t[i];
+    return BH_OK;
+}
+
+int bh_energy(bh_ctx *c, bh_energy_t *out)
+{
+    if (!c || !out) return fail(c, BH_ERR_ARG, "bh_energy: null argument");
+    if (int rc = diag_check(c, "bh_energy")) return rc;
+    if (!c->phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
+    BH_HIP(c, hipSetDevice(c->device));
+    auto go = [&](auto real2) {
+        using Real2 = decltype(real2);
+        using Real = decltype(Real2{}.x);
+        hipLaunchKernelGGL((energy_partial_kernel<Real2, Real>), dim3(kDiagParts), dim3(kBlock), 0, c->stream,
+                           static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass),
+                           c->phi, c->n, c->diag_part);
+    };
+    if (c->state64()) go(double2{}); else go(float2{});
+    hipLaunchKernelGGL(energy_final_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->diag_part, c->diag_out);
+    BH_HIP(c, hipGetLastError());
+    double q[kDiagQuantities];
+    BH_HIP(c, hipMemcpyAsync(q, c->diag_out, sizeof(q), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    bh_energy_t e{};
+    e.mass = q[0];
+    e.com[0] = q[0] != 0.0 ? q[1] / q[0] : 0.0;
+    e.com[1] = q[0] != 0.0 ? q[2] / q[0] : 0.0;
+    e.momentum[0] = q[3]; e.momentum[1] = q[4];
+    e.angular_momentum = q[5];
+    e.kinetic = 0.5 * q[6];
+    e.potential = 0.5 * q[7];
+    e.total = e.kinetic + e.potential;
+    e.n_bodies = c->n;
+    *out = e;
+    return BH_OK;
+}
+
 // ---- tree export: DFS pre-order, children in index order (TraverseTreeToFile, project.cu:504-534)
 static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vector<int32_t> &depth)
 {
@@ -1415,7 +1561,7 @@ int bh_scatter_sorted(bh_ctx *c)
                            c->perm, c->sstate, (float2 *)c->pos, (float2 *)c->vel, c->n);
         BH_HIP(c, hipGetLastError());
     }
-    c->partial_count = 0; c->slots_valid = false;
+    c->partial_count = 0; c->slots_valid = false; c->phi_current = false;
     c->steps_done += 1;
     return BH_OK;
 }
@@ -1728,6 +1874,7 @@ int bh_migrate_unpack(bh_ctx *c, int64_t n_new)
     c->n = n_new;
     c->partial_count = 0; c->slots_valid = false;
     c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
+    c->phi_current = false;
     c->tree_valid = false;
     c->orig_identity = true;                                // arrival order is the caller order from here on
     c->builds = 0;

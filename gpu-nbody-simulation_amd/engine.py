@@ -80,6 +80,19 @@ class BhStats:
     walk_launches: int = 0      # walk kernel launches of the last step (1, or the passes of n_threads)
 
 
+@dataclass
+class BhEnergy:
+    """bh_energy_t: energy, momentum and angular momentum of the current state (fp64 device reductions)."""
+    kinetic: float               # 1/2 sum m |v|^2
+    potential: float             # 1/2 sum m_i phi_i, over the force walk's terms
+    total: float
+    momentum: tuple              # (px, py) = sum m v
+    angular_momentum: float      # sum m (x vy - y vx), about the origin
+    com: tuple                   # centre of mass
+    mass: float
+    n_bodies: int
+
+
 def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -180,6 +193,24 @@ class BarnesHutEngine:
         c = np.zeros(max(self.n, 1), dtype=np.uint32)
         self._check(self._lib.bh_get_interaction_counts(self._h, c.ctypes.data_as(C.POINTER(C.c_uint32))))
         return c[:self.n]
+
+    # -- diagnostics ------------------------------------------------------------------------
+    def potential(self, with_counts: bool = False):
+        """Potential per unit mass of every body (caller order) over the force walk's terms of the current state;
+        with_counts: also the terms summed per body.  Builds a tree; the run is not perturbed."""
+        self._check(self._lib.bh_compute_potential(self._h))
+        phi = np.zeros(max(self.n, 1))
+        cnt = np.zeros(max(self.n, 1), dtype=np.uint32) if with_counts else None
+        self._check(self._lib.bh_get_potential(self._h, _dptr(phi),
+                                               cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if with_counts else None))
+        return (phi[:self.n], cnt[:self.n]) if with_counts else phi[:self.n]
+
+    def energy(self) -> BhEnergy:
+        """Kinetic, potential and total energy, momentum, angular momentum, centre of mass of the current state."""
+        e = _lib.bh_energy_t()
+        self._check(self._lib.bh_energy(self._h, C.byref(e)))
+        return BhEnergy(e.kinetic, e.potential, e.total, (e.momentum[0], e.momentum[1]), e.angular_momentum,
+                        (e.com[0], e.com[1]), e.mass, e.n_bodies)
 
     # -- tree output ------------------------------------------------------------------------
     def export_tree(self):

@@ -72,14 +72,17 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      theta: float = THETA, g: float = G, delta_t: float = DELTA_T,
                      max_depth: int = QUADTREE_MAX_DEPTH, precision: Precision = Precision.F64_EXACT,
                      reference_compat: bool = True, out_dir: str = ".", device: int = 0,
-                     positions_file: str | None = None):
+                     positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
     project.cu:918, 1010; the caller gets the same values as the first return value).
     positions_file: also write the trajectory as runSimulationCpu does into positions_cpu.txt
     (savePositions, project.cu:855-863, 876, 909: `t i x y ` per body, before the first step and
-    after every step); this downloads the positions every step."""
+    after every step); this downloads the positions every step.
+    energy_file: also write the diagnostics of the state (BarnesHutEngine.energy) before the first step, after every
+    energy_every-th step and after the last one, one line each: `step,t,kinetic,potential,total,px,py,Lz` (%.17g).
+    The steps in between still run batched, and the diagnostics are not part of gpu_parallel_duration_us."""
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -97,8 +100,17 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         if positions_file is not None:
             traj = open(os.path.join(out_dir, positions_file) if not os.path.isabs(positions_file) else positions_file, "w")
             _write_frame(traj, absolute_t, np.asarray(positions, dtype=np.float64))
+        energy = None
+        if energy_file is not None:
+            energy = open(os.path.join(out_dir, energy_file) if not os.path.isabs(energy_file) else energy_file, "w")
+        done = 0
 
-        def advance(k):
+        def sample():
+            e = eng.energy()
+            energy.write(",".join([str(done)] + ["%.17g" % v for v in (done * delta_t, e.kinetic, e.potential, e.total,
+                                                                       e.momentum[0], e.momentum[1], e.angular_momentum)]) + "\n")
+
+        def steps(k):
             nonlocal gpu_parallel_us, absolute_t
             if k <= 0:
                 return
@@ -111,6 +123,20 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 gpu_parallel_us += eng.stats().last_step_ms * 1e3
                 absolute_t += delta_t
                 _write_frame(traj, absolute_t, eng.download()[0])
+
+        def advance(k):
+            # (with an energy file: batches that end at the sampled steps)
+            nonlocal done
+            while k > 0:
+                j = k if energy is None or energy_every <= 0 else min(k, energy_every - done % energy_every)
+                steps(j)
+                done += j
+                k -= j
+                if energy is not None and (done == n_simulations or (energy_every > 0 and done % energy_every == 0)):
+                    sample()
+
+        if energy is not None:
+            sample()
 
         step = 0
         while step < n_simulations:
@@ -131,6 +157,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         pos, vel = eng.download()
         if traj is not None:
             traj.close()
+        if energy is not None:
+            energy.close()
     return pos, vel, gpu_parallel_us
 
 
@@ -152,6 +180,11 @@ def _parse(argv):
                          "gpu: initializeGpu (on-device generator); auto: files when masses_init.txt "
                          "exists, else gpu -- the reference as shipped calls initializeGpu")
     ap.add_argument("--positions-file", default=None, help="also write the trajectory (savePositions format)")
+    ap.add_argument("--energy-file", default=None, metavar="PATH",
+                    help="also write step,t,kinetic,potential,total,px,py,Lz before the first step, every "
+                         "--energy-every steps and after the last")
+    ap.add_argument("--energy-every", type=int, default=0, metavar="K",
+                    help="steps between two lines of --energy-file (0: first and last state only)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -213,7 +246,8 @@ def main(argv=None) -> int:
         masses, positions, velocities, mac["N_SIMULATIONS"], n_threads=mac["N_THREADS"],
         theta=a.theta, max_depth=a.max_depth,
         precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32,
-        reference_compat=not a.no_compat, positions_file=a.positions_file)
+        reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
+        energy_every=a.energy_every)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -231,6 +231,40 @@ int bh_get_accel(bh_ctx *ctx, double *accel);
  * Needs BH_FLAG_WALK_STATS; fp32, mixed precision and BH_PRECISION_F64; caller order. */
 int bh_get_interaction_counts(bh_ctx *ctx, uint32_t *counts);
 
+/* --- diagnostics: potential, energy, momentum --------------------------------------------
+ * The reference has NO potential or energy at all (project.cu computes forces only); these entry points are new.
+ * phi_i = -G sum_j M_j / d_ij over exactly the terms the precision's force walk takes for body i -- the term set of
+ * computeForces (project.cu:617-658): the `mass <= 1e-15` cut-off, the same acceptance decisions, the self skip
+ * (`occ == i`, and `occ + 2 == -i` under reference_compat), depth-cap aggregates, fp32 bucket leaves body by body.
+ * d is the force walk's distance: sqrt(d2) + 1e-15 in the fp64 precisions (project.cu:630-634), the fp32 walk's
+ * 1 / rsq(d2) in BH_PRECISION_F32 / MIXED (fp32 terms, fp64 sums).  Single GPU: a context in LET mode or with
+ * world > 1 gets BH_ERR_STATE.
+ * The diagnostics do not perturb the run: a following bh_step computes the trajectory bit for bit as it would have
+ * without them, in every precision.  They build their own tree of the current state (which bh_export_tree then
+ * exports) but leave the forces, interaction counts, step timings and walk_launches of the last force walk as they
+ * were: bh_get_forces still returns the forces of the last bh_step / bh_compute_forces.  The device buffers are
+ * allocated on first use (bh_stats.device_bytes grows then, not before). */
+typedef struct bh_energy_t {
+    double kinetic, potential, total;   /* 1/2 sum m |v|^2, 1/2 sum m_i phi_i, their sum        */
+    double momentum[2];                 /* sum m v                                              */
+    double angular_momentum;            /* sum m (x v_y - y v_x), about the origin              */
+    double com[2];                      /* sum m x / sum m                                      */
+    double mass;                        /* sum m                                                */
+    int64_t n_bodies;
+} bh_energy_t;
+
+/* Builds the tree of the CURRENT state and runs the potential walk (one launch over all bodies, whatever
+ * n_threads); the state is not advanced. */
+int bh_compute_potential(bh_ctx *ctx);
+/* phi[n] (per unit mass) and, if counts != NULL, the terms summed per body -- equal to the force walk's per-body
+ * interaction counts (project.cu:651-658 once per accepted node); caller order.  BH_ERR_STATE unless the last
+ * bh_compute_potential / bh_energy saw the current state. */
+int bh_get_potential(bh_ctx *ctx, double *phi, uint32_t *counts);
+/* Runs bh_compute_potential unless the potential is current, then deterministic fp64 reductions on the device
+ * (fixed-shape partials, Neumaier-compensated, folded in a fixed order: two calls on the same state return the
+ * same bits).  Only the final sums reach the host. */
+int bh_energy(bh_ctx *ctx, bh_energy_t *out);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
