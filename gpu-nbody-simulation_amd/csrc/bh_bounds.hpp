@@ -1,20 +1,18 @@
-// bh_bounds.hpp -- workgroup min/max of positions, shared by the tree build and both walk kernels.
+// bh_bounds.hpp -- the root box's bounds records, shared by the tree build and the walk kernels.
 #pragma once
 
 #include "bh_prims.hpp"
 
 namespace bh {
 
-// Block-level min/max of one position per thread -> partial[block]; called from the walk kernels'
-// epilogue so that the NEXT step's root box needs no pass over the bodies.  `partial` points at
-// this workgroup's four doubles.  All threads of the block must call it (it synchronises).
-// `slots` (may be null): kBoundSlots running {xlo, xhi, ylo, yhi} records that the workgroups of a launch fold their
-// bounds into with four atomics each (slot = workgroup index mod kBoundSlots).  The next build's keys_kernel reduces
-// those 64 records in every one of its workgroups -- 2 KB from L2 -- instead of waiting for a one-workgroup launch
-// that reduces thousands of partials (bounds_final: a 4 us dependent launch feeding 64 bytes); prep_kernel, two launches
-// on, puts the slots back to +-inf (no reader counter: it was 4,100 atomics on one word).  Records that are still all
-// +-inf when keys_kernel reads them mean that the walk returned at once on an overflowed tree: the box in memory stays.
-// min / max are exact and order-free: the box is the same, bit for bit.
+// The root box of step s+1 is the min/max of the positions that step s's walk wrote.  Outside LET mode it is kept in
+// kBoundSlots running {xlo, xhi, ylo, yhi} records: every workgroup of an integrating walk over all bodies -- in however many
+// passes -- folds its min/max into one of them with four atomics (slot = workgroup index mod kBoundSlots).  When no walk has
+// left the bounds (the first build after an upload, n < 2), the positions pass bounds_partial folds them in instead.  The next
+// build's keys_kernel reduces the 64 records in every one of its workgroups -- 2 KB from L2 -- pads the box and clears the
+// step's counters; prep_kernel, two launches on, puts the records back to +-inf (no reader counter: it was 4,100 atomics on one
+// word).  Records from a walk that are still all +-inf mean that the walk returned at once on an overflowed tree: the box in
+// memory stays.  min / max are exact and order-free: any set of workgroups gives the same box, bit for bit.
 constexpr int kBoundSlots = 64;
 __device__ __forceinline__ void bounds_to_slot(double xlo, double xhi, double ylo, double yhi, double *slots, uint32_t group)
 {
@@ -22,12 +20,12 @@ __device__ __forceinline__ void bounds_to_slot(double xlo, double xhi, double yl
     atomicMin(s + 0, xlo); atomicMax(s + 1, xhi); atomicMin(s + 2, ylo); atomicMax(s + 3, yhi);
 }
 
-__device__ __forceinline__ void block_bounds_to_partial(bool valid, double x, double y,
-                                                        double *__restrict__ partial, double *slots = nullptr)
+// Block-level min/max of per-thread bounds, folded into `slots` (may be null); `partial` (may be null: only the fp32 walk in LET
+// mode passes it) also gets this workgroup's four doubles.  All threads of the block must call it (it synchronises).
+__device__ __forceinline__ void block_bounds(double xlo, double xhi, double ylo, double yhi, double *slots,
+                                             double *__restrict__ partial = nullptr)
 {
     __shared__ double sm[4][kWavesPerBlock];
-    double xlo = valid ? x : INFINITY, xhi = valid ? x : -INFINITY;
-    double ylo = valid ? y : INFINITY, yhi = valid ? y : -INFINITY;
     xlo = wave_min(xlo); xhi = wave_max(xhi); ylo = wave_min(ylo); yhi = wave_max(yhi);
     if (lane_id() == 0) { sm[0][wave_id()] = xlo; sm[1][wave_id()] = xhi; sm[2][wave_id()] = ylo; sm[3][wave_id()] = yhi; }
     __syncthreads();
@@ -36,9 +34,14 @@ __device__ __forceinline__ void block_bounds_to_partial(bool valid, double x, do
             xlo = (sm[0][w] < xlo) ? sm[0][w] : xlo;  xhi = (xhi < sm[1][w]) ? sm[1][w] : xhi;
             ylo = (sm[2][w] < ylo) ? sm[2][w] : ylo;  yhi = (yhi < sm[3][w]) ? sm[3][w] : yhi;
         }
-        partial[0] = xlo; partial[1] = xhi; partial[2] = ylo; partial[3] = yhi;
+        if (partial) { partial[0] = xlo; partial[1] = xhi; partial[2] = ylo; partial[3] = yhi; }
         if (slots) bounds_to_slot(xlo, xhi, ylo, yhi, slots, blockIdx.x);
     }
+}
+// ... of one position per thread (none where !valid)
+__device__ __forceinline__ void block_bounds(bool valid, double x, double y, double *slots, double *__restrict__ partial = nullptr)
+{
+    block_bounds(valid ? x : INFINITY, valid ? x : -INFINITY, valid ? y : INFINITY, valid ? y : -INFINITY, slots, partial);
 }
 
 // The constants of keys_kernel's one-multiply cell lookup (bh_tree.hpp, key_of_fast), written behind the root

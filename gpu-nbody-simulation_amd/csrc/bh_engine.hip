@@ -80,9 +80,9 @@ struct bh_ctx {
     uint16_t *sort_dig = nullptr;  // bucket of every key (written by the histogram, read by the scatter)
     int build_items = 0;           // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
     bool hilbert = false;                // fp32 mode: Hilbert-ordered keys (BH_HILBERT=0 disables, A/B)
-    int partial_count = 0;         // > 0: partial[] holds per-workgroup min/max of the current positions
+    int partial_count = 0;         // LET mode: > 0: partial[] holds per-workgroup min/max of the current positions
     double *bslots = nullptr;      // kBoundSlots running bounds records (bh_bounds.hpp)
-    bool slots_valid = false;      // the last full-range fp32 walk folded the bounds of the current positions into bslots
+    bool slots_valid = false;      // the last walk folded the bounds of the current positions into bslots
     bool slots_dirty = true;       // bslots may hold something else than +-inf (written, not yet consumed by keys_kernel)
 
     // state (double2/double or float2/float).  Exact mode: caller order.  fp32 / mixed: DEVICE order --
@@ -272,6 +272,13 @@ static void launch_nodes_fast(bh_ctx *c, bool full_aux, hipStream_t st)
     c->aux_full = full_aux;
 }
 
+// before the bounds are folded into the slot records (bh_bounds.hpp): every record +-inf
+void clean_slots(bh_ctx *c)
+{
+    if (c->slots_dirty) hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
+    c->slots_dirty = true;
+}
+
 template <bool TREE64, bool STATE64 = TREE64, int ITEMS = kItems>
 int enqueue_build_t(bh_ctx *c)
 {
@@ -285,22 +292,20 @@ int enqueue_build_t(bh_ctx *c)
     const Real2 *pos = static_cast<const Real2 *>(c->pos);     // (re-read after a reorder)
     const Real *mass = static_cast<const Real *>(c->mass);
 
-    // 1. root box (ComputeRootBounds, project.cu:536-573); the per-workgroup partials usually
-    //    come from the previous step's walk epilogue
-    const bool from_slots = !c->external_box && c->slots_valid && n >= 2;
-    double *slots = from_slots ? c->bslots : nullptr;
-    if (from_slots) {
-        c->partial_count = 0; c->slots_valid = false; c->slots_dirty = false;   // (keys_kernel below consumes and resets them)
-    } else if (!c->external_box) {
-        const bool from_walk = c->partial_count > 0;
+    // 1. root box (ComputeRootBounds, project.cu:536-573): the min/max of the positions is in the bounds slot records
+    //    (bh_bounds.hpp) -- folded by the previous step's walk, or here by bounds_partial when no walk has left it --
+    //    and keys_kernel reduces and pads it (LET mode: let_box_kernel has set the global box and cleared the counters)
+    const bool from_walk = c->slots_valid;
+    double *slots = c->external_box ? nullptr : c->bslots;
+    if (slots) {
         if (!from_walk) {
             const unsigned nbb = std::max(1u, std::min(1024u, blocks_for(n, kBlock)));
-            hipLaunchKernelGGL((bounds_partial<Real2>), dim3(nbb), dim3(kBlock), 0, st, pos, n, c->partial);
-            c->partial_count = (int)nbb;
+            clean_slots(c);
+            hipLaunchKernelGGL((bounds_partial<Real2>), dim3(nbb), dim3(kBlock), 0, st, pos, n, slots);
         }
-        hipLaunchKernelGGL(bounds_final, dim3(1), dim3(kBlock), 0, st, c->partial, c->partial_count, c->box, c->ctr, Dm, from_walk ? 1 : 0);
-        c->partial_count = 0; c->slots_valid = false;
-    }   // else: let_box_kernel has set the global box and cleared the counters
+        c->slots_valid = false;
+        if (n > 0) c->slots_dirty = false;                       // (prep_kernel puts them back to +-inf)
+    }
 
     if (n > 0) {
         // 2. keys by fp64 bisection, 3. stable radix sort
@@ -330,10 +335,11 @@ int enqueue_build_t(bh_ctx *c)
                 // samples: the previous build's sorted positions -- the fp32 walk's copy, or through the previous perm in the exact modes
                 hipLaunchKernelGGL((keys_kernel<Real2, H, P, F>), dim3(nkb + (smp ? ns / kWave : 0)), dim3(kBlock), 0, st, pos, c->box,
                                    c->keys[0], c->vals[0], n, Dm, (smp && !TREE64) ? (const float2 *)c->spos : nullptr, c->splitters, nb, ns,
-                                   slots, c->ctr, smp ? c->bsum_sort : nullptr, smp ? nb : 0, (smp && TREE64) ? c->perm : nullptr);
+                                   slots, c->ctr, smp ? c->bsum_sort : nullptr, smp ? nb : 0, (smp && TREE64) ? c->perm : nullptr,
+                                   from_walk ? 1 : 0);
             };
             // (exact mode and BH_HILBERT=0: child-index keys, packed all the same)
-            dispatch(keys_launch, from_slots, pack, c->hilbert);
+            dispatch(keys_launch, slots != nullptr, pack, c->hilbert);
         }
         if (c->time_groups) (void)hipEventRecord(c->ev_grp[0], st);
         const unsigned nbl = blocks_for(n, ITEMS == kItems ? kSortTile : TILE);
@@ -438,6 +444,9 @@ int enqueue_build_t(bh_ctx *c)
         c->samples_n = n;                                        // spos (exact modes: perm): this build's sorted order
         if (c->time_groups) (void)hipEventRecord(c->ev_grp[2], st);
     } else {
+        if (slots)          // no keys: one workgroup still writes the box and clears the counters
+            hipLaunchKernelGGL((keys_kernel<Real2, false, false, true>), dim3(1), dim3(kBlock), 0, st, pos, c->box, c->keys[0],
+                               c->vals[0], n, Dm, nullptr, nullptr, 0, 0, slots, c->ctr);
         c->keys_sorted = c->keys[0];
         c->perm = c->vals[0];
         if (c->time_groups) for (auto e : c->ev_grp) (void)hipEventRecord(e, st);
@@ -492,17 +501,14 @@ int enqueue_build(bh_ctx *c)
     }
 }
 
-// records in `partial`: one per workgroup of the walk that fills it
-inline int64_t partial_room(const bh_ctx *c) { return std::max<int64_t>(1024, (c->cfg.capacity + kWave - 1) / kWave); }
-
 // fp64 walks (exact and throughput): bodies per wavefront for a launch of `cnt` bodies.  A wave's walk is one dependent chain
 // over the union of its bodies' walks (~900 node visits for 64 bodies, ~150 for one), and up to ~130k bodies the launch cannot
 // fill the GPU's 8,192 wave slots with 64-body waves anyway.  Measured (scripts/bpw_ab.py, profiles/r04_f64/bpw_sweep.txt): the
 // best number of waves is ~4,096 for the throughput walk: the smallest power of two that stays below that.  The bit-exact walk
 // (round 4's assembly loop, ~50 vector instructions per visit; scripts/bpw_ab.py -> profiles/r04_exact/bpw_sweep.txt): one body
 // per wave up to 4,096 bodies, from there 16 bodies per wave or what keeps the launch within ~2,048 waves (more waves than that
-// cost more vector work than the shorter chains return).  Always within what `partial` holds (one record per workgroup).  The
-// bit-exact mode's results do not depend on it, bit for bit.
+// cost more vector work than the shorter chains return).  BH_EXACT_BPW sets it for both walks.  The bit-exact mode's results do
+// not depend on it, bit for bit.
 static int fp64_bodies_per_wave(const bh_ctx *c, int64_t cnt)
 {
     // (the throughput walk adds a lane's terms in the order its WAVE meets them: its last bits depend on who shares the wave, like
@@ -516,7 +522,6 @@ static int fp64_bodies_per_wave(const bh_ctx *c, int64_t cnt)
         b = 16;
         while (b < kWave && (int64_t)b * 2048 < cnt) b <<= 1;
     }
-    while (b < kWave && (cnt + (int64_t)kWavesPerBlock * b - 1) / ((int64_t)kWavesPerBlock * b) > partial_room(c)) b <<= 1;
     return b;
 }
 
@@ -526,7 +531,7 @@ struct WalkRange {
     int64_t pass;              // bodies per launch (hi - lo: one launch)
     bool integrate, to_sorted, stats;
     int part;                  // LET mode: 1 = local tree only, 2 = received trees only, 0 = both
-    double *partial;           // per-workgroup min/max of the new positions, may be null
+    double *partial;           // LET mode, fp32 walk: per-workgroup min/max of the new positions (bh_let_bounds), may be null
     double *slots;             // bounds slot records for the next keys_kernel (bh_bounds.hpp), may be null
 };
 
@@ -569,30 +574,28 @@ WalkChoice choose_walk(const bh_ctx *c, const WalkRange &w)
     }
 }
 
-// The launchers, one per walk family: each returns how many `partial` records its workgroups write, or a BH_ERR_* code.
+// The launchers, one per walk family: each returns BH_OK or a BH_ERR_* code.
 
-// One launch per pass of w.pass bodies, per_record bodies per `partial` record: launch(lo, hi, workgroups of per_record bodies,
-// the pass's records) returns BH_OK or a BH_ERR_* code
+// One launch per pass of w.pass bodies: launch(lo, hi, workgroups of per_group bodies) returns BH_OK or a BH_ERR_* code
 template <typename Launch>
-int each_pass(bh_ctx *c, const WalkRange &w, int per_record, Launch launch)
+int each_pass(bh_ctx *c, const WalkRange &w, int per_group, Launch launch)
 {
     for (int64_t plo = w.lo; plo < w.hi; plo += w.pass) {
         const int64_t phi = std::min(w.hi, plo + w.pass);
-        if (int rc = launch(plo, phi, blocks_for(phi - plo, per_record), w.partial ? w.partial + 4 * ((plo - w.lo) / per_record) : nullptr))
-            return rc;
+        if (int rc = launch(plo, phi, blocks_for(phi - plo, per_group))) return rc;
         c->walk_launches += 1;
     }
-    return (int)blocks_for(w.hi - w.lo, per_record);
+    return BH_OK;
 }
 
 int launch_walk_f64(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
 {
     const bool deep = 3 * c->Dm + 1 > kWave;                 // (deeper than 21 levels: the two-tier stack)
-    return each_pass(c, w, (kF64Block / kWave) * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid, double *pp) {
+    return each_pass(c, w, (kF64Block / kWave) * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid) {
         WalkF64Args wa{};
         wa.gd = c->gd; wa.ld = c->ld; wa.perm = c->perm; wa.pos = (double2 *)c->pos; wa.vel = (double2 *)c->vel;
         wa.mass = (const double *)c->mass; wa.force_out = (double2 *)c->force; wa.lo = plo; wa.hi = phi;
-        wa.G = c->cfg.G; wa.dt = c->cfg.dt; wa.integrate = w.integrate ? 1 : 0; wa.ctr = c->ctr; wa.partial = pp;
+        wa.G = c->cfg.G; wa.dt = c->cfg.dt; wa.integrate = w.integrate ? 1 : 0; wa.ctr = c->ctr;
         wa.body_counts = w.stats ? c->body_counts : nullptr; wa.slots = w.slots; wa.bpw = k.bpw;
         dispatch([&](auto compat, auto deep_stack) {
             constexpr bool CP = decltype(compat)::value, DP = decltype(deep_stack)::value;
@@ -605,31 +608,32 @@ int launch_walk_f64(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
     });
 }
 
-// a workgroup = four wavefronts, each taking bodies (turn * grid + workgroup) * 4 + wave one after the other; as many
-// workgroups as `partial` has records (at least 1,024), every wave at most 64 bodies
+// a workgroup = four wavefronts, each taking bodies (turn * grid + workgroup) * 4 + wave one after the other; at most
+// max(1,024, capacity / 64) workgroups, every wave at most 64 bodies
 int launch_walk_exact_bfs(bh_ctx *c, const WalkRange &w)
 {
     const int64_t cnt = w.hi - w.lo;
-    const int64_t grid = std::max<int64_t>(std::min<int64_t>(blocks_for(cnt, kWavesPerBlock), partial_room(c)),
+    const int64_t max_groups = std::max<int64_t>(1024, (c->cfg.capacity + kWave - 1) / kWave);
+    const int64_t grid = std::max<int64_t>(std::min<int64_t>(blocks_for(cnt, kWavesPerBlock), max_groups),
                                            blocks_for(cnt, kWavesPerBlock * kBfsBodiesPerWave));
     // (more interactions per body in larger trees: 384 terms per walk -- 52 KB of LDS per workgroup, three per CU; 512 would leave two)
     dispatch([&](auto compat, auto big) {
         hipLaunchKernelGGL((walk_exact_bfs_kernel<decltype(compat)::value, decltype(big)::value ? 384 : 256>), dim3((unsigned)grid),
                            dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, (double2 *)c->pos, (double2 *)c->vel,
                            (const double *)c->mass, (double2 *)c->force, w.lo, w.hi, c->cfg.G, c->cfg.dt, w.integrate ? 1 : 0,
-                           c->ctr, w.partial, w.slots, c->box);
+                           c->ctr, w.slots, c->box);
     }, c->compat, cnt > 4096);
     c->walk_launches += 1;
-    return (int)grid;
+    return BH_OK;
 }
 
 int launch_walk_exact(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
 {
-    return each_pass(c, w, kWavesPerBlock * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid, double *pp) {
+    return each_pass(c, w, kWavesPerBlock * k.bpw, [&](int64_t plo, int64_t phi, unsigned grid) {
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, (double2 *)c->pos,
                                (double2 *)c->vel, (const double *)c->mass, (double2 *)c->force, plo, phi, c->cfg.theta, c->cfg.G,
-                               c->cfg.dt, w.integrate ? 1 : 0, c->ctr, pp, w.slots, k.bpw, c->box);
+                               c->cfg.dt, w.integrate ? 1 : 0, c->ctr, w.slots, k.bpw, c->box);
         };
         dispatch([&](auto compat) {
             constexpr bool CP = decltype(compat)::value;
@@ -681,8 +685,9 @@ int launch_walk_f32(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
     }
     if (3 * c->Dm + 2 > kWave) split = 1;        // the level-synchronous walk's depth-first fallback has 64 entries
     const int per_record = walk_fast_split_effective(a, lds, split) ? kWave : kBlock;
-    return each_pass(c, w, per_record, [&](int64_t plo, int64_t phi, unsigned, double *pp) -> int {
-        a.lo = plo; a.hi = phi; a.partial = pp;
+    if (w.partial) c->partial_count = (int)blocks_for(w.hi - w.lo, per_record);
+    return each_pass(c, w, per_record, [&](int64_t plo, int64_t phi, unsigned) -> int {
+        a.lo = plo; a.hi = phi; a.partial = w.partial ? w.partial + 4 * ((plo - w.lo) / per_record) : nullptr;
         BH_HIP(c, launch_walk_fast(a, lds, w.stats, split, k.use_asm, c->stream));
         return BH_OK;
     });
@@ -696,46 +701,37 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     w.integrate = integrate; w.to_sorted = to_sorted; w.part = part;
     w.stats = (c->cfg.flags & BH_FLAG_WALK_STATS) != 0;
     if (part != 2) c->walk_launches = 0;
-    // a full-range integrating walk also leaves the min/max of the NEW positions per workgroup
-    if (integrate && !to_sorted && w.lo == 0 && w.hi == c->n) w.partial = c->partial;
     // N_THREADS (project.cu:5-7, 703: `body_i += N_THREADS`): at most that many bodies are walked at a time -- the
     // range is taken in passes of n_threads bodies, rounded up to whole 256-thread workgroups, one launch after the
     // other on the stream, as the reference's threads take their bodies one after the other.  0 (the default):
     // one pass.  It gives the thread axis of the reference's first scaling experiment (first_scaling_script.sh:
     // 17-36) a meaning on this hardware: n_threads = 1 is one workgroup at a time.
     w.pass = c->cfg.n_threads > 0 ? ((int64_t)c->cfg.n_threads + kBlock - 1) / kBlock * kBlock : w.hi - w.lo;
-    // one launch over all bodies that integrates: the workgroups also fold their bounds into the slot records the
-    // next keys_kernel reduces (bh_bounds.hpp) -- that build then needs no bounds_final launch
-    const bool want_slots = w.partial && w.pass == w.hi - w.lo && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
-    if (want_slots) {
-        if (c->slots_dirty)
-            hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
-        w.slots = c->bslots; c->slots_dirty = true;
-    }
+    // a walk over all bodies that integrates also leaves the min/max of the NEW positions for the next build's root box: its
+    // workgroups fold them into the slot records the next keys_kernel reduces (bh_bounds.hpp), in every pass.  LET mode: the
+    // fp32 walk writes one `partial` record per workgroup instead, for bh_let_bounds.
+    const bool full = integrate && !to_sorted && w.lo == 0 && w.hi == c->n;
+    if (full && c->let_mode) w.partial = c->partial;
+    const bool want_slots = full && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
+    if (want_slots) { clean_slots(c); w.slots = c->bslots; }
     if (integrate) { c->slots_valid = want_slots; c->phi_current = false; }    // (the positions change)
 
     const WalkChoice k = choose_walk(c, w);
-    // the fp64 cooperative walks size bodies per wave by ONE pass: over all passes of n_threads their workgroups can be more
-    // than `partial` has records -- then no records are written and the next build takes the bounds pass
-    if (w.partial && (k.kind == WalkKind::F64 || k.kind == WalkKind::Exact) &&
-        (int64_t)blocks_for(w.hi - w.lo, (k.kind == WalkKind::F64 ? kF64Block / kWave : kWavesPerBlock) * k.bpw) > partial_room(c))
-        w.partial = nullptr;
     if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
         if (!c->body_counts) { int rc = dev_alloc(c, &c->body_counts, (size_t)std::max<int64_t>(c->cfg.capacity, 1)); if (rc) return rc; }
         // (a launch writes the slots of the bodies it walks: an owned range smaller than n, or a walk that returned
         // early on an overflowed tree, must not leave the others uninitialised; part 2 adds to the counts of part 1)
         if (part != 2) BH_HIP(c, hipMemsetAsync(c->body_counts, 0, (size_t)std::max<int64_t>(c->n, 1) * sizeof(uint32_t), c->stream));
     }
-    int records = 0;
+    int rc = BH_OK;
     switch (k.kind) {
-    case WalkKind::F64: records = launch_walk_f64(c, w, k); break;
-    case WalkKind::ExactBfs: records = launch_walk_exact_bfs(c, w); break;
-    case WalkKind::Exact: records = launch_walk_exact(c, w, k); break;
-    case WalkKind::F32: records = launch_walk_f32(c, w, k); break;
+    case WalkKind::F64: rc = launch_walk_f64(c, w, k); break;
+    case WalkKind::ExactBfs: rc = launch_walk_exact_bfs(c, w); break;
+    case WalkKind::Exact: rc = launch_walk_exact(c, w, k); break;
+    case WalkKind::F32: rc = launch_walk_f32(c, w, k); break;
     }
-    if (records < 0) return records;
+    if (rc) return rc;
     BH_HIP(c, hipGetLastError());
-    if (w.partial) c->partial_count = records;
     if (!c->tree64() && w.lo == 0 && w.hi == c->n) c->group_cost_valid = true;
     return BH_OK;
 }
@@ -872,7 +868,8 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     // scan scratch (bsum_u32, bsum_d3): one record per scan tile, sized for the smallest tile
     const size_t scan_tiles = std::max<size_t>(blocks_for(cap + 1, kTile), blocks_for(std::min<int64_t>(cap, 1 << 22) + 1, kBlock * kSmallItems)) + 8;
     A(&c->bsum_u32, scan_tiles);
-    A(&c->partial, 4 * (std::max<size_t>(1024, blocks_for(cap, kWave)) + 2)); A(&c->box, 8); A(&c->bslots, 4 * kBoundSlots);
+    A(&c->partial, 4 * (std::max<size_t>(1024, blocks_for(cap, kWave)) + 2));   // (LET mode only: the records of bh_let_bounds)
+    A(&c->box, 8); A(&c->bslots, 4 * kBoundSlots);
     A(&c->ctr, 1);
     if (c->tree64()) {
         // (node 0 is the root, the four children of cell r are nodes 1 + 4 r ..: the arrays start three records into their
@@ -1148,7 +1145,7 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
 // A tree of the current state is built for the potential walk without perturbing the run: the build runs as a step's build
 // would, except that it never re-orders the state, and afterwards everything a later build reads from an earlier one is put
 // back -- the build count (re-order cadence), samples_n (whether the next sort takes the bucket path), the bounds slot
-// records the last walk folded (copied aside on the device and back) and partial_count.  What the build leaves otherwise --
+// records the last walk folded (copied aside on the device and back) and their flags.  What the build leaves otherwise --
 // the sorted copies and splitter samples of THIS state, the tree itself -- only changes the splitters of the next bucket
 // sort, whose result is the same permutation whatever the splitters (the keys carry the body index, so there are no ties).
 // The walk writes phi and its own term counts only: force, body_counts, group_cost, partial, the event timings and
@@ -1178,14 +1175,14 @@ static int diag_alloc(bh_ctx *c)
 static int enqueue_potential(bh_ctx *c)
 {
     const int64_t builds = c->builds, samples_n = c->samples_n;
-    const int partial_count = c->partial_count, reorder_every = c->reorder_every;
+    const int reorder_every = c->reorder_every;
     const bool slots_valid = c->slots_valid, slots_dirty = c->slots_dirty;
     const size_t slot_bytes = (size_t)4 * kBoundSlots * sizeof(double);
     BH_HIP(c, hipMemcpyAsync(c->slots_save, c->bslots, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
     c->reorder_every = 0;
     int rc = enqueue_build(c);
     c->reorder_every = reorder_every;
-    c->builds = builds; c->samples_n = samples_n; c->partial_count = partial_count;
+    c->builds = builds; c->samples_n = samples_n;
     c->slots_valid = slots_valid; c->slots_dirty = slots_dirty;
     BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
     if (rc) return rc;
@@ -1561,7 +1558,7 @@ int bh_scatter_sorted(bh_ctx *c)
                            c->perm, c->sstate, (float2 *)c->pos, (float2 *)c->vel, c->n);
         BH_HIP(c, hipGetLastError());
     }
-    c->partial_count = 0; c->slots_valid = false; c->phi_current = false;
+    c->slots_valid = false; c->phi_current = false;
     c->steps_done += 1;
     return BH_OK;
 }

@@ -22,8 +22,8 @@
 //               ComputeMass does (project.cu:473-502).  fp32 mode: from fp64 prefix sums.
 //
 // Launch count matters as much as kernel quality here: on MI355X every launch costs ~6 us (4.7 us
-// minimum kernel duration + boundary).  Per step at max_depth 21: bounds_final | keys |
-// 5 x (hist, rowscan, scatter) | prep | scan_top2 | scan_apply2 | nodes | walk = 22 launches
+// minimum kernel duration + boundary).  Per step at max_depth 21: keys |
+// 5 x (hist, rowscan, scatter) | prep | scan_top2 | scan_apply2 | nodes | walk = 21 launches
 // (it was 40).
 #pragma once
 
@@ -49,71 +49,24 @@ __device__ __forceinline__ int shared_levels(uint64_t a, uint64_t b, int Dm)
 }
 
 // ---- root box: ComputeRootBounds, project.cu:536-573 ------------------------------------------
+// min/max of the positions folded into the kBoundSlots records (bh_bounds.hpp) by <= 1,024 workgroups: the root box when no walk
+// has left it.  NaN positions are skipped (every compare with one is false).
 template <typename Real2>
-__global__ __launch_bounds__(kBlock) void bounds_partial(const Real2 *__restrict__ pos, int64_t n,
-                                                          double *__restrict__ partial)
+__global__ __launch_bounds__(kBlock) void bounds_partial(const Real2 *__restrict__ pos, int64_t n, double *slots)
 {
-    __shared__ double sm[4][kWavesPerBlock];
     double xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const double x = (double)pos[i].x, y = (double)pos[i].y;
         xlo = (x < xlo) ? x : xlo;  xhi = (xhi < x) ? x : xhi;
         ylo = (y < ylo) ? y : ylo;  yhi = (yhi < y) ? y : yhi;
     }
-    xlo = wave_min(xlo); xhi = wave_max(xhi); ylo = wave_min(ylo); yhi = wave_max(yhi);
-    if (lane_id() == 0) { sm[0][wave_id()] = xlo; sm[1][wave_id()] = xhi; sm[2][wave_id()] = ylo; sm[3][wave_id()] = yhi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWavesPerBlock; ++w) {
-            xlo = (sm[0][w] < xlo) ? sm[0][w] : xlo;  xhi = (xhi < sm[1][w]) ? sm[1][w] : xhi;
-            ylo = (sm[2][w] < ylo) ? sm[2][w] : ylo;  yhi = (yhi < sm[3][w]) ? sm[3][w] : yhi;
-        }
-        partial[4 * blockIdx.x + 0] = xlo; partial[4 * blockIdx.x + 1] = xhi;
-        partial[4 * blockIdx.x + 2] = ylo; partial[4 * blockIdx.x + 3] = yhi;
-    }
+    block_bounds(xlo, xhi, ylo, yhi, slots);
 }
 
 __global__ void bounds_slots_reset(double *slots)                // one wave: records back to +-inf
 {
     double *w = slots + 4 * threadIdx.x;
     w[0] = INFINITY; w[1] = -INFINITY; w[2] = INFINITY; w[3] = -INFINITY;
-}
-
-// final reduction + the padding of project.cu:553-570; also clears the per-step counters.
-// from_walk: the partials are what the previous walk's epilogue left.  A walk whose tree had outgrown node_capacity
-// returned at once and wrote none: the box and the overflow flag stay as they are (the bodies have not moved), so every
-// later step of the same bh_step call is a no-op too and bh_sync / bh_download report BH_ERR_CAPACITY.
-__global__ __launch_bounds__(kBlock) void bounds_final(const double *__restrict__ partial, int nb,
-                                                        double *__restrict__ box, TreeCounters *ctr, int Dm, int from_walk)
-{
-    __shared__ double sm[4][kWavesPerBlock];
-    double xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
-#pragma unroll 8
-    for (int i = threadIdx.x; i < nb; i += kBlock) {
-        const double a = partial[4 * i], b = partial[4 * i + 1], c = partial[4 * i + 2], d = partial[4 * i + 3];
-        xlo = (a < xlo) ? a : xlo;  xhi = (xhi < b) ? b : xhi;
-        ylo = (c < ylo) ? c : ylo;  yhi = (yhi < d) ? d : yhi;
-    }
-    xlo = wave_min(xlo); xhi = wave_max(xhi); ylo = wave_min(ylo); yhi = wave_max(yhi);
-    if (lane_id() == 0) { sm[0][wave_id()] = xlo; sm[1][wave_id()] = xhi; sm[2][wave_id()] = ylo; sm[3][wave_id()] = yhi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWavesPerBlock; ++w) {
-            xlo = (sm[0][w] < xlo) ? sm[0][w] : xlo;  xhi = (xhi < sm[1][w]) ? sm[1][w] : xhi;
-            ylo = (sm[2][w] < ylo) ? sm[2][w] : ylo;  yhi = (yhi < sm[3][w]) ? sm[3][w] : yhi;
-        }
-        if (!(from_walk && ctr->overflow)) {
-            const double ex = xhi - xlo, ey = yhi - ylo;
-            const double span = (ex < ey) ? ey : ex;
-            double pad = 0.1 * span;
-            if (span == 0.0) pad = 1e-6;
-            box[0] = xlo - pad; box[1] = xhi + pad; box[2] = ylo - pad; box[3] = yhi + pad;
-            write_key_consts(box, Dm);
-            ctr->overflow = 0;
-        }
-        ctr->n_internal = 0;
-        ctr->visits = 0; ctr->interactions = 0; ctr->wave_nodes = 0; ctr->wave_quads = 0; ctr->wave_accepts = 0;
-    }
 }
 
 // ---- keys: DetermineChild (project.cu:348-356) applied max_depth-1 times -----------------------
@@ -279,31 +232,32 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
                                                        uint64_t *__restrict__ splitters = nullptr, int nb = 0,
                                                        int ns = 0, double *slots = nullptr, TreeCounters *ctr = nullptr,
                                                        uint32_t *__restrict__ zero_words = nullptr, int n_zero = 0,
-                                                       const uint32_t *__restrict__ sample_perm = nullptr)
+                                                       const uint32_t *__restrict__ sample_perm = nullptr, int from_walk = 0)
 {
     if (blockIdx.x == 0)                                         // (the bucket totals the histogram launch adds into: bh_sort.hpp)
         for (int k = threadIdx.x; k < n_zero; k += kBlock) zero_words[k] = 0u;
-    // FROM_SLOTS: the root box is not in memory yet -- the previous walk left its bounds in kBoundSlots
-    // records (bh_bounds.hpp).  Every workgroup reduces them and pads the box as bounds_final does
-    // (project.cu:553-570), workgroup 0 also writes it out and clears the step's counters for the kernels that
+    // FROM_SLOTS (all but LET mode, whose box is in memory already): the bounds of the positions are in kBoundSlots
+    // records (bh_bounds.hpp), from the previous walk (from_walk) or from bounds_partial.  Every workgroup reduces them and
+    // pads the box (project.cu:553-570), workgroup 0 also writes it out and clears the step's counters for the kernels that
     // follow; prep_kernel, two launches on, puts the slots back to +-inf for the next walk.  (A counter of readers
     // that let the last workgroup do that here made this kernel 51 us instead of 10: 4,100 atomics on one word.)
     __shared__ double s_box[FROM_SLOTS ? 8 : 1];
-    __shared__ int s_empty;
+    __shared__ int s_keep;
     if (FROM_SLOTS) {
         if (threadIdx.x < kWave) {
             const double *sl = slots + 4 * threadIdx.x;
             const double xlo = wave_min(sl[0]), xhi = wave_max(sl[1]), ylo = wave_min(sl[2]), yhi = wave_max(sl[3]);
-            // No workgroup folded anything (every record still +-inf): the previous walk returned at once because its tree
+            // No workgroup of the walk folded anything (every record still +-inf): the walk returned at once because its tree
             // had outgrown node_capacity (`if (ctr->overflow) return`), so the bodies have not moved.  Keep the box in
             // memory and leave the overflow flag standing -- this build's walk then does nothing either, and the state
             // stays the last good one until bh_sync / bh_download report BH_ERR_CAPACITY (a box of {+inf, -inf}
             // gave every body the same key, a short tree that did NOT overflow, and a step integrated with garbage forces).
-            const bool empty = xlo > xhi;
-            if (threadIdx.x == 0) s_empty = empty ? 1 : 0;
+            // (from bounds_partial, all +-inf -- no bodies, or all NaN -- is padded like any other box)
+            const bool keep = from_walk && xlo > xhi;
+            if (threadIdx.x == 0) s_keep = keep ? 1 : 0;
             if (threadIdx.x < 2) {                               // lane a: axis a (four fp64 divisions in a row otherwise)
                 const int a = threadIdx.x;
-                if (empty) {
+                if (keep) {
                     s_box[2 * a] = box_global[2 * a]; s_box[2 * a + 1] = box_global[2 * a + 1];
                     s_box[4 + a] = box_global[4 + a]; s_box[6 + a] = box_global[6 + a];
                 } else {
@@ -318,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
         }
         __syncthreads();
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            if (!s_empty) {
+            if (!s_keep) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) box_global[k] = s_box[k];
                 ctr->overflow = 0;

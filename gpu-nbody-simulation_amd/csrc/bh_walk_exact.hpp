@@ -303,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void walk_exact_kernel(
     const NodeD *__restrict__ gd, const LinkD *__restrict__ ld, const uint32_t *__restrict__ perm,
     double2 *__restrict__ pos, double2 *__restrict__ vel, const double *__restrict__ mass,
     double2 *__restrict__ force_out, int64_t lo, int64_t hi, double theta, double G, double dt,
-    int integrate, TreeCounters *ctr, double *__restrict__ partial, double *slots, int bpw, const double *__restrict__ box)
+    int integrate, TreeCounters *ctr, double *slots, int bpw, const double *__restrict__ box)
 {
     // bpw: bodies per wavefront, a power of two <= 64 (lanes bpw .. 63 idle).  A wave's walk is ONE dependent chain over the
     // union of its lanes' walks; a launch of few bodies leaves the GPU empty however it is cut, so the engine gives every
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(kBlock) void walk_exact_kernel(
         }
     }
     // min/max of the new positions per workgroup: the next step's root box needs no body pass
-    if (partial) block_bounds_to_partial(valid, np.x, np.y, partial + 4 * (size_t)blockIdx.x, slots);
+    if (slots) block_bounds(valid, np.x, np.y, slots);
     if (STATS) {
         // one atomic per wave
         if (lane == 0) {
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(kBlock) void walk_exact_bfs_kernel(
     const NodeD *__restrict__ gd, const LinkD *__restrict__ ld, const uint32_t *__restrict__ perm,
     double2 *__restrict__ pos, double2 *__restrict__ vel, const double *__restrict__ mass,
     double2 *__restrict__ force_out, int64_t lo, int64_t hi, double G, double dt, int integrate, TreeCounters *ctr,
-    double *__restrict__ partial, double *slots, const double *__restrict__ box)
+    double *slots, const double *__restrict__ box)
 {
     __shared__ uint64_t s_meta[kWavesPerBlock][kBfsQueue];       // node id | depth << 32
     __shared__ uint64_t s_qkey[kWavesPerBlock][kBfsQueue];
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(kBlock) void walk_exact_bfs_kernel(
     }
     if (lane == turn) { npx = np.x; npy = np.y; np_valid = true; }
     }   // turn
-    if (partial) block_bounds_to_partial(np_valid, npx, npy, partial + 4 * (size_t)blockIdx.x, slots);
+    if (slots) block_bounds(np_valid, npx, npy, slots);
 }
 
 }  // namespace bh

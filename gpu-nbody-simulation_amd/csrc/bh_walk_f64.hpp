@@ -278,9 +278,8 @@ struct WalkF64Args {
     double G, dt;
     int32_t integrate, pad0;
     TreeCounters *ctr;
-    double *partial;               // per-workgroup min/max of the new positions (next root box), may be null
     uint32_t *body_counts;         // counting variant: accepted force evaluations per body, may be null
-    double *slots;                 // bh_bounds.hpp: running bounds records, may be null
+    double *slots;                 // bh_bounds.hpp: bounds records the new positions fold into (next root box), may be null
     int32_t bpw, pad1;             // bodies per wavefront, a power of two <= 64 (see walk_exact_kernel): few bodies, short chains
 };
 
@@ -466,17 +465,13 @@ __global__ __launch_bounds__(kF64Block) void walk_f64_kernel(WalkF64Args a)
         }
         if (STATS && e.body_counts) e.body_counts[body] = my_int;
     }
-    if (e.partial) {                                              // min/max of the new positions per workgroup (next root box)
+    if (e.slots) {                                                // min/max of the new positions per workgroup (next root box)
         if (kF64Block == kWave) {
             const double xlo = wave_min(valid ? np.x : (double)INFINITY), xhi = wave_max(valid ? np.x : -(double)INFINITY);
             const double ylo = wave_min(valid ? np.y : (double)INFINITY), yhi = wave_max(valid ? np.y : -(double)INFINITY);
-            if (lane == 0) {
-                double *o = e.partial + 4 * (size_t)blockIdx.x;
-                o[0] = xlo; o[1] = xhi; o[2] = ylo; o[3] = yhi;
-                if (e.slots) bounds_to_slot(xlo, xhi, ylo, yhi, e.slots, blockIdx.x);
-            }
+            if (lane == 0) bounds_to_slot(xlo, xhi, ylo, yhi, e.slots, blockIdx.x);
         } else {
-            block_bounds_to_partial(valid, np.x, np.y, e.partial + 4 * (size_t)blockIdx.x, e.slots);
+            block_bounds(valid, np.x, np.y, e.slots);
         }
     }
     if (STATS && lane == 0) {

@@ -24,7 +24,7 @@ struct WalkFastArgs {
     float4 *sstate;            // sorted-order output {x, y, vx, vy} per body (integrate && to_sorted): ONE exchange buffer
     float2 *acc_out;           // caller-order accelerations, may be null
     TreeCounters *ctr;
-    double *partial;           // per-workgroup min/max of the new positions, may be null
+    double *partial;           // LET mode: per-workgroup min/max of the new positions (bh_let_bounds), may be null
     int64_t lo, hi;            // sorted range walked by this launch
     float G, dt;
     int integrate, to_sorted;
@@ -44,13 +44,13 @@ struct WalkFastArgs {
     int32_t part;
     float2 *acc_part;
     int64_t forest_base, let_cap;
-    double *slots;                 // bh_bounds.hpp: running bounds records of this launch's workgroups (with `partial`), may be null
+    double *slots;                 // bh_bounds.hpp: bounds records the new positions fold into (next root box), may be null
     uint32_t *body_counts;         // counting variant (BH_FLAG_WALK_STATS): accepted force evaluations per body, added
                                    // atomically at the body's device slot (the engine zeroes it); may be null
 };
 
 // split: 1 = one wave per 64 bodies; 2/4/8 = that many waves share each 64-body group (few bodies; more than 8 -> 8).
-// The launch writes one `partial` entry per workgroup: per 256 bodies, or per 64 when split > 1
+// The launch writes one bounds record per workgroup: per 256 bodies, or per 64 when split > 1
 // (walk_fast_split_effective tells which applies).
 // use_asm: take the hand-scheduled loop where it applies (32-bit byte offsets into the quad array: the
 // caller checks that the forest is smaller than 2 GiB and the bodies fewer than 2^28).

@@ -911,16 +911,18 @@ __global__ __launch_bounds__(SPLIT > 1 ? kWave * SPLIT : kBlock) void walk_fast_
     // min/max of the new positions per workgroup: the next step's root box needs no body pass
     const double bx = e.state64 ? np64.x : (double)np.x, by = e.state64 ? np64.y : (double)np.y;
     if (SPLIT > 1) {
-        if (e.partial && w == 0) {                          // one partial per 64-body group
+        if ((e.slots || e.partial) && w == 0) {             // one record per 64-body group
             const double xlo = wave_min(valid ? bx : (double)INFINITY), xhi = wave_max(valid ? bx : -(double)INFINITY);
             const double ylo = wave_min(valid ? by : (double)INFINITY), yhi = wave_max(valid ? by : -(double)INFINITY);
             if (lane == 0) {
-                double *o = e.partial + 4 * (size_t)lb;
-                o[0] = xlo; o[1] = xhi; o[2] = ylo; o[3] = yhi;
+                if (e.partial) {
+                    double *o = e.partial + 4 * (size_t)lb;
+                    o[0] = xlo; o[1] = xhi; o[2] = ylo; o[3] = yhi;
+                }
                 if (e.slots) bounds_to_slot(xlo, xhi, ylo, yhi, e.slots, (uint32_t)lb);
             }
         }
-    } else if (e.partial) block_bounds_to_partial(valid, bx, by, e.partial + 4 * (size_t)lb, e.slots);
+    } else if (e.slots || e.partial) block_bounds(valid, bx, by, e.slots, e.partial ? e.partial + 4 * (size_t)lb : nullptr);
 #ifdef BHGPU_EXPERIMENTS
     if (e.timeline && lane == 0) {                              // per wave: start, end (10 ns ticks), hardware id, cost, clock stamps
         const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + w;

@@ -141,7 +141,7 @@ typedef struct bh_stats_t {
     uint64_t device_bytes;       /* device memory held by the context                       */
     /* per kernel group of the last timed step (HIP events on the context's stream):
      * the reference times "GPU parallel computation" as a whole (project.cu:957, 1008)          */
-    double   keys_ms;            /* root box + keys (bounds_final, keys_kernel)              */
+    double   keys_ms;            /* root box + keys (bounds_partial, keys_kernel)            */
     double   sort_ms;            /* radix passes (+ the state re-ordering when it ran)       */
     double   scan_ms;            /* cell counts, sorted copies, ranks, prefix sums           */
     double   nodes_ms;           /* node records (+ the bottom-up mass pass in exact mode)   */

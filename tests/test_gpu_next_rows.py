@@ -167,3 +167,100 @@ def test_overflow_inside_a_multi_step_call_keeps_the_last_good_state(precision, 
     a = np.hstack([gp, gv]); b = np.hstack([p, v])
     a = a[np.lexsort(a.T[::-1])]; b = b[np.lexsort(b.T[::-1])]
     assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("nt", [256, 4096])
+@pytest.mark.parametrize("precision,bpw", [(G.Precision.F64_EXACT, None), (G.Precision.F64, "1"), (G.Precision.F64, None),
+                                           (G.Precision.F32, None)])
+def test_n_threads_at_many_workgroups_folds_the_root_box_of_every_pass(monkeypatch, precision, bpw, nt):
+    """passes of n_threads at N = 40,000 give the fp64 walks one workgroup per four bodies (bpw 1 per pass), more
+    than the per-workgroup bounds records held.  Every pass now folds its workgroups into the 64 bounds slot records
+    (bh_bounds.hpp): three steps bitwise equal to n_threads = 0, one walk launch per pass.  (F64 adds a lane's terms in
+    wave order: BH_EXACT_BPW=1 keeps one body per wave on both sides, BH_FLAG_WALK_NO_SPLIT 64; F32 as the test above.)"""
+    n = 40000
+    r = np.random.default_rng(40)
+    m, p, v = r.uniform(0.1, 0.5, n), r.uniform(-1, 1, (n, 2)), r.uniform(-1e-3, 1e-3, (n, 2))
+    if precision == G.Precision.F32:
+        m, p, v = (x.astype(np.float32).astype(np.float64) for x in (m, p, v))
+    if bpw is None:
+        monkeypatch.delenv("BH_EXACT_BPW", raising=False)
+    else:
+        monkeypatch.setenv("BH_EXACT_BPW", bpw)
+    flags = FLAG_WALK_NO_SPLIT if bpw is None else 0
+    out, launches = [], []
+    for threads in (0, nt):
+        with G.BarnesHutEngine(G.BhConfig(capacity=n, precision=precision, n_threads=threads, flags=flags)) as e:
+            e.upload(p, v, m)
+            e.step(3)
+            out.append(e.download())
+            launches.append(e.stats().walk_launches)
+    assert np.array_equal(out[1][0], out[0][0]) and np.array_equal(out[1][1], out[0][1])
+    assert launches == [1, -(-n // nt)]
+
+
+@pytest.mark.parametrize("precision", [G.Precision.F32, G.Precision.F64, G.Precision.F64_EXACT])
+def test_overflow_under_n_threads_keeps_the_last_good_state(precision):
+    """As test_overflow_inside_a_multi_step_call_keeps_the_last_good_state, with the walk taken in passes: a walk that returns
+    at once in every pass folds nothing into the bounds slots, the box and the flag stay, sync raises -4 and the device
+    state is the uploaded one."""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    r = np.random.default_rng(0)
+    n = 4096
+    m, p, v = 10.0 ** r.uniform(-2, 1, n), r.uniform(-0.1, 0.1, (n, 2)), r.uniform(-1e-4, 1e-4, (n, 2))
+    f32 = precision == G.Precision.F32
+    if f32:
+        m, p, v = (x.astype(np.float32).astype(np.float64) for x in (m, p, v))
+    with G.BarnesHutEngine(G.BhConfig(capacity=n, node_capacity=101, precision=precision, max_depth=16, n_threads=1024)) as e:
+        e.upload(p, v, m)
+        e.step(3)
+        with pytest.raises(G.BhError) as ei:
+            e.sync()
+        assert ei.value.code == -4
+        dp, dv, _, dn, eb = e.device_state()
+        ts = np.float32 if f32 else np.float64
+        state = []
+        for ptr in (dp, dv):
+            a = np.empty(2 * n, dtype=ts)
+            assert hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2) == 0   # hipMemcpyDeviceToHost
+            state.append(a.astype(np.float64).reshape(n, 2))
+    a = np.hstack(state); b = np.hstack([p, v])
+    a = a[np.lexsort(a.T[::-1])]; b = b[np.lexsort(b.T[::-1])]
+    assert np.array_equal(a, b)
+
+
+def _box_formula(p):
+    """ComputeRootBounds (project.cu:536-573): min/max from +-inf (a NaN never wins), padded by a tenth of the larger side."""
+    xs, ys = p[:, 0][~np.isnan(p[:, 0])], p[:, 1][~np.isnan(p[:, 1])]
+    lo = np.array([xs.min(initial=np.inf), ys.min(initial=np.inf)])
+    hi = np.array([xs.max(initial=-np.inf), ys.max(initial=-np.inf)])
+    ex, ey = hi - lo
+    span = ey if ex < ey else ex
+    pad = 1e-6 if span == 0.0 else 0.1 * span
+    return np.array([lo[0] - pad, hi[0] + pad, lo[1] - pad, hi[1] + pad])
+
+
+@pytest.mark.parametrize("precision", [G.Precision.F64_EXACT, G.Precision.F64, G.Precision.MIXED, G.Precision.F32])
+@pytest.mark.parametrize("case", ["n1", "n2", "one_nan", "all_nan"])
+def test_root_box_from_the_positions_pass(precision, case):
+    """The first build after an upload has no walk's bounds: the positions pass folds the min/max into the bounds slots and
+    keys_kernel pads them.  n = 1, n = 2 and a set with one NaN body give ComputeRootBounds' box bit for bit; a NaN body
+    is skipped.  All bodies NaN: every record stays +-inf and the box is {+inf, -inf, +inf, -inf}, as it always was."""
+    r = np.random.default_rng(5)
+    p = {"n1": np.array([[0.25, -0.5]]), "n2": np.array([[0.25, -0.5], [0.25, 0.75]]),
+         "one_nan": r.uniform(-1, 1, (300, 2)), "all_nan": np.full((1, 2), np.nan)}[case]
+    if case == "one_nan":
+        p[17] = np.nan
+    if precision == G.Precision.F32:
+        p = p.astype(np.float32).astype(np.float64)
+    n = len(p)
+    m, v = np.full(n, 0.25), np.zeros((n, 2))
+    with G.BarnesHutEngine(G.BhConfig(capacity=n, precision=precision, max_depth=10)) as e:
+        e.upload(p, v, m)
+        e.build_tree()
+        nodes, _ = e.export_tree()
+    box = np.array([nodes[0]["xmin"], nodes[0]["xmax"], nodes[0]["ymin"], nodes[0]["ymax"]])
+    expect = _box_formula(p)
+    if case == "all_nan":
+        assert np.array_equal(expect, [np.inf, -np.inf, np.inf, -np.inf])
+    assert np.array_equal(box, expect)
