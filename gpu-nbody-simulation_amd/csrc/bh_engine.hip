@@ -18,6 +18,7 @@
 #include "bh_walk_exact.hpp"
 #include "bh_walk_f64.hpp"
 #include "bh_diag.hpp"
+#include "bh_direct.hpp"
 #include "bh_init.hpp"
 #include "bh_let.hpp"
 #include "bh_migrate.hpp"
@@ -142,6 +143,14 @@ struct bh_ctx {
     uint32_t *phi_counts = nullptr;
     double *diag_part = nullptr, *diag_out = nullptr, *slots_save = nullptr;
     bool phi_current = false;           // phi holds the potential of the current state
+    // direct sums and the force check (bh_direct.hpp), allocated on first use: caller index -> slot, one launch's targets and
+    // results (capacity of them), and the check walk's own force / count / group-cost outputs and a copy of the walk counters
+    uint32_t *slot_of = nullptr;
+    int64_t *direct_targets = nullptr;
+    double2 *direct_out = nullptr;
+    void *check_force = nullptr;
+    uint32_t *check_counts = nullptr, *check_cost = nullptr;
+    TreeCounters *ctr_save = nullptr;
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -1094,13 +1103,13 @@ int bh_step(bh_ctx *c, int32_t nsteps)
     return BH_OK;
 }
 
-// The device holds forces (fp64 tree) or accelerations (fp32 / mixed); the other is converted with the masses
+// A walk's output `dev` holds forces (fp64 tree) or accelerations (fp32 / mixed); the other is converted with the masses
 // (a = F / m_i: updateAccelerations, project.cu:795-801)
-static int forces_or_accels(bh_ctx *c, double *out, bool forces)
+static int forces_or_accels(bh_ctx *c, const void *dev, double *out, bool forces)
 {
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = download_pairs(c, c->force, out, 2 * c->n, c->tree64());
+    int rc = download_pairs(c, dev, out, 2 * c->n, c->tree64());
     if (rc) return rc;
     if (forces != c->tree64()) {
         std::vector<double> m(std::max<int64_t>(c->n, 1));
@@ -1114,13 +1123,13 @@ static int forces_or_accels(bh_ctx *c, double *out, bool forces)
 int bh_get_forces(bh_ctx *c, double *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_get_forces: null array");
-    return forces_or_accels(c, out, true);
+    return forces_or_accels(c, c->force, out, true);
 }
 
 int bh_get_accel(bh_ctx *c, double *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_get_accel: null array");
-    return forces_or_accels(c, out, false);
+    return forces_or_accels(c, c->force, out, false);
 }
 
 int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
@@ -1142,7 +1151,8 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
 }
 
 // ---- diagnostics (bh_diag.hpp): potential walk and reductions
-// A tree of the current state is built for the potential walk without perturbing the run: the build runs as a step's build
+// A tree of the current state is built for the potential walk and the force check without perturbing the run
+// (enqueue_quiet_build): the build runs as a step's build
 // would, except that it never re-orders the state, and afterwards everything a later build reads from an earlier one is put
 // back -- the build count (re-order cadence), samples_n (whether the next sort takes the bucket path), the bounds slot
 // records the last walk folded (copied aside on the device and back) and their flags.  What the build leaves otherwise --
@@ -1166,14 +1176,15 @@ static int diag_alloc(bh_ctx *c)
     if (!rc) rc = dev_alloc(c, &c->phi_counts, cap);
     if (!rc) rc = dev_alloc(c, &c->diag_part, (size_t)kDiagParts * 2 * kDiagQuantities);
     if (!rc) rc = dev_alloc(c, &c->diag_out, (size_t)kDiagQuantities);
-    if (!rc) rc = dev_alloc(c, &c->slots_save, (size_t)4 * kBoundSlots);
-    if (rc) { for (void *p : {(void *)c->phi, (void *)c->phi_counts, (void *)c->diag_part, (void *)c->diag_out, (void *)c->slots_save}) dev_free(c, p);
-              c->phi = nullptr; c->phi_counts = nullptr; c->diag_part = c->diag_out = c->slots_save = nullptr; }
+    if (rc) { for (void *p : {(void *)c->phi, (void *)c->phi_counts, (void *)c->diag_part, (void *)c->diag_out}) dev_free(c, p);
+              c->phi = nullptr; c->phi_counts = nullptr; c->diag_part = c->diag_out = nullptr; }
     return rc;
 }
 
-static int enqueue_potential(bh_ctx *c)
+// the tree of the current state, no re-order, and everything a later build reads from an earlier one put back (above)
+static int enqueue_quiet_build(bh_ctx *c)
 {
+    if (!c->slots_save) { if (int rc = dev_alloc(c, &c->slots_save, (size_t)4 * kBoundSlots)) return rc; }
     const int64_t builds = c->builds, samples_n = c->samples_n;
     const int reorder_every = c->reorder_every;
     const bool slots_valid = c->slots_valid, slots_dirty = c->slots_dirty;
@@ -1185,7 +1196,12 @@ static int enqueue_potential(bh_ctx *c)
     c->builds = builds; c->samples_n = samples_n;
     c->slots_valid = slots_valid; c->slots_dirty = slots_dirty;
     BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
-    if (rc) return rc;
+    return rc;
+}
+
+static int enqueue_potential(bh_ctx *c)
+{
+    if (int rc = enqueue_quiet_build(c)) return rc;
     if (c->n == 0) return BH_OK;
     const unsigned grid = blocks_for(c->n, kBlock);
     if (c->tree64()) {
@@ -1273,6 +1289,119 @@ int bh_energy(bh_ctx *c, bh_energy_t *out)
     e.n_bodies = c->n;
     *out = e;
     return BH_OK;
+}
+
+// ---- direct sums and the Barnes-Hut force check (bh_direct.hpp)
+// The direct kernel reads the state only.  The check's tree forces come from a quiet build (enqueue_quiet_build) and the
+// precision's own force walk (enqueue_walk, not integrating: n_threads applies as in a step) with the walk's outputs --
+// force, body_counts, group_cost -- swapped for scratch buffers, and walk_launches, group_cost_valid and the walk counters of
+// bh_stats put back: bh_get_forces, bh_get_interaction_counts, bh_stats and the ORB weights still describe the last real
+// force walk, and a following bh_step runs bit for bit as it would have.
+static int check_targets(bh_ctx *c, const char *what, const int64_t *targets, int64_t n_targets)
+{
+    if (targets) {
+        for (int64_t t = 0; t < n_targets; ++t)
+            if (targets[t] < 0 || targets[t] >= c->n)
+                return fail(c, BH_ERR_ARG, std::string(what) + ": target " + std::to_string(targets[t]) + " outside [0, n)");
+    } else if (n_targets != c->n) {
+        return fail(c, BH_ERR_ARG, std::string(what) + ": targets == NULL takes all n bodies (n_targets must be n)");
+    }
+    return BH_OK;
+}
+
+// out[n_targets][2]: the direct-sum forces of the targets (NULL: bodies 0 .. n_targets-1), launches of up to capacity targets
+static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targets, double *out)
+{
+    if (n_targets == 0) return BH_OK;
+    const int64_t chunk = std::max<int64_t>(c->cfg.capacity, 1);
+    if (!c->direct_out) {
+        int rc = dev_alloc(c, &c->direct_targets, (size_t)chunk);
+        if (!rc) rc = dev_alloc(c, &c->direct_out, (size_t)chunk);
+        if (rc) { dev_free(c, c->direct_targets); dev_free(c, c->direct_out); c->direct_targets = nullptr; c->direct_out = nullptr; return rc; }
+    }
+    const uint32_t *slot_of = nullptr;
+    if (!c->tree64() && !c->orig_identity) {            // (fp32 / mixed after a physical re-order: slots are not caller indices)
+        if (!c->slot_of) { if (int rc = dev_alloc(c, &c->slot_of, (size_t)chunk)) return rc; }
+        hipLaunchKernelGGL(direct_slot_kernel, dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream, c->orig, c->n, c->slot_of);
+        slot_of = c->slot_of;
+    }
+    for (int64_t t0 = 0; t0 < n_targets; t0 += chunk) {
+        const int64_t k = std::min(chunk, n_targets - t0);
+        if (targets) BH_HIP(c, hipMemcpyAsync(c->direct_targets, targets + t0, k * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        const int64_t *tg = targets ? c->direct_targets : nullptr;
+        if (c->state64())
+            hipLaunchKernelGGL((direct_forces_kernel<double2, double>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
+                               (const double2 *)c->pos, (const double *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
+        else
+            hipLaunchKernelGGL((direct_forces_kernel<float2, float>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
+                               (const float2 *)c->pos, (const float *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
+        BH_HIP(c, hipGetLastError());
+        BH_HIP(c, hipMemcpyAsync(out + 2 * t0, c->direct_out, k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        BH_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return BH_OK;
+}
+
+// the check walk's tree forces (caller order, all n) into out[n][2]
+static int check_walk(bh_ctx *c, double *out)
+{
+    const size_t cap = (size_t)std::max<int64_t>(c->cfg.capacity, 1);
+    int rc = BH_OK;
+    if (!c->check_force) {
+        char *f = nullptr;
+        rc = dev_alloc(c, &f, cap * 2 * (c->tree64() ? sizeof(double) : sizeof(float)));
+        c->check_force = f;
+        if (!rc) rc = dev_alloc(c, &c->ctr_save, 1);
+        if (!rc && c->group_cost) rc = dev_alloc(c, &c->check_cost, cap / kWave + 2);
+        if (rc) return rc;
+    }
+    if ((c->cfg.flags & BH_FLAG_WALK_STATS) && !c->check_counts) { if ((rc = dev_alloc(c, &c->check_counts, cap))) return rc; }
+    const int64_t launches = c->walk_launches;
+    const bool cost_valid = c->group_cost_valid;
+    constexpr size_t wc_off = offsetof(TreeCounters, visits), wc_bytes = sizeof(TreeCounters) - wc_off;
+    BH_HIP(c, hipMemcpyAsync((char *)c->ctr_save + wc_off, (char *)c->ctr + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    rc = enqueue_quiet_build(c);
+    if (!rc) {
+        auto swap_outputs = [&] {
+            std::swap(c->force, c->check_force);
+            std::swap(c->body_counts, c->check_counts);
+            std::swap(c->group_cost, c->check_cost);
+        };
+        swap_outputs();
+        rc = enqueue_walk(c, false, false);
+        swap_outputs();
+    }
+    c->walk_launches = launches;
+    c->group_cost_valid = cost_valid;
+    BH_HIP(c, hipMemcpyAsync((char *)c->ctr + wc_off, (char *)c->ctr_save + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (!rc) rc = check_overflow(c);
+    return rc ? rc : forces_or_accels(c, c->check_force, out, true);
+}
+
+int bh_direct_forces(bh_ctx *c, const int64_t *targets, int64_t n_targets, double *forces)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!forces || n_targets < 0) return fail(c, BH_ERR_ARG, "bh_direct_forces: null output array or n_targets < 0");
+    if (int rc = diag_check(c, "bh_direct_forces")) return rc;
+    if (int rc = check_targets(c, "bh_direct_forces", targets, n_targets)) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    return direct_forces_host(c, targets, n_targets, forces);
+}
+
+int bh_force_check(bh_ctx *c, const int64_t *targets, int64_t n_targets, double *tree, double *direct)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!tree || !direct || n_targets < 0) return fail(c, BH_ERR_ARG, "bh_force_check: null output array or n_targets < 0");
+    if (int rc = diag_check(c, "bh_force_check")) return rc;
+    if (int rc = check_targets(c, "bh_force_check", targets, n_targets)) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    std::vector<double> all((size_t)std::max<int64_t>(2 * c->n, 1));
+    if (int rc = check_walk(c, all.data())) return rc;
+    for (int64_t t = 0; t < n_targets; ++t) {
+        const int64_t i = targets ? targets[t] : t;
+        tree[2 * t] = all[2 * i]; tree[2 * t + 1] = all[2 * i + 1];
+    }
+    return direct_forces_host(c, targets, n_targets, direct);
 }
 
 // ---- tree export: DFS pre-order, children in index order (TraverseTreeToFile, project.cu:504-534)

@@ -93,8 +93,63 @@ class BhEnergy:
     n_bodies: int
 
 
+@dataclass
+class BhForceError:
+    """Relative Barnes-Hut force error rel_i = |F_tree - F_dir| / |F_dir| over a set of bodies (force_error_stats)."""
+    n: int                       # bodies in the statistics
+    n_zero: int                  # excluded: |F_dir| == 0 (finite forces)
+    n_nonfinite: int             # excluded: a non-finite component in F_tree or F_dir
+    median: float                # order statistics: the sorted value at index ceil(q n) - 1
+    p90: float
+    p99: float
+    p999: float
+    max: float
+    worst: int                   # caller index of the body with the largest error (-1: none)
+    rms: float                   # RMS |F_tree - F_dir| / RMS |F_dir|
+
+
+# (q as exact fractions: ceil(q n) in integers, so that no rounding of q * n moves an index)
+_QUANTILES = {"median": (1, 2), "p90": (9, 10), "p99": (99, 100), "p999": (999, 1000)}
+
+
+def force_error_stats(tree, direct, targets=None) -> BhForceError:
+    """Reduce tree and direct forces ((k, 2) each, row t for body targets[t], or body t without targets) to BhForceError.
+    Bodies with a non-finite component are counted in n_nonfinite, then bodies with |F_dir| == 0 in n_zero; both are
+    left out of every statistic.  With no body left, the statistics are NaN and worst is -1."""
+    tree = np.asarray(tree, dtype=np.float64).reshape(-1, 2)
+    direct = np.asarray(direct, dtype=np.float64).reshape(-1, 2)
+    if tree.shape != direct.shape:
+        raise ValueError("tree and direct must have the same shape")
+    idx = np.arange(len(direct)) if targets is None else np.asarray(targets, dtype=np.int64).reshape(-1)
+    if len(idx) != len(direct):
+        raise ValueError("one target per row")
+    finite = np.isfinite(tree).all(axis=1) & np.isfinite(direct).all(axis=1)
+    fd = np.hypot(direct[:, 0], direct[:, 1])
+    zero = finite & (fd == 0.0)
+    ok = finite & ~zero
+    fd = fd[ok]
+    df = np.hypot(tree[ok, 0] - direct[ok, 0], tree[ok, 1] - direct[ok, 1])
+    m = int(ok.sum())
+    n_nonfinite, n_zero = int((~finite).sum()), int(zero.sum())
+    if m == 0:
+        nan = float("nan")
+        return BhForceError(0, n_zero, n_nonfinite, nan, nan, nan, nan, nan, -1, nan)
+    rel = df / fd
+    srt = np.sort(rel)
+    q = {k: float(srt[-(-num * m // den) - 1]) for k, (num, den) in _QUANTILES.items()}
+    w = int(np.argmax(rel))
+    rms = float(np.sqrt(np.mean(df * df)) / np.sqrt(np.mean(fd * fd)))
+    return BhForceError(m, n_zero, n_nonfinite, q["median"], q["p90"], q["p99"], q["p999"], float(srt[-1]),
+                        int(idx[ok][w]), rms)
+
+
 def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def sample_targets(n: int, sample: int = 65536, seed: int = 0) -> np.ndarray:
+    """min(n, sample) distinct caller indices, drawn with numpy.random.default_rng(seed), in drawing order."""
+    return np.random.default_rng(seed).choice(n, size=min(n, max(int(sample), 0)), replace=False).astype(np.int64)
 
 
 class BarnesHutEngine:
@@ -211,6 +266,40 @@ class BarnesHutEngine:
         self._check(self._lib.bh_energy(self._h, C.byref(e)))
         return BhEnergy(e.kinetic, e.potential, e.total, (e.momentum[0], e.momentum[1]), e.angular_momentum,
                         (e.com[0], e.com[1]), e.mass, e.n_bodies)
+
+    # -- exact forces and the Barnes-Hut force error --------------------------------------------
+    def _targets(self, targets):
+        """(int64 array or None, count, pointer for the C-ABI) of a target list (None: every body)."""
+        if targets is None:
+            return None, self.n, None
+        t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+        return t, len(t), t.ctypes.data_as(C.POINTER(C.c_int64)) if len(t) else (C.c_int64 * 1)()
+
+    def direct_forces(self, targets=None) -> np.ndarray:
+        """fp64 direct-sum forces of the current state (main_approach_1.cpp:53-75 bit for bit) on the caller indices
+        `targets` (None: every body), shape (k, 2).  Reads the state only."""
+        _, k, tp = self._targets(targets)
+        f = np.zeros((max(k, 1), 2))
+        self._check(self._lib.bh_direct_forces(self._h, tp, k, _dptr(f)))
+        return f[:k]
+
+    def force_check(self, targets=None):
+        """(tree, direct), (k, 2) each: the precision's Barnes-Hut forces of the current state (a quiet tree build and
+        the force walk; n_threads applies) and the direct-sum forces, on `targets` (None: every body).  The run is not
+        perturbed: forces(), interaction_counts(), stats() and the following steps are as they were."""
+        _, k, tp = self._targets(targets)
+        tree, direct = np.zeros((max(k, 1), 2)), np.zeros((max(k, 1), 2))
+        self._check(self._lib.bh_force_check(self._h, tp, k, _dptr(tree), _dptr(direct)))
+        return tree[:k], direct[:k]
+
+    def force_error(self, sample: int = 65536, seed: int = 0, targets=None) -> BhForceError:
+        """Barnes-Hut force error of the current state against the direct sum on min(n, sample) distinct caller indices
+        drawn with numpy.random.default_rng(seed) (or on `targets`): force_error_stats of force_check."""
+        if targets is None:
+            targets = sample_targets(self.n, sample, seed)
+        t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+        tree, direct = self.force_check(t)
+        return force_error_stats(tree, direct, t)
 
     # -- tree output ------------------------------------------------------------------------
     def export_tree(self):

@@ -23,7 +23,7 @@ import time
 
 import numpy as np
 
-from .engine import BarnesHutEngine, BhConfig, Precision
+from .engine import BarnesHutEngine, BhConfig, Precision, sample_targets
 from .textio import loadSimulationDataFromText
 
 # project.cu:27-35, 60-61
@@ -72,7 +72,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      theta: float = THETA, g: float = G, delta_t: float = DELTA_T,
                      max_depth: int = QUADTREE_MAX_DEPTH, precision: Precision = Precision.F64_EXACT,
                      reference_compat: bool = True, out_dir: str = ".", device: int = 0,
-                     positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0):
+                     positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0,
+                     force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -82,7 +83,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     after every step); this downloads the positions every step.
     energy_file: also write the diagnostics of the state (BarnesHutEngine.energy) before the first step, after every
     energy_every-th step and after the last one, one line each: `step,t,kinetic,potential,total,px,py,Lz` (%.17g).
-    The steps in between still run batched, and the diagnostics are not part of gpu_parallel_duration_us."""
+    The steps in between still run batched, and the diagnostics are not part of gpu_parallel_duration_us.
+    force_error_file: likewise, with the same cadence rules (force_error_every), the Barnes-Hut force error of the state
+    against the direct sum (BarnesHutEngine.force_error) on min(n, force_error_sample) bodies drawn once, the same on
+    every line: `step,t,n,median,p90,p99,p999,max,worst`."""
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -103,12 +107,28 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         energy = None
         if energy_file is not None:
             energy = open(os.path.join(out_dir, energy_file) if not os.path.isabs(energy_file) else energy_file, "w")
+        ferr = None
+        if force_error_file is not None:
+            ferr = open(os.path.join(out_dir, force_error_file) if not os.path.isabs(force_error_file) else force_error_file, "w")
+            ferr_targets = sample_targets(n, force_error_sample)
         done = 0
+        # (file, steps between its lines, what writes a line)
+        samplers = []
 
-        def sample():
+        def sample_energy():
             e = eng.energy()
             energy.write(",".join([str(done)] + ["%.17g" % v for v in (done * delta_t, e.kinetic, e.potential, e.total,
                                                                        e.momentum[0], e.momentum[1], e.angular_momentum)]) + "\n")
+
+        def sample_force_error():
+            r = eng.force_error(targets=ferr_targets)
+            ferr.write(",".join([str(done), "%.17g" % (done * delta_t), str(r.n)]
+                                + ["%.17g" % v for v in (r.median, r.p90, r.p99, r.p999, r.max)] + [str(r.worst)]) + "\n")
+
+        if energy is not None:
+            samplers.append((energy_every, sample_energy))
+        if ferr is not None:
+            samplers.append((force_error_every, sample_force_error))
 
         def steps(k):
             nonlocal gpu_parallel_us, absolute_t
@@ -125,18 +145,22 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 _write_frame(traj, absolute_t, eng.download()[0])
 
         def advance(k):
-            # (with an energy file: batches that end at the sampled steps)
+            # (with an energy or force-error file: batches that end at the sampled steps)
             nonlocal done
             while k > 0:
-                j = k if energy is None or energy_every <= 0 else min(k, energy_every - done % energy_every)
+                j = k
+                for every, _ in samplers:
+                    if every > 0:
+                        j = min(j, every - done % every)
                 steps(j)
                 done += j
                 k -= j
-                if energy is not None and (done == n_simulations or (energy_every > 0 and done % energy_every == 0)):
-                    sample()
+                for every, write in samplers:
+                    if done == n_simulations or (every > 0 and done % every == 0):
+                        write()
 
-        if energy is not None:
-            sample()
+        for _, write in samplers:
+            write()
 
         step = 0
         while step < n_simulations:
@@ -157,8 +181,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         pos, vel = eng.download()
         if traj is not None:
             traj.close()
-        if energy is not None:
-            energy.close()
+        for f in (energy, ferr):
+            if f is not None:
+                f.close()
     return pos, vel, gpu_parallel_us
 
 
@@ -185,6 +210,13 @@ def _parse(argv):
                          "--energy-every steps and after the last")
     ap.add_argument("--energy-every", type=int, default=0, metavar="K",
                     help="steps between two lines of --energy-file (0: first and last state only)")
+    ap.add_argument("--force-error-file", default=None, metavar="PATH",
+                    help="also write step,t,n,median,p90,p99,p999,max,worst (Barnes-Hut force error against the direct "
+                         "sum) before the first step, every --force-error-every steps and after the last")
+    ap.add_argument("--force-error-every", type=int, default=0, metavar="K",
+                    help="steps between two lines of --force-error-file (0: first and last state only)")
+    ap.add_argument("--force-error-sample", type=int, default=65536, metavar="S",
+                    help="bodies in the force-error sample (drawn once; all bodies when S >= N_BODIES)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -247,7 +279,8 @@ def main(argv=None) -> int:
         theta=a.theta, max_depth=a.max_depth,
         precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32,
         reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
-        energy_every=a.energy_every)
+        energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
+        force_error_sample=a.force_error_sample)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -265,6 +265,23 @@ int bh_get_potential(bh_ctx *ctx, double *phi, uint32_t *counts);
  * same bits).  Only the final sums reach the host. */
 int bh_energy(bh_ctx *ctx, bh_energy_t *out);
 
+/* --- exact forces and the Barnes-Hut force error ------------------------------------------
+ * bh_direct_forces: fp64 direct-sum forces of the CURRENT state, computeForces of main_approach_1.cpp:53-75 bit for
+ * bit (in BH_PRECISION_F32 of the fp32 state widened exactly): for each target i, the sum over j = 0 .. n-1 in caller
+ * order, j != i, of ((G m_i) m_j) / (d2 d) * (dx, dy) with IEEE sqrt and division, in every precision.  targets:
+ * caller indices (any order, repeats allowed), or NULL for all n bodies in caller order (then n_targets must be n);
+ * forces[n_targets][2], FORCE with m_i included.  Reads the state only: no tree, nothing of the run changes.
+ * Coincident bodies give inf / NaN as in the reference (NaN payloads are not part of the contract).
+ * bh_force_check: tree[k][2] are the precision's Barnes-Hut forces of the current state -- a tree built as the
+ * diagnostics build theirs and the force walk bh_compute_forces would run (n_threads applies), accelerations times m_i
+ * in BH_PRECISION_F32 / MIXED -- and direct[k][2] the bh_direct_forces of the same targets.  A following bh_step is
+ * bit for bit unchanged, and bh_get_forces, bh_get_interaction_counts, bh_stats (walk_launches, the walk counters) and
+ * the ORB weights still describe the last real force walk.
+ * Both: BH_ERR_ARG for a null output array, n_targets < 0 or a target outside [0, n); BH_ERR_STATE before upload and in
+ * LET mode or with world > 1.  n_targets = 0 is valid.  Device buffers are allocated on first use. */
+int bh_direct_forces(bh_ctx *ctx, const int64_t *targets, int64_t n_targets, double *forces);
+int bh_force_check(bh_ctx *ctx, const int64_t *targets, int64_t n_targets, double *tree, double *direct);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
