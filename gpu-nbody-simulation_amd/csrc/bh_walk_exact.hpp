@@ -748,6 +748,15 @@ __global__ __launch_bounds__(kBlock) void walk_exact_bfs_kernel(
                                        (int32_t)body, COMPAT ? (int32_t)(-body - 2) : (int32_t)body, fx, fy);
 #pragma clang diagnostic pop
             }
+            // only lane 0 walked (live = 1): every lane takes its sums, or lane `turn` would record p + v * dt without the
+            // force for the workgroup's bounds (tests/test_gpu_walk_bounds.py)
+            auto lane0 = [](double x) {
+                const uint64_t b = __builtin_bit_cast(uint64_t, x);
+                return __builtin_bit_cast(double, ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(b >> 32)) << 32) |
+                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)b));
+            };
+            fx = lane0(fx);
+            fy = lane0(fy);
         }
     }
 

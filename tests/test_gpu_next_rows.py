@@ -14,6 +14,7 @@ from oracle import bh_oracle as O  # noqa: E402
 import gpu_nbody_simulation_amd as G  # noqa: E402
 from gpu_nbody_simulation_amd.engine import FLAG_WALK_NO_SPLIT  # noqa: E402
 from gpu_nbody_simulation_amd import project, scaling, textio  # noqa: E402
+from box_ref import box_ref, root_box  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -229,17 +230,6 @@ def test_overflow_under_n_threads_keeps_the_last_good_state(precision):
     assert np.array_equal(a, b)
 
 
-def _box_formula(p):
-    """ComputeRootBounds (project.cu:536-573): min/max from +-inf (a NaN never wins), padded by a tenth of the larger side."""
-    xs, ys = p[:, 0][~np.isnan(p[:, 0])], p[:, 1][~np.isnan(p[:, 1])]
-    lo = np.array([xs.min(initial=np.inf), ys.min(initial=np.inf)])
-    hi = np.array([xs.max(initial=-np.inf), ys.max(initial=-np.inf)])
-    ex, ey = hi - lo
-    span = ey if ex < ey else ex
-    pad = 1e-6 if span == 0.0 else 0.1 * span
-    return np.array([lo[0] - pad, hi[0] + pad, lo[1] - pad, hi[1] + pad])
-
-
 @pytest.mark.parametrize("precision", [G.Precision.F64_EXACT, G.Precision.F64, G.Precision.MIXED, G.Precision.F32])
 @pytest.mark.parametrize("case", ["n1", "n2", "one_nan", "all_nan"])
 def test_root_box_from_the_positions_pass(precision, case):
@@ -259,8 +249,8 @@ def test_root_box_from_the_positions_pass(precision, case):
         e.upload(p, v, m)
         e.build_tree()
         nodes, _ = e.export_tree()
-    box = np.array([nodes[0]["xmin"], nodes[0]["xmax"], nodes[0]["ymin"], nodes[0]["ymax"]])
-    expect = _box_formula(p)
+    box = root_box(nodes)
+    expect = box_ref(p)
     if case == "all_nan":
         assert np.array_equal(expect, [np.inf, -np.inf, np.inf, -np.inf])
     assert np.array_equal(box, expect)
