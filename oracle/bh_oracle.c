@@ -141,12 +141,13 @@ static void mass_pass(bho_node *nodes, int64_t ni, double *m_out, double *x_out,
     *m_out = tot; *x_out = sx; *y_out = sy;
 }
 
-int64_t bho_build_tree(const double *pos, const double *mass, int64_t n, int max_depth,
-                       bho_node *nodes, int64_t cap)
+/* The tree of `n` bodies under a GIVEN root cell box = {xmin, xmax, ymin, ymax} (every body inside it): the insertion and
+ * mass pass of bho_build_tree, which is this with bho_root_bounds of its own bodies.  A rank of the distributed step
+ * builds its local tree under the box of ALL ranks' bodies (tests/forest_ref.py). */
+int64_t bho_build_tree_box(const double *pos, const double *mass, int64_t n, int max_depth, const double box[4],
+                           bho_node *nodes, int64_t cap)
 {
     if (cap < 1) return -1;
-    double box[4];
-    bho_root_bounds(pos, n, box);
     build_ctx c = { nodes, 0, cap, pos, mass, max_depth, 0 };
     blank_node(&nodes[0], box[0], box[1], box[2], box[3]);
     c.count = 1;
@@ -157,6 +158,14 @@ int64_t bho_build_tree(const double *pos, const double *mass, int64_t n, int max
     double m, x, y;
     mass_pass(nodes, 0, &m, &x, &y);
     return c.count;
+}
+
+int64_t bho_build_tree(const double *pos, const double *mass, int64_t n, int max_depth,
+                       bho_node *nodes, int64_t cap)
+{
+    double box[4];
+    bho_root_bounds(pos, n, box);
+    return bho_build_tree_box(pos, mass, n, max_depth, box, nodes, cap);
 }
 
 /* ---- theta walk: project.cu:593-675 / main_approach_2.cpp:261-343 ------------------ */

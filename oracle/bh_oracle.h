@@ -49,6 +49,11 @@ void bho_root_bounds(const double *pos, int64_t n, double out[4]);
 int64_t bho_build_tree(const double *pos, const double *mass, int64_t n, int max_depth,
                        bho_node *nodes, int64_t cap);
 
+/* bho_build_tree under a given root cell box = {xmin, xmax, ymin, ymax} that holds every body (bho_build_tree is this with
+ * bho_root_bounds of its own bodies): the local tree of one rank of the distributed step under the global box. */
+int64_t bho_build_tree_box(const double *pos, const double *mass, int64_t n, int max_depth, const double box[4],
+                           bho_node *nodes, int64_t cap);
+
 /* project.cu:593-675 (compat_self_skip=1: `occ==i || occ+2==-i`) and
  * main_approach_2.cpp:261-343 (compat_self_skip=0: `occ==i`).  forces is AoS [n][2]
  * and holds FORCE (m_i included), as in the reference.  stats may be NULL. */

@@ -67,6 +67,8 @@ def lib() -> C.CDLL:
         L.bho_root_bounds.restype = None
         L.bho_build_tree.argtypes = [dp, dp, C.c_int64, C.c_int, vp, C.c_int64]
         L.bho_build_tree.restype = C.c_int64
+        L.bho_build_tree_box.argtypes = [dp, dp, C.c_int64, C.c_int, dp, vp, C.c_int64]
+        L.bho_build_tree_box.restype = C.c_int64
         L.bho_compute_forces_range.argtypes = [vp, dp, dp, C.c_int64, C.c_int64, C.c_double,
                                                C.c_double, C.c_int, dp, C.POINTER(_WalkStats)]
         L.bho_compute_forces_range.restype = None
@@ -124,6 +126,21 @@ def build_tree(pos, mass, max_depth: int = 10) -> np.ndarray:
     cnt = lib().bho_build_tree(_d(pos), _d(mass), n, max_depth, nodes.ctypes.data, cap)
     if cnt < 0:
         raise RuntimeError(f"bho_build_tree failed: {cnt}")
+    return nodes[:cnt].copy()
+
+
+def build_tree_box(pos, mass, box, max_depth: int = 10) -> np.ndarray:
+    """build_tree under the given root cell box = [xmin, xmax, ymin, ymax], which must hold every body."""
+    pos, mass, box = _f64(pos), _f64(mass), _f64(box).reshape(4)
+    n = pos.shape[0]
+    if n and not ((pos[:, 0] >= box[0]).all() and (pos[:, 0] <= box[1]).all()
+                  and (pos[:, 1] >= box[2]).all() and (pos[:, 1] <= box[3]).all()):
+        raise ValueError("a body lies outside the box")
+    cap = node_capacity(n, max_depth)
+    nodes = np.zeros(cap, dtype=NODE_DTYPE)
+    cnt = lib().bho_build_tree_box(_d(pos), _d(mass), n, max_depth, _d(box), nodes.ctypes.data, cap)
+    if cnt < 0:
+        raise RuntimeError(f"bho_build_tree_box failed: {cnt}")
     return nodes[:cnt].copy()
 
 

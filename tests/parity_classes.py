@@ -68,13 +68,17 @@ def sample_first(m, p, v, s):
     return m[perm], p[perm], v[perm], len(chosen)
 
 
-def classify(a_gpu, counts_gpu, m, p, theta, s, pos_rounded=False, tree=None, cap_depth=21) -> ClassReport:
+def classify(a_gpu, counts_gpu, m, p, theta, s, pos_rounded=False, tree=None, cap_depth=21, diag=None) -> ClassReport:
     """a_gpu, counts_gpu: accelerations and interaction counts of bodies [0, s) from the device; the oracle walks the
-    same bodies through the UNCAPPED tree (main_approach_2.cpp's; compat off sums a depth-cap cell body by body)."""
-    if tree is None:
-        tree = O.build_tree(p, m, 0)
-    d = O.compute_forces_diag(tree, p, m, theta=theta, compat_self_skip=False, hi=s, pos_rounded=pos_rounded,
-                              cap_depth=cap_depth)
+    same bodies through the UNCAPPED tree (main_approach_2.cpp's; compat off sums a depth-cap cell body by body).
+    diag: a precomputed O.WalkDiag of bodies [0, s) instead of that one tree's walk (tests/forest_ref.py: the sum over
+    the trees of a forest); tree, theta, pos_rounded and cap_depth are then not used."""
+    d = diag
+    if d is None:
+        if tree is None:
+            tree = O.build_tree(p, m, 0)
+        d = O.compute_forces_diag(tree, p, m, theta=theta, compat_self_skip=False, hi=s, pos_rounded=pos_rounded,
+                                  cap_depth=cap_depth)
     ms = m[:s]
     ao = d.forces[:s] / ms[:, None]
     ok = np.isfinite(ao).all(axis=1)

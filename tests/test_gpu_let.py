@@ -18,122 +18,10 @@ pytestmark = pytest.mark.gpu
 from oracle import bh_oracle as O  # noqa: E402
 import gpu_nbody_simulation_amd as G  # noqa: E402
 from gpu_nbody_simulation_amd import initial_conditions as IC  # noqa: E402
-from gpu_nbody_simulation_amd.distributed import (ORB_BINS, OrbCuts, choose_cut, padded_root_box,  # noqa: E402
-                                                  partition_hilbert, partition_orb, wrap_device)
+from gpu_nbody_simulation_amd.distributed import OrbCuts, choose_cut, wrap_device  # noqa: E402
 
 
-class EmulatedRanks:
-    def __init__(self, mass, pos, vel, world, let_cap, partition=partition_orb, headroom=1.0, **cfg):
-        self.world = world
-        self.parts = partition(pos, world)
-        dev = torch.device("cuda", 0)
-        self.engs, self.bufs = [], []
-        cfg.setdefault("precision", G.Precision.F32)
-        # every context sized for ITS OWN bodies, as bench.py does: the contexts' quad arrays then differ
-        # in size, and only the agreed forest_base makes a sender's links land in the receiver's blocks
-        for ix in self.parts:
-            e = G.BarnesHutEngine(G.BhConfig(capacity=max(int(headroom * len(ix)), 1), **cfg))
-            e.set_stream(torch.cuda.current_stream().cuda_stream)   # one stream for the contexts and the "collectives"
-            e.upload(pos[ix], vel[ix], mass[ix])
-            e.set_ids(ix)
-            self.engs.append(e)
-        self.forest_base = max(e.let_local_quads() for e in self.engs)
-        self.dev = dev
-        self.configure(let_cap)
-
-    def configure(self, let_cap):
-        self.let_cap, self.bufs = let_cap, []
-        dev, world = self.dev, self.world
-        for r, e in enumerate(self.engs):
-            e.let_configure(r, world, let_cap, self.forest_base)
-            lb, ab, sd, rv, nb, k = e.let_pointers()
-            self.bufs.append((wrap_device(lb, 4 * k, "<f8", dev), wrap_device(ab, 4 * k * world, "<f8", dev),
-                              wrap_device(sd, world * nb, "|u1", dev), wrap_device(rv, world * nb, "|u1", dev), nb))
-
-    def rebalance(self, tol=0.01):
-        """LetStepper.rebalance() with the three collectives replaced by device copies / sums between the
-        contexts of this one GPU: the device code (histogram, classify, group, pack, unpack) is the real one.
-        Returns (cuts, summed histograms per level)."""
-        W, dev = self.world, self.dev
-        for e in self.engs:
-            e.let_bounds()
-        torch.cuda.synchronize()
-        b = torch.cat([x[0] for x in self.bufs]).cpu().numpy().reshape(-1, 4)
-        b = b[np.isfinite(b).all(1) & (b[:, 0] <= b[:, 1])]
-        cuts = OrbCuts(W, padded_root_box(b[:, 0].min(), b[:, 1].max(), b[:, 2].min(), b[:, 3].max()))
-        hists = []
-        for level in range(cuts.depth()):
-            regs = cuts.regions(level)
-            for k, _, _, rb in regs:
-                cuts.axis[k] = int((rb[3] - rb[2]) > (rb[1] - rb[0]))
-            tot = None
-            for e in self.engs:
-                ptr, nw = e.orb_histogram(cuts, level)
-                h = wrap_device(ptr, nw, "<i8", dev).clone()
-                tot = h if tot is None else tot + h                      # "all_reduce"
-            hh = tot.cpu().numpy().reshape(-1, ORB_BINS)
-            hists.append(hh)
-            for k, _, nr, rb in regs:
-                cuts.value[k] = choose_cut(hh[k], rb, cuts.box, int(cuts.axis[k]), (nr // 2) / nr, tol)
-        counts = [e.migrate_pack(cuts) for e in self.engs]               # counts[src][dst]
-        ptrs = [e.migrate_pointers() for e in self.engs]
-        send = [wrap_device(p[0], p[2] * 6, "<f8", dev) for p in ptrs]
-        recv = [wrap_device(p[1], p[2] * 6, "<f8", dev) for p in ptrs]
-        for dst in range(W):                                             # "all_to_all_single" with splits
-            o = 0
-            for src in range(W):
-                c = counts[src][dst]
-                so = sum(counts[src][:dst])
-                assert o + c <= ptrs[dst][2], "capacity"
-                recv[dst][6 * o: 6 * (o + c)].copy_(send[src][6 * so: 6 * (so + c)])
-                o += c
-            self.engs[dst].migrate_unpack(o)
-        torch.cuda.synchronize()
-        self.cuts = cuts
-        return cuts, hists
-
-    def ids(self):
-        return [e.ids() for e in self.engs]
-
-    def step(self, integrate=True, two_launches=False):
-        for e in self.engs:
-            e.let_bounds()
-            e.sync()
-        allb = torch.cat([b[0] for b in self.bufs])                 # "all_gather"
-        for b in self.bufs:
-            b[1].copy_(allb)
-        torch.cuda.synchronize()
-        for e in self.engs:
-            e.let_build()
-            e.sync()
-        for r in range(self.world):                                  # "all_to_all"
-            nb = self.bufs[r][4]
-            for q in range(self.world):
-                if q != r:
-                    self.bufs[q][3][r * nb:(r + 1) * nb].copy_(self.bufs[r][2][q * nb:(q + 1) * nb])
-        torch.cuda.synchronize()
-        for e in self.engs:
-            if two_launches:
-                e.let_walk_local()
-                e.let_walk_remote(integrate)
-            else:
-                e.let_walk() if integrate else e.let_forces()
-            e.sync()
-
-    def gather(self, what):
-        n = sum(e.n for e in self.engs)
-        out = np.zeros((n, 2))
-        for e in self.engs:
-            out[e.ids()] = what(e)                                       # ids = the caller's global indices
-        return out
-
-    def close(self):
-        for e in self.engs:
-            e.close()
-
-
-def rel(a, ref):
-    return np.linalg.norm(a - ref, axis=1) / np.linalg.norm(ref, axis=1)
+from let_ranks import EmulatedRanks, rel  # noqa: E402
 
 
 @pytest.mark.parametrize("world", [2, 5])

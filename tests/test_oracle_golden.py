@@ -34,6 +34,7 @@ def test_project_1024_step0_tree_forces_state(gold, init1024):
     t = O.build_tree(p, m, 10)
     assert len(t) == 3085 == int(g["tree_0_n_nodes"])          # SURVEY 8(c) known answer
     assert _same_tree(t, g["tree_0"])
+    assert t.tobytes() == O.build_tree_box(p, m, O.root_bounds(p), 10).tobytes()     # the box variant, given the same box
     f, st = O.compute_forces(t, p, m, with_stats=True)
     assert np.array_equal(f, g["forces_0"])
     assert st.interactions == 104117 and st.max_stack == 20     # 101.7/body, stack 20
