@@ -19,6 +19,7 @@
 #include "bh_walk_f64.hpp"
 #include "bh_diag.hpp"
 #include "bh_direct.hpp"
+#include "bh_field.hpp"
 #include "bh_init.hpp"
 #include "bh_let.hpp"
 #include "bh_migrate.hpp"
@@ -151,6 +152,15 @@ struct bh_ctx {
     void *check_force = nullptr;
     uint32_t *check_counts = nullptr, *check_cost = nullptr;
     TreeCounters *ctr_save = nullptr;
+    // the field at arbitrary points (bh_field.hpp), allocated on first use: one block for a launch of up to field_cap points --
+    // the points, their results, two key arrays and the sorted order, the sort's count matrix and row totals
+    char *field_block = nullptr;
+    int64_t field_cap = 0;
+    uint64_t field_bytes = 0;
+    double2 *field_points = nullptr, *field_accel = nullptr;
+    uint64_t *field_keys[2] = {nullptr, nullptr};
+    double *field_phi = nullptr;
+    uint32_t *field_order = nullptr, *field_counts = nullptr, *field_radix = nullptr, *field_rows = nullptr;
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -1351,7 +1361,7 @@ static int check_walk(bh_ctx *c, double *out)
         char *f = nullptr;
         rc = dev_alloc(c, &f, cap * 2 * (c->tree64() ? sizeof(double) : sizeof(float)));
         c->check_force = f;
-        if (!rc) rc = dev_alloc(c, &c->ctr_save, 1);
+        if (!rc && !c->ctr_save) rc = dev_alloc(c, &c->ctr_save, 1);
         if (!rc && c->group_cost) rc = dev_alloc(c, &c->check_cost, cap / kWave + 2);
         if (rc) return rc;
     }
@@ -1402,6 +1412,114 @@ int bh_force_check(bh_ctx *c, const int64_t *targets, int64_t n_targets, double 
         tree[2 * t] = all[2 * i]; tree[2 * t + 1] = all[2 * i + 1];
     }
     return direct_forces_host(c, targets, n_targets, direct);
+}
+
+// ---- the field at arbitrary points (bh_field.hpp)
+// The tree comes from a quiet build (enqueue_quiet_build), with the walk counters of bh_stats copied aside and put back as in
+// check_walk (keys_kernel clears them).  The kernels read the tree and the call's own buffers and write the call's own buffers
+// only: force, body_counts, group_cost, phi, the event timings and walk_launches are not touched.
+static int field_alloc(bh_ctx *c, int64_t want)
+{
+    if (want <= c->field_cap) return BH_OK;
+    int64_t cap = 1024;
+    while (cap < want) cap <<= 1;                              // (want <= kFieldChunk, a power of two)
+    if (c->field_block) {                                      // (the previous call has waited for its stream)
+        dev_free(c, c->field_block);
+        c->device_bytes -= c->field_bytes;
+        c->field_block = nullptr; c->field_cap = 0; c->field_bytes = 0;
+    }
+    const size_t nbl = blocks_for(cap, kBlock * kFieldSortItems);
+    const size_t per_point = 2 * sizeof(double2) + 2 * sizeof(uint64_t) + sizeof(double) + 2 * sizeof(uint32_t);
+    const size_t bytes = (size_t)cap * per_point + ((size_t)kRadix * nbl + kRadix) * sizeof(uint32_t);
+    char *b = nullptr;
+    if (int rc = dev_alloc(c, &b, bytes)) return rc;
+    c->field_block = b; c->field_cap = cap; c->field_bytes = bytes;
+    auto take = [&](auto **out, size_t count) {
+        using T = typename std::remove_reference<decltype(**out)>::type;
+        *out = reinterpret_cast<T *>(b);
+        b += count * sizeof(T);
+    };
+    take(&c->field_points, (size_t)cap); take(&c->field_accel, (size_t)cap);       // (16-byte records first: every array aligned)
+    take(&c->field_keys[0], (size_t)cap); take(&c->field_keys[1], (size_t)cap); take(&c->field_phi, (size_t)cap);
+    take(&c->field_order, (size_t)cap); take(&c->field_counts, (size_t)cap);
+    take(&c->field_radix, (size_t)kRadix * nbl); take(&c->field_rows, (size_t)kRadix);
+    return BH_OK;
+}
+
+// one launch of k <= field_cap points that are in field_points: keys, sort, walk; results at the points' places
+static int enqueue_field(bh_ctx *c, int64_t k)
+{
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(k, kBlock);
+    hipLaunchKernelGGL(field_keys_kernel, dim3(grid), dim3(kBlock), 0, st, c->field_points, k, c->box, c->field_keys[0]);
+    constexpr int SI = kFieldSortItems, SB = kSortBits, passes = kFieldKeyBits / SB;
+    static_assert(kFieldKeyBits % SB == 0 && kFieldKeyBits <= kPackShift && kFieldChunk <= ((int64_t)1 << (64 - kPackShift)),
+                  "the keys and the indices of a launch share a word");
+    const unsigned nbl = blocks_for(k, kBlock * SI);
+    int cur = 0;
+    for (int p = 0; p < passes; ++p) {
+        const int shift = p * SB;
+        hipLaunchKernelGGL((radix_hist<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], c->field_radix, k, shift, (int)nbl);
+        hipLaunchKernelGGL(radix_rowscan, dim3(1 << SB), dim3(kBlock), 0, st, c->field_radix, c->field_rows, (int)nbl);
+        if (p + 1 < passes)
+            hipLaunchKernelGGL((radix_scatter_w<SI, SB, 1>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], nullptr,
+                               c->field_keys[cur ^ 1], c->field_order, c->field_radix, c->field_rows, k, shift, (int)nbl);
+        else
+            hipLaunchKernelGGL((radix_scatter_w<SI, SB, 2>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], nullptr,
+                               c->field_keys[cur ^ 1], c->field_order, c->field_radix, c->field_rows, k, shift, (int)nbl);
+        cur ^= 1;
+    }
+    if (c->tree64()) {
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, c->gd, c->ld, c->field_order, c->field_points, k, c->cfg.theta,
+                               c->cfg.G, c->ctr, c->field_accel, c->field_phi, c->field_counts);
+        };
+        if (c->mode == Mode::F64) go(field_f64_kernel<kAcceptThr>);
+        else if (c->exact_thresholds) go(field_f64_kernel<kAcceptExactThr>);
+        else go(field_f64_kernel<kAcceptSize>);
+    } else {
+        hipLaunchKernelGGL(field_f32_kernel, dim3(grid), dim3(kBlock), 0, st, c->qf, c->aux, c->spos, c->smass, c->field_order,
+                           c->field_points, k, c->cfg.G, c->ctr, c->field_accel, c->field_phi, c->field_counts);
+    }
+    BH_HIP(c, hipGetLastError());
+    return BH_OK;
+}
+
+int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel, double *phi, uint32_t *counts)
+{
+    if (!c) return BH_ERR_ARG;
+    if (n_points < 0 || (n_points > 0 && !points) || (!accel && !phi && !counts))
+        return fail(c, BH_ERR_ARG, "bh_field_at: n_points < 0, null points or no output array");
+    if (int rc = diag_check(c, "bh_field_at")) return rc;
+    for (int64_t i = 0; i < 2 * n_points; ++i)
+        if (!std::isfinite(points[i]))
+            return fail(c, BH_ERR_ARG, "bh_field_at: point " + std::to_string(i / 2) + " has a non-finite coordinate");
+    if (n_points == 0) return BH_OK;
+    if (c->n == 0) {                                           // no bodies: no field, no terms
+        if (accel) std::fill(accel, accel + 2 * n_points, 0.0);
+        if (phi) std::fill(phi, phi + n_points, 0.0);
+        if (counts) std::fill(counts, counts + n_points, 0u);
+        return BH_OK;
+    }
+    BH_HIP(c, hipSetDevice(c->device));
+    if (!c->ctr_save) { if (int rc = dev_alloc(c, &c->ctr_save, 1)) return rc; }
+    if (int rc = field_alloc(c, std::min(n_points, kFieldChunk))) return rc;
+    constexpr size_t wc_off = offsetof(TreeCounters, visits), wc_bytes = sizeof(TreeCounters) - wc_off;
+    BH_HIP(c, hipMemcpyAsync((char *)c->ctr_save + wc_off, (char *)c->ctr + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    int rc = enqueue_quiet_build(c);
+    BH_HIP(c, hipMemcpyAsync((char *)c->ctr + wc_off, (char *)c->ctr_save + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (!rc) rc = check_overflow(c);
+    if (rc) return rc;
+    for (int64_t t0 = 0; t0 < n_points; t0 += kFieldChunk) {
+        const int64_t k = std::min(kFieldChunk, n_points - t0);
+        BH_HIP(c, hipMemcpyAsync(c->field_points, points + 2 * t0, (size_t)k * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+        if ((rc = enqueue_field(c, k))) return rc;
+        if (accel) BH_HIP(c, hipMemcpyAsync(accel + 2 * t0, c->field_accel, (size_t)k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        if (phi) BH_HIP(c, hipMemcpyAsync(phi + t0, c->field_phi, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (counts) BH_HIP(c, hipMemcpyAsync(counts + t0, c->field_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        BH_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return BH_OK;
 }
 
 // ---- tree export: DFS pre-order, children in index order (TraverseTreeToFile, project.cu:504-534)

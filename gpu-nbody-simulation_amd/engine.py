@@ -301,6 +301,20 @@ class BarnesHutEngine:
         tree, direct = self.force_check(t)
         return force_error_stats(tree, direct, t)
 
+    # -- the field at arbitrary points ----------------------------------------------------------
+    def field(self, points, with_counts: bool = False):
+        """(accel (k, 2), phi (k,)[, counts (k,)]) at the coordinates `points` (k, 2): what the precision's Barnes-Hut walk
+        of the current state gives a body standing there that is nobody -- no self skip, so a point ON a body is
+        non-finite in the fp64 precisions and feels nothing of that body in F32 / MIXED.  Row t belongs to points[t],
+        whatever else is in the list.  Builds a tree; the run is not perturbed."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        k = len(p)
+        acc, phi = np.zeros((max(k, 1), 2)), np.zeros(max(k, 1))
+        cnt = np.zeros(max(k, 1), dtype=np.uint32) if with_counts else None
+        self._check(self._lib.bh_field_at(self._h, _dptr(p) if k else None, k, _dptr(acc), _dptr(phi),
+                                          cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if with_counts else None))
+        return (acc[:k], phi[:k], cnt[:k]) if with_counts else (acc[:k], phi[:k])
+
     # -- tree output ------------------------------------------------------------------------
     def export_tree(self):
         """(nodes in DFS pre-order as TREE_NODE_DTYPE, depth)."""

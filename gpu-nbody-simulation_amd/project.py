@@ -73,7 +73,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      max_depth: int = QUADTREE_MAX_DEPTH, precision: Precision = Precision.F64_EXACT,
                      reference_compat: bool = True, out_dir: str = ".", device: int = 0,
                      positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0,
-                     force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536):
+                     force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
+                     field_file: str | None = None, field_grid=None, field_box=None):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -86,7 +87,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     The steps in between still run batched, and the diagnostics are not part of gpu_parallel_duration_us.
     force_error_file: likewise, with the same cadence rules (force_error_every), the Barnes-Hut force error of the state
     against the direct sum (BarnesHutEngine.force_error) on min(n, force_error_sample) bodies drawn once, the same on
-    every line: `step,t,n,median,p90,p99,p999,max,worst`."""
+    every line: `step,t,n,median,p90,p99,p999,max,worst`.
+    field_file: after the last step, also write the Barnes-Hut field of the final state (BarnesHutEngine.field) on the
+    cell-centred field_grid = (NX, NY) grid over field_box = (xmin, xmax, ymin, ymax) (None: the bounding box of the final
+    positions): the line `# x,y,ax,ay,phi`, then one row per point (%.17g), y the outer axis.  Not part of
+    gpu_parallel_duration_us."""
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -179,12 +184,35 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 advance(k)
                 step += k
         pos, vel = eng.download()
+        if field_file is not None:
+            pts = field_grid_points(field_grid, field_box, pos)
+            acc, phi = eng.field(pts)
+            with open(os.path.join(out_dir, field_file) if not os.path.isabs(field_file) else field_file, "w") as f:
+                f.write("# x,y,ax,ay,phi\n")
+                f.write("".join("%.17g,%.17g,%.17g,%.17g,%.17g\n" % (x, y, a[0], a[1], q) for (x, y), a, q in zip(pts, acc, phi)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr):
             if f is not None:
                 f.close()
     return pos, vel, gpu_parallel_us
+
+
+def field_grid_points(grid, box, positions) -> np.ndarray:
+    """The (NX * NY, 2) cell centres of the NX x NY grid over box = (xmin, xmax, ymin, ymax) in row-major order, y the
+    outer axis; box None: the bounding box of `positions`."""
+    nx, ny = (int(g) for g in grid)
+    if nx < 1 or ny < 1:
+        raise ValueError("the field grid needs at least one cell per axis")
+    if box is None:
+        p = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+        if len(p) == 0:
+            raise ValueError("no bodies: give the field box")
+        box = (p[:, 0].min(), p[:, 0].max(), p[:, 1].min(), p[:, 1].max())
+    x0, x1, y0, y1 = (float(b) for b in box)
+    xs = x0 + (np.arange(nx) + 0.5) * ((x1 - x0) / nx)
+    ys = y0 + (np.arange(ny) + 0.5) * ((y1 - y0) / ny)
+    return np.stack([np.tile(xs, ny), np.repeat(ys, nx)], axis=1)
 
 
 def _write_frame(f, t: float, pos) -> None:
@@ -217,6 +245,12 @@ def _parse(argv):
                     help="steps between two lines of --force-error-file (0: first and last state only)")
     ap.add_argument("--force-error-sample", type=int, default=65536, metavar="S",
                     help="bodies in the force-error sample (drawn once; all bodies when S >= N_BODIES)")
+    ap.add_argument("--field-file", default=None, metavar="PATH",
+                    help="after the last step, also write x,y,ax,ay,phi of the Barnes-Hut field on the --field-grid")
+    ap.add_argument("--field-grid", type=int, nargs=2, default=None, metavar=("NX", "NY"),
+                    help="cells of the cell-centred grid of --field-file (row-major rows, y the outer axis)")
+    ap.add_argument("--field-box", type=float, nargs=4, default=None, metavar=("XMIN", "XMAX", "YMIN", "YMAX"),
+                    help="what the grid covers (default: the bounding box of the final positions)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -226,6 +260,10 @@ def _parse(argv):
     ap.add_argument("-o", dest="ignored_output", help="accepted and ignored (nvcc line compatibility)")
     ap.add_argument("source", nargs="?", help="accepted and ignored (nvcc line compatibility)")
     a = ap.parse_args(argv)
+    if (a.field_file is None) != (a.field_grid is None):
+        ap.error("--field-file and --field-grid go together")
+    if a.field_box is not None and a.field_file is None:
+        ap.error("--field-box needs --field-file")
     # project.cu:1-11.  N_THREADS: the reference's default is 1,024 CUDA threads striding over the bodies; here it
     # caps the bodies walked at a time ONLY when given (-DN_THREADS=... / --n-threads, as the scaling scripts do):
     # unset, a step walks all bodies in one launch.
@@ -280,7 +318,7 @@ def main(argv=None) -> int:
         precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32,
         reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
         energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
-        force_error_sample=a.force_error_sample)
+        force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -282,6 +282,31 @@ int bh_energy(bh_ctx *ctx, bh_energy_t *out);
 int bh_direct_forces(bh_ctx *ctx, const int64_t *targets, int64_t n_targets, double *forces);
 int bh_force_check(bh_ctx *ctx, const int64_t *targets, int64_t n_targets, double *tree, double *direct);
 
+/* --- the field at arbitrary points ----------------------------------------------------------
+ * bh_field_at: what the precision's Barnes-Hut walk of the CURRENT state gives at caller coordinates that are nobody's.
+ * points[n_points][2]; accel[n_points][2] the acceleration (force per unit mass, G included), phi[n_points] the potential
+ * per unit mass over the same terms, counts[n_points] the number of terms taken; any output may be NULL, but not all
+ * three.  Results are in the order of `points`.
+ * Term set: exactly the terms the precision's force walk would take for a body standing at the point -- the
+ * `mass <= 1e-15` cut-off, the force walk's acceptance decisions (read from the node data it compares against),
+ * depth-cap aggregates as point masses, fp32 bucket leaves body by body -- without any self skip: a point is no body.
+ *   BH_PRECISION_F64_EXACT / F64: d = sqrt(d2) + 1e-15, a += ((G M) / d2) * (dx / d), phi -= (G M) / d
+ *     (project.cu:630-658 with m_i = 1), IEEE sqrt and division.  A point that COINCIDES with a body gets what that
+ *     expression gives there: inf * 0, a non-finite acceleration (the potential stays finite: -G M / 1e-15).
+ *   BH_PRECISION_F32 / MIXED: the point is rounded to fp32 on the device; the fp32 walk's terms (ri = rsq(d2),
+ *     w = m ri ri ri; w dx, w dy, m ri) in fp32, summed in fp64, times G in fp64.  A node or bucket body at d2 == 0
+ *     contributes nothing, as in the fp32 walk.
+ * A point's result does not depend on the other points of the call, their order or their number (the points are
+ * Morton-sorted on the device and walked 64 to a wavefront, up to 2^20 per launch; every lane adds its own terms in a
+ * fixed order).  Points outside the root box are valid.  With no bodies the field is 0 and the counts are 0.
+ * Like the diagnostics, the call builds its own tree of the current state and does not perturb the run: a following
+ * bh_step is bit for bit what it would have been, and bh_get_forces, bh_get_interaction_counts, bh_stats (the walk
+ * counters, walk_launches), the step timings and the ORB weights still describe the last real force walk.
+ * BH_ERR_ARG: n_points < 0, points == NULL with n_points > 0, all outputs NULL, a non-finite coordinate (checked
+ * before anything is enqueued).  BH_ERR_STATE before upload, in LET mode or with world > 1.  n_points = 0 is valid.
+ * Device buffers for one launch are allocated on first use (bh_stats.device_bytes grows then). */
+int bh_field_at(bh_ctx *ctx, const double *points, int64_t n_points, double *accel, double *phi, uint32_t *counts);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
