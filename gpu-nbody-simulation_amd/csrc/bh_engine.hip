@@ -235,6 +235,19 @@ void dispatch(F &&f, bool b, B... rest)
     else dispatch([&](auto... t) { f(std::false_type{}, t...); }, rest...);
 }
 
+// f(double2{}) or f(float2{}): the vector type of the state arrays (its scalar type is decltype(Real2{}.x))
+template <typename F>
+void with_state(const bh_ctx *c, F &&f)
+{
+    if (c->state64()) f(double2{}); else f(float2{});
+}
+
+// bytes of a walk's output for n bodies: forces (fp64 tree) or accelerations (fp32 / mixed)
+inline size_t force_bytes(const bh_ctx *c, int64_t n)
+{
+    return (size_t)std::max<int64_t>(n, 1) * 2 * (c->tree64() ? sizeof(double) : sizeof(float));
+}
+
 // node kernels and the mass pass: one thread per subdivided cell; I <= (n-1)*Dm and <= internal_cap (at least one
 // thread: the root-only case)
 inline int64_t cell_span(const bh_ctx *c)
@@ -296,6 +309,34 @@ void clean_slots(bh_ctx *c)
 {
     if (c->slots_dirty) hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
     c->slots_dirty = true;
+}
+
+// Stable LSD radix sort of n keys over key bits [0, bits): kSortBits-wide digits, wave-private ranking, digit-sorted
+// write-out, tiles of kBlock * SI keys.  Pass p reads keys[cur] / vals[cur] and writes keys[cur ^ 1] / vals[cur ^ 1], cur = 0
+// first; returns the cur that holds the result.  packed: the index travels in the key word, no pass reads a value array (the
+// kernels get a null input) and only the last writes one: the unpacked {key, index} pair.
+template <int SI>
+int enqueue_lsd_passes(hipStream_t st, uint64_t *const keys[2], uint32_t *const vals[2], uint32_t *counts, uint32_t *rows, int64_t n,
+                       int bits, bool packed)
+{
+    constexpr int SB = kSortBits;
+    const unsigned nbl = blocks_for(n, kBlock * SI);
+    const int passes = (bits + SB - 1) / SB;
+    int cur = 0;
+    for (int p = 0; p < passes; ++p) {
+        const int shift = p * SB;
+        auto scatter = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nbl), dim3(kBlock), 0, st, keys[cur], packed ? nullptr : vals[cur], keys[cur ^ 1],
+                               vals[cur ^ 1], counts, rows, n, shift, (int)nbl, nullptr, nullptr);
+        };
+        hipLaunchKernelGGL((radix_hist<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, keys[cur], counts, n, shift, (int)nbl);
+        hipLaunchKernelGGL(radix_rowscan, dim3(1 << SB), dim3(kBlock), 0, st, counts, rows, (int)nbl);
+        if (!packed) scatter(radix_scatter_w<SI, SB>);
+        else if (p + 1 == passes) scatter(radix_scatter_w<SI, SB, 2>);
+        else scatter(radix_scatter_w<SI, SB, 1>);
+        cur ^= 1;
+    }
+    return cur;
 }
 
 template <bool TREE64, bool STATE64 = TREE64, int ITEMS = kItems>
@@ -391,26 +432,8 @@ int enqueue_build_t(bh_ctx *c)
                                c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0);
             cur = 0;
         } else {
-            // kSortBits-wide digits, wave-private ranking, digit-sorted write-out
-            constexpr int SB = kSortBits, SR = 1 << SB, SI = (ITEMS == kItems ? kSortItems : ITEMS);
-            const int passes = (2 * Dm + SB - 1) / SB;
-            for (int p = 0; p < passes; ++p) {
-                const int shift = p * SB;
-                hipLaunchKernelGGL((radix_hist<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, c->keys[cur], c->radix_counts, n,
-                                   shift, (int)nbl);
-                hipLaunchKernelGGL(radix_rowscan, dim3(SR), dim3(kBlock), 0, st, c->radix_counts, c->bsum_sort, (int)nbl);
-                if (pack && p + 1 < passes)
-                    hipLaunchKernelGGL((radix_scatter_w<SI, SB, 1>), dim3(nbl), dim3(kBlock), 0, st, c->keys[cur], c->vals[cur],
-                                       c->keys[cur ^ 1], c->vals[cur ^ 1], c->radix_counts, c->bsum_sort, n, shift, (int)nbl);
-                else if (pack)
-                    hipLaunchKernelGGL((radix_scatter_w<SI, SB, 2>), dim3(nbl), dim3(kBlock), 0, st, c->keys[cur], c->vals[cur],
-                                       c->keys[cur ^ 1], c->vals[cur ^ 1], c->radix_counts, c->bsum_sort, n, shift, (int)nbl);
-                else
-                    hipLaunchKernelGGL((radix_scatter_w<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, c->keys[cur], c->vals[cur],
-                                       c->keys[cur ^ 1], c->vals[cur ^ 1], c->radix_counts, c->bsum_sort, n, shift,
-                                       (int)nbl);
-                cur ^= 1;
-            }
+            constexpr int SI = (ITEMS == kItems ? kSortItems : ITEMS);
+            cur = enqueue_lsd_passes<SI>(st, c->keys, c->vals, c->radix_counts, c->bsum_sort, n, 2 * Dm, pack);
         }
         c->keys_sorted = c->keys[cur];
         c->perm = c->vals[cur];
@@ -766,19 +789,25 @@ int check_overflow(bh_ctx *c)
     return BH_OK;
 }
 
+// the state arrays hold another set of bodies, in caller order: nothing an earlier build, walk or potential left describes them
+void forget_body_set(bh_ctx *c)
+{
+    c->partial_count = 0; c->slots_valid = false;
+    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
+    c->phi_current = false;
+    c->tree_valid = false;
+    c->orig_identity = true;
+    c->builds = 0;
+    c->group_cost_valid = false;
+}
+
 // bh_upload / bh_initialize: the state arrays hold n new bodies in caller order
 int new_bodies(bh_ctx *c, int64_t n)
 {
     c->n = n;
-    c->partial_count = 0; c->slots_valid = false;
-    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
+    forget_body_set(c);
     c->uploaded = true;
-    c->tree_valid = false;
     c->steps_done = 0;
-    c->orig_identity = true;
-    c->builds = 0;
-    c->group_cost_valid = false;
-    c->phi_current = false;
     if (c->gid && n > 0) {
         hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
         BH_HIP(c, hipGetLastError());
@@ -864,7 +893,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     { char *t; A(&t, cap * 2 * rs); c->pos = t; }
     { char *t; A(&t, cap * 2 * rs); c->vel = t; }
     { char *t; A(&t, cap * rs); c->mass = t; }
-    { char *t; A(&t, cap * 2 * (c->tree64() ? sizeof(double) : sizeof(float))); c->force = t; }
+    { char *t; A(&t, force_bytes(c, cap)); c->force = t; }
     if (!c->tree64()) {
         { char *t; A(&t, cap * 2 * rs); c->pos2 = t; }
         { char *t; A(&t, cap * 2 * rs); c->vel2 = t; }
@@ -966,7 +995,7 @@ int bh_upload(bh_ctx *c, const double *pos, const double *vel, const double *mas
         for (int64_t i = 0; i < n; ++i) t[i] = (float)mass[i];
         BH_HIP(c, hipMemcpy(c->mass, t.data(), n * sizeof(float), hipMemcpyHostToDevice));
     }
-    BH_HIP(c, hipMemset(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->tree64() ? sizeof(double) : sizeof(float))));
+    BH_HIP(c, hipMemset(c->force, 0, force_bytes(c, n)));
     return new_bodies(c, n);
 }
 
@@ -995,6 +1024,20 @@ static int to_caller_order(bh_ctx *c, double *host, int per)
     return BH_OK;
 }
 
+// one uint32 per body, read from the device in DEVICE order -> out in caller order (an fp64 tree never re-orders its
+// state: orig_identity holds there)
+static int counts_to_caller_order(bh_ctx *c, const uint32_t *dev_counts, uint32_t *out)
+{
+    const int64_t n = c->n;
+    if (n == 0) return BH_OK;
+    if (c->orig_identity) { BH_HIP(c, hipMemcpy(out, dev_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return BH_OK; }
+    std::vector<uint32_t> t(n), o(n);
+    BH_HIP(c, hipMemcpy(t.data(), dev_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) out[o[i]] = t[i];
+    return BH_OK;
+}
+
 // a state array (`per` values per body) -> host, caller order
 static int download_state(bh_ctx *c, const void *dev, double *host, int per)
 {
@@ -1012,17 +1055,16 @@ int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lowe
     BH_HIP(c, hipSetDevice(c->device));
     if (n > 0) {
         const unsigned g = blocks_for(n, kBlock);
-        if (c->state64())
-            hipLaunchKernelGGL((init_bodies_kernel<double2, double>), dim3(g), dim3(kBlock), 0, c->stream,
-                               (double2 *)c->pos, (double2 *)c->vel, (double *)c->mass, n, seed, kind, lower_m,
-                               higher_m, lower_p, higher_p, lower_v, higher_v);
-        else
-            hipLaunchKernelGGL((init_bodies_kernel<float2, float>), dim3(g), dim3(kBlock), 0, c->stream,
-                               (float2 *)c->pos, (float2 *)c->vel, (float *)c->mass, n, seed, kind, lower_m,
-                               higher_m, lower_p, higher_p, lower_v, higher_v);
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((init_bodies_kernel<Real2, Real>), dim3(g), dim3(kBlock), 0, c->stream, (Real2 *)c->pos,
+                               (Real2 *)c->vel, (Real *)c->mass, n, seed, kind, lower_m, higher_m, lower_p, higher_p, lower_v,
+                               higher_v);
+        });
         BH_HIP(c, hipGetLastError());
     }
-    BH_HIP(c, hipMemsetAsync(c->force, 0, std::max<int64_t>(n, 1) * 2 * (c->tree64() ? sizeof(double) : sizeof(float)), c->stream));
+    BH_HIP(c, hipMemsetAsync(c->force, 0, force_bytes(c, n), c->stream));
     return new_bodies(c, n);
 }
 
@@ -1149,15 +1191,7 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
         return fail(c, BH_ERR_STATE, "bh_get_interaction_counts: fp32 / mixed / BH_PRECISION_F64 with BH_FLAG_WALK_STATS, after a walk");
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
-    const int64_t n = c->n;
-    if (n == 0) return BH_OK;
-    std::vector<uint32_t> t(n);
-    BH_HIP(c, hipMemcpy(t.data(), c->body_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (c->orig_identity) { std::memcpy(out, t.data(), n * sizeof(uint32_t)); return BH_OK; }
-    std::vector<uint32_t> o(n);
-    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) out[o[i]] = t[i];
-    return BH_OK;
+    return counts_to_caller_order(c, c->body_counts, out);
 }
 
 // ---- diagnostics (bh_diag.hpp): potential walk and reductions
@@ -1191,9 +1225,21 @@ static int diag_alloc(bh_ctx *c)
     return rc;
 }
 
-// the tree of the current state, no re-order, and everything a later build reads from an earlier one put back (above)
-static int enqueue_quiet_build(bh_ctx *c)
+// the walk counters of bh_stats (TreeCounters from `visits` on, which a build's keys_kernel clears): copied aside, or put back
+static int copy_walk_counters(bh_ctx *c, bool aside)
 {
+    if (!c->ctr_save) { if (int rc = dev_alloc(c, &c->ctr_save, 1)) return rc; }
+    constexpr size_t off = offsetof(TreeCounters, visits), bytes = sizeof(TreeCounters) - off;
+    char *from = (char *)(aside ? c->ctr : c->ctr_save) + off, *to = (char *)(aside ? c->ctr_save : c->ctr) + off;
+    BH_HIP(c, hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return BH_OK;
+}
+
+// the tree of the current state, no re-order, and everything a later build reads from an earlier one put back (above);
+// keep_walk_counters: also the walk counters of bh_stats, copied aside before the build and put back after it
+static int enqueue_quiet_build(bh_ctx *c, bool keep_walk_counters)
+{
+    if (keep_walk_counters) { if (int rc = copy_walk_counters(c, true)) return rc; }
     if (!c->slots_save) { if (int rc = dev_alloc(c, &c->slots_save, (size_t)4 * kBoundSlots)) return rc; }
     const int64_t builds = c->builds, samples_n = c->samples_n;
     const int reorder_every = c->reorder_every;
@@ -1206,12 +1252,14 @@ static int enqueue_quiet_build(bh_ctx *c)
     c->builds = builds; c->samples_n = samples_n;
     c->slots_valid = slots_valid; c->slots_dirty = slots_dirty;
     BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (keep_walk_counters) { if (int rc2 = copy_walk_counters(c, false)) return rc2; }
     return rc;
 }
 
 static int enqueue_potential(bh_ctx *c)
 {
-    if (int rc = enqueue_quiet_build(c)) return rc;
+    // (false: bh_stats after a potential on a BH_FLAG_WALK_STATS context reads zero walk counters -- as it always has)
+    if (int rc = enqueue_quiet_build(c, false)) return rc;
     if (c->n == 0) return BH_OK;
     const unsigned grid = blocks_for(c->n, kBlock);
     if (c->tree64()) {
@@ -1259,13 +1307,7 @@ int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
     BH_HIP(c, hipMemcpy(phi, c->phi, n * sizeof(double), hipMemcpyDeviceToHost));
     int rc = to_caller_order(c, phi, 1);
     if (rc || !counts) return rc;
-    std::vector<uint32_t> t(n);
-    BH_HIP(c, hipMemcpy(t.data(), c->phi_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (c->tree64() || c->orig_identity) { std::memcpy(counts, t.data(), n * sizeof(uint32_t)); return BH_OK; }
-    std::vector<uint32_t> o(n);
-    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) counts[o[i]] = t[i];
-    return BH_OK;
+    return counts_to_caller_order(c, c->phi_counts, counts);
 }
 
 int bh_energy(bh_ctx *c, bh_energy_t *out)
@@ -1274,14 +1316,13 @@ int bh_energy(bh_ctx *c, bh_energy_t *out)
     if (int rc = diag_check(c, "bh_energy")) return rc;
     if (!c->phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
     BH_HIP(c, hipSetDevice(c->device));
-    auto go = [&](auto real2) {
-        using Real2 = decltype(real2);
-        using Real = decltype(Real2{}.x);
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        using Real = decltype(r2.x);
         hipLaunchKernelGGL((energy_partial_kernel<Real2, Real>), dim3(kDiagParts), dim3(kBlock), 0, c->stream,
                            static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass),
                            c->phi, c->n, c->diag_part);
-    };
-    if (c->state64()) go(double2{}); else go(float2{});
+    });
     hipLaunchKernelGGL(energy_final_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->diag_part, c->diag_out);
     BH_HIP(c, hipGetLastError());
     double q[kDiagQuantities];
@@ -1339,12 +1380,12 @@ static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targe
         const int64_t k = std::min(chunk, n_targets - t0);
         if (targets) BH_HIP(c, hipMemcpyAsync(c->direct_targets, targets + t0, k * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         const int64_t *tg = targets ? c->direct_targets : nullptr;
-        if (c->state64())
-            hipLaunchKernelGGL((direct_forces_kernel<double2, double>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
-                               (const double2 *)c->pos, (const double *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
-        else
-            hipLaunchKernelGGL((direct_forces_kernel<float2, float>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
-                               (const float2 *)c->pos, (const float *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((direct_forces_kernel<Real2, Real>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
+                               (const Real2 *)c->pos, (const Real *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
+        });
         BH_HIP(c, hipGetLastError());
         BH_HIP(c, hipMemcpyAsync(out + 2 * t0, c->direct_out, k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
         BH_HIP(c, hipStreamSynchronize(c->stream));
@@ -1359,18 +1400,17 @@ static int check_walk(bh_ctx *c, double *out)
     int rc = BH_OK;
     if (!c->check_force) {
         char *f = nullptr;
-        rc = dev_alloc(c, &f, cap * 2 * (c->tree64() ? sizeof(double) : sizeof(float)));
+        rc = dev_alloc(c, &f, force_bytes(c, (int64_t)cap));
         c->check_force = f;
-        if (!rc && !c->ctr_save) rc = dev_alloc(c, &c->ctr_save, 1);
         if (!rc && c->group_cost) rc = dev_alloc(c, &c->check_cost, cap / kWave + 2);
         if (rc) return rc;
     }
     if ((c->cfg.flags & BH_FLAG_WALK_STATS) && !c->check_counts) { if ((rc = dev_alloc(c, &c->check_counts, cap))) return rc; }
     const int64_t launches = c->walk_launches;
     const bool cost_valid = c->group_cost_valid;
-    constexpr size_t wc_off = offsetof(TreeCounters, visits), wc_bytes = sizeof(TreeCounters) - wc_off;
-    BH_HIP(c, hipMemcpyAsync((char *)c->ctr_save + wc_off, (char *)c->ctr + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
-    rc = enqueue_quiet_build(c);
+    // (the check's walk counts as well: its counters are kept around build and walk together, so the quiet build keeps none)
+    if ((rc = copy_walk_counters(c, true))) return rc;
+    rc = enqueue_quiet_build(c, false);
     if (!rc) {
         auto swap_outputs = [&] {
             std::swap(c->force, c->check_force);
@@ -1383,7 +1423,7 @@ static int check_walk(bh_ctx *c, double *out)
     }
     c->walk_launches = launches;
     c->group_cost_valid = cost_valid;
-    BH_HIP(c, hipMemcpyAsync((char *)c->ctr + wc_off, (char *)c->ctr_save + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (int rc2 = copy_walk_counters(c, false)) return rc2;
     if (!rc) rc = check_overflow(c);
     return rc ? rc : forces_or_accels(c, c->check_force, out, true);
 }
@@ -1452,23 +1492,10 @@ static int enqueue_field(bh_ctx *c, int64_t k)
     hipStream_t st = c->stream;
     const unsigned grid = blocks_for(k, kBlock);
     hipLaunchKernelGGL(field_keys_kernel, dim3(grid), dim3(kBlock), 0, st, c->field_points, k, c->box, c->field_keys[0]);
-    constexpr int SI = kFieldSortItems, SB = kSortBits, passes = kFieldKeyBits / SB;
-    static_assert(kFieldKeyBits % SB == 0 && kFieldKeyBits <= kPackShift && kFieldChunk <= ((int64_t)1 << (64 - kPackShift)),
+    static_assert(kFieldKeyBits % kSortBits == 0 && kFieldKeyBits <= kPackShift && kFieldChunk <= ((int64_t)1 << (64 - kPackShift)),
                   "the keys and the indices of a launch share a word");
-    const unsigned nbl = blocks_for(k, kBlock * SI);
-    int cur = 0;
-    for (int p = 0; p < passes; ++p) {
-        const int shift = p * SB;
-        hipLaunchKernelGGL((radix_hist<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], c->field_radix, k, shift, (int)nbl);
-        hipLaunchKernelGGL(radix_rowscan, dim3(1 << SB), dim3(kBlock), 0, st, c->field_radix, c->field_rows, (int)nbl);
-        if (p + 1 < passes)
-            hipLaunchKernelGGL((radix_scatter_w<SI, SB, 1>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], nullptr,
-                               c->field_keys[cur ^ 1], c->field_order, c->field_radix, c->field_rows, k, shift, (int)nbl);
-        else
-            hipLaunchKernelGGL((radix_scatter_w<SI, SB, 2>), dim3(nbl), dim3(kBlock), 0, st, c->field_keys[cur], nullptr,
-                               c->field_keys[cur ^ 1], c->field_order, c->field_radix, c->field_rows, k, shift, (int)nbl);
-        cur ^= 1;
-    }
+    uint32_t *const order[2] = {c->field_order, c->field_order};  // (packed: written by the last pass only, wherever it ends)
+    enqueue_lsd_passes<kFieldSortItems>(st, c->field_keys, order, c->field_radix, c->field_rows, k, kFieldKeyBits, true);
     if (c->tree64()) {
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, c->gd, c->ld, c->field_order, c->field_points, k, c->cfg.theta,
@@ -1502,12 +1529,8 @@ int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel
         return BH_OK;
     }
     BH_HIP(c, hipSetDevice(c->device));
-    if (!c->ctr_save) { if (int rc = dev_alloc(c, &c->ctr_save, 1)) return rc; }
     if (int rc = field_alloc(c, std::min(n_points, kFieldChunk))) return rc;
-    constexpr size_t wc_off = offsetof(TreeCounters, visits), wc_bytes = sizeof(TreeCounters) - wc_off;
-    BH_HIP(c, hipMemcpyAsync((char *)c->ctr_save + wc_off, (char *)c->ctr + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
-    int rc = enqueue_quiet_build(c);
-    BH_HIP(c, hipMemcpyAsync((char *)c->ctr + wc_off, (char *)c->ctr_save + wc_off, wc_bytes, hipMemcpyDeviceToDevice, c->stream));
+    int rc = enqueue_quiet_build(c, true);
     if (!rc) rc = check_overflow(c);
     if (rc) return rc;
     for (int64_t t0 = 0; t0 < n_points; t0 += kFieldChunk) {
@@ -1871,12 +1894,11 @@ int bh_let_bounds(bh_ctx *c)
     BH_HIP(c, hipSetDevice(c->device));
     if (c->partial_count <= 0) {
         const unsigned nbb = kLetBoxes * kLetBoxParts;
-        if (c->state64())
-            hipLaunchKernelGGL((let_slice_bounds_kernel<double2>), dim3(nbb), dim3(kBlock), 0, c->stream,
-                               (const double2 *)c->pos, c->n, c->partial);
-        else
-            hipLaunchKernelGGL((let_slice_bounds_kernel<float2>), dim3(nbb), dim3(kBlock), 0, c->stream,
-                               (const float2 *)c->pos, c->n, c->partial);
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            hipLaunchKernelGGL((let_slice_bounds_kernel<Real2>), dim3(nbb), dim3(kBlock), 0, c->stream, (const Real2 *)c->pos, c->n,
+                               c->partial);
+        });
         c->partial_count = (int)nbb;
     }
     hipLaunchKernelGGL(let_local_bounds_kernel, dim3(kLetBoxes), dim3(kWave), 0, c->stream, c->partial,
@@ -2015,12 +2037,11 @@ int bh_orb_histogram(bh_ctx *c, const bh_orb_cuts *cuts, int32_t level, void **h
         const uint32_t *perm = weighted ? c->perm : nullptr;
         const uint32_t *cost = weighted ? c->group_cost : nullptr;
         const unsigned g = blocks_for(c->n, kBlock);
-        if (c->state64())
-            hipLaunchKernelGGL((orb_hist_kernel<double2>), dim3(g), dim3(kBlock), 0, c->stream, (const double2 *)c->pos,
-                               perm, cost, c->n, *cuts, (int)level, c->orb_hist);
-        else
-            hipLaunchKernelGGL((orb_hist_kernel<float2>), dim3(g), dim3(kBlock), 0, c->stream, (const float2 *)c->pos,
-                               perm, cost, c->n, *cuts, (int)level, c->orb_hist);
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            hipLaunchKernelGGL((orb_hist_kernel<Real2>), dim3(g), dim3(kBlock), 0, c->stream, (const Real2 *)c->pos, perm, cost,
+                               c->n, *cuts, (int)level, c->orb_hist);
+        });
         BH_HIP(c, hipGetLastError());
     }
     *hist = c->orb_hist;
@@ -2052,28 +2073,20 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
     if (n == 0) { BH_HIP(c, hipStreamSynchronize(c->stream)); return BH_OK; }
     hipStream_t st = c->stream;
     const unsigned g = blocks_for(n, kBlock);
-    if (c->state64())
-        hipLaunchKernelGGL((migrate_classify_kernel<double2>), dim3(g), dim3(kBlock), 0, st, (const double2 *)c->pos, n,
-                           *cuts, c->keys[0], c->vals[0]);
-    else
-        hipLaunchKernelGGL((migrate_classify_kernel<float2>), dim3(g), dim3(kBlock), 0, st, (const float2 *)c->pos, n,
-                           *cuts, c->keys[0], c->vals[0]);
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        hipLaunchKernelGGL((migrate_classify_kernel<Real2>), dim3(g), dim3(kBlock), 0, st, (const Real2 *)c->pos, n, *cuts,
+                           c->keys[0], c->vals[0]);
+    });
     // one stable radix pass on the destination rank (< 64 < 256): slots grouped by destination, slot order kept
-    const unsigned nbl = blocks_for(n, kSortTile);
-    hipLaunchKernelGGL((radix_hist<kSortItems, kSortBits>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->radix_counts, n,
-                       0, (int)nbl);
-    hipLaunchKernelGGL(radix_rowscan, dim3(1 << kSortBits), dim3(kBlock), 0, st, c->radix_counts, c->bsum_sort, (int)nbl);
-    hipLaunchKernelGGL((radix_scatter_w<kSortItems, kSortBits>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->vals[0],
-                       c->keys[1], c->vals[1], c->radix_counts, c->bsum_sort, n, 0, (int)nbl);
+    const int cur = enqueue_lsd_passes<kSortItems>(st, c->keys, c->vals, c->radix_counts, c->bsum_sort, n, kSortBits, false);
     const uint32_t *orig = c->orig_identity ? nullptr : c->orig;
-    if (c->state64())
-        hipLaunchKernelGGL((migrate_pack_kernel<double2, double>), dim3(g), dim3(kBlock), 0, st, c->vals[1],
-                           (const double2 *)c->pos, (const double2 *)c->vel, (const double *)c->mass, orig, c->gid, n,
-                           c->mig_send);
-    else
-        hipLaunchKernelGGL((migrate_pack_kernel<float2, float>), dim3(g), dim3(kBlock), 0, st, c->vals[1],
-                           (const float2 *)c->pos, (const float2 *)c->vel, (const float *)c->mass, orig, c->gid, n,
-                           c->mig_send);
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        using Real = decltype(r2.x);
+        hipLaunchKernelGGL((migrate_pack_kernel<Real2, Real>), dim3(g), dim3(kBlock), 0, st, c->vals[cur], (const Real2 *)c->pos,
+                           (const Real2 *)c->vel, (const Real *)c->mass, orig, c->gid, n, c->mig_send);
+    });
     BH_HIP(c, hipGetLastError());
     uint32_t totals[kMaxWorld];
     BH_HIP(c, hipMemcpyAsync(totals, c->bsum_sort, W * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -2107,22 +2120,16 @@ int bh_migrate_unpack(bh_ctx *c, int64_t n_new)
     BH_HIP(c, hipSetDevice(c->device));
     if (n_new > 0) {
         const unsigned g = blocks_for(n_new, kBlock);
-        if (c->state64())
-            hipLaunchKernelGGL((migrate_unpack_kernel<double2, double>), dim3(g), dim3(kBlock), 0, c->stream, c->mig_recv,
-                               n_new, (double2 *)c->pos, (double2 *)c->vel, (double *)c->mass, (float2 *)c->force, c->gid);
-        else
-            hipLaunchKernelGGL((migrate_unpack_kernel<float2, float>), dim3(g), dim3(kBlock), 0, c->stream, c->mig_recv,
-                               n_new, (float2 *)c->pos, (float2 *)c->vel, (float *)c->mass, (float2 *)c->force, c->gid);
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((migrate_unpack_kernel<Real2, Real>), dim3(g), dim3(kBlock), 0, c->stream, c->mig_recv, n_new,
+                               (Real2 *)c->pos, (Real2 *)c->vel, (Real *)c->mass, (float2 *)c->force, c->gid);
+        });
         BH_HIP(c, hipGetLastError());
     }
     c->n = n_new;
-    c->partial_count = 0; c->slots_valid = false;
-    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
-    c->phi_current = false;
-    c->tree_valid = false;
-    c->orig_identity = true;                                // arrival order is the caller order from here on
-    c->builds = 0;
-    c->group_cost_valid = false;
+    forget_body_set(c);                                       // (arrival order is the caller order from here on)
     return BH_OK;
 }
 

@@ -1,6 +1,7 @@
 """Reference field at arbitrary points for the tests of bh_field_at: the numpy walk of tests/potential_ref.py over the
 oracle's node array (reference order, oracle.bh_oracle.build_tree), extended from the potential to everything the
-checks need.  Helper of tests/test_field_cpu.py and tests/test_gpu_field.py -- not a test file.
+checks need.  Helper of tests/test_field_cpu.py, tests/test_gpu_field.py and (the deep chain) tests/test_gpu_energy.py -- not a
+test file.
 
 A point is nobody, so no leaf is skipped.  Per node (project.cu:617-658 with m_i = 1):
 
@@ -145,3 +146,54 @@ def class_points(pos, k, seed):
     u = rng.uniform(lo - 0.2 * ext, hi + 0.2 * ext, (a, 2))
     j = pos[rng.integers(0, len(pos), k - a)] + rng.normal(0.0, 0.004, (k - a, 2))
     return np.concatenate([u, j]).astype(np.float32).astype(np.float64)
+
+
+# ---- the deep chain: an input whose walks need the second tier of the kernels' lane stack -----------------------------
+DEEP_THETA, DEEP_DEPTH = 0.2, 32
+DEEP_POINT = np.array([[-1e-10, -1e-10]])
+
+
+def deep_chain(levels=28):
+    """172 bodies of mass 0.3.  Anchors at (-1, -1) and (1, 1) pad the root box to [-1.2, 1.2]^2, centre at the origin.  For
+    l = 1 .. levels the cell [-s, 0]^2, s = 1.2 * 2^-l, has two bodies in each of its three children other than the
+    upper-right one, at (0.3, 0.3) and (0.7, 0.6) of the child's extent, and the last upper-right child holds two more: a
+    walker next to the origin opens the upper-right child of every level last and leaves its three siblings pending."""
+    at = np.array([[0.3, 0.3], [0.7, 0.6]])
+    pos = [np.array([[-1.0, -1.0], [1.0, 1.0]])]
+    for l in range(1, levels + 1):
+        h = 1.2 * 2.0 ** -l / 2.0                                  # extent of the children of [-s, 0]^2
+        for cx, cy in ((-2.0 * h, -2.0 * h), (-h, -2.0 * h), (-2.0 * h, -h)):
+            pos.append(np.array([cx, cy]) + at * h)
+    pos.append(np.array([-h, -h]) + at * h)
+    pos = np.concatenate(pos)
+    return pos, np.full(len(pos), 0.3)
+
+
+def pending_quads(nodes, point, theta, self_index=-1):
+    """(most sibling quads pending at once, terms taken) of one walker's depth-first walk as the side-walk kernels run it
+    (csrc/bh_treewalk.hpp): the root alone, then quads popped last first, their siblings in index order, every opened
+    cell's quad pushed.  A wavefront's stack is at least its deepest lane's: same sibling order, a superset pushed."""
+    child = nodes["child"].astype(np.int64)
+    size = np.maximum(nodes["xmax"] - nodes["xmin"], nodes["ymax"] - nodes["ymin"])
+    stack, deepest, terms = [], 0, 0
+
+    def visit(nd):
+        nonlocal deepest, terms
+        if not nodes["mass"][nd] > 1e-15:
+            return
+        dx, dy = nodes["comx"][nd] - point[0], nodes["comy"][nd] - point[1]
+        d = np.sqrt(dx * dx + dy * dy) + 1e-15
+        if (child[nd] == -1).all():
+            terms += int(nodes["particle"][nd]) != self_index
+        elif size[nd] / d < theta:
+            terms += 1
+        else:
+            stack.append(child[nd])
+            deepest = max(deepest, len(stack))
+
+    visit(0)
+    while stack:
+        for nd in stack.pop():
+            if nd >= 0:
+                visit(nd)
+    return deepest, terms

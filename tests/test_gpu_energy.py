@@ -19,9 +19,10 @@ pytestmark = pytest.mark.gpu
 from oracle import bh_oracle as O  # noqa: E402
 import gpu_nbody_simulation_amd as G  # noqa: E402
 from gpu_nbody_simulation_amd import _lib, initial_conditions as IC  # noqa: E402
-from gpu_nbody_simulation_amd.engine import FLAG_WALK_STATS  # noqa: E402
+from gpu_nbody_simulation_amd.engine import FLAG_WALK_PORTABLE, FLAG_WALK_STATS  # noqa: E402
 from gpu_nbody_simulation_amd.project import runSimulationGpu  # noqa: E402
 from potential_ref import potential_walk  # noqa: E402
+import field_ref as FR  # noqa: E402
 
 P = G.Precision
 F64_TOL = 1e-12
@@ -90,6 +91,25 @@ def test_portable_exact_walk_takes_the_same_terms(init1024):
     ref, rcnt = potential_walk(nodes, p)
     assert np.array_equal(cnt.astype(np.int64), rcnt)
     assert (np.abs(phi - ref) <= F64_TOL * np.abs(ref)).all()
+
+
+def test_fp64_potential_of_the_deep_chain_uses_the_second_stack_tier():
+    """field_ref.deep_chain at theta 0.2: the last body's walk holds more than 64 quads pending (tests/test_field_cpu.py), so
+    its wavefront pushes past entry 64 of the lane stack.  All 172 bodies, checked as above.  (No body meets a cell whose
+    size / d is closer to theta than 9.7e-3 relative -- field_ref.field_walk(...).margin --, so BH_PRECISION_F64's own
+    thresholds decide as the oracle does.)"""
+    p, m = FR.deep_chain()
+    nodes = O.build_tree(p, m, FR.DEEP_DEPTH)
+    d = O.compute_forces_diag(nodes, p, m, theta=FR.DEEP_THETA, compat_self_skip=False)
+    ref, rcnt = potential_walk(nodes, p, theta=FR.DEEP_THETA, compat=False)
+    assert np.array_equal(rcnt, d.counts.astype(np.int64))
+    for prec, flags in [(P.F64_EXACT, 0), (P.F64_EXACT, FLAG_WALK_PORTABLE), (P.F64, 0)]:
+        with engine(len(m), precision=prec, theta=FR.DEEP_THETA, reference_compat=False, max_depth=FR.DEEP_DEPTH, flags=flags) as e:
+            e.upload(p, np.zeros_like(p), m)
+            phi, cnt = e.potential(with_counts=True)
+        assert np.array_equal(cnt, d.counts), (prec, flags)
+        print(prec.name, flags, "max rel err %.3e" % np.max(np.abs(phi - ref) / np.abs(ref)))
+        assert (np.abs(phi - ref) <= F64_TOL * np.abs(ref)).all(), (prec, flags, np.max(np.abs(phi - ref) / np.abs(ref)))
 
 
 # ---- 2. fp32 precisions --------------------------------------------------------------------------------------------

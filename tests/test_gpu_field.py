@@ -86,6 +86,34 @@ def test_fp64_field_against_the_oracle(init1024, gold, name, theta, max_depth, c
         assert np.isfinite(acc).all() and np.isfinite(phi).all()
 
 
+def test_fp64_field_of_the_deep_chain_uses_the_second_stack_tier():
+    """field_ref.deep_chain at theta 0.2: the point next to the origin holds 85 quads pending (tests/test_field_cpu.py), so
+    its wavefront pushes past entry 64 of the lane stack.  That point and the eight corner and edge points of the bounding
+    box, checked as above; the two corners that are the anchor bodies' own places get the non-finite acceleration the
+    oracle gets there (inf * 0), so the acceleration bound is held on the other seven points and the potential bound on all."""
+    p, m = FR.deep_chain()
+    pts = np.concatenate([FR.DEEP_POINT, FR.points_around(p, 24, 0)[16:24]])     # (of 24 points, 16..23 are the corners and edges)
+    nodes = O.build_tree(p, m, FR.DEEP_DEPTH)
+    d = FR.oracle_at_points(nodes, p, m, pts, theta=FR.DEEP_THETA, compat=False)
+    r = FR.field_walk(nodes, pts, theta=FR.DEEP_THETA)
+    assert np.array_equal(r.counts, d.counts.astype(np.int64)) and d.counts[0] == 172
+    assert r.margin.min() >= MARGIN                               # (no decision BH_PRECISION_F64 could turn: 1.5e-2 at the least)
+    fin = np.isfinite(d.forces).all(axis=1)
+    assert fin.sum() == 7 and fin[0]
+    ba, bp = FR.accel_bound(d.counts, r.abs_sum), FR.accel_bound(d.counts, r.pot_sum)
+    for label, prec, flags in [("exact", P.F64_EXACT, 0), ("portable", P.F64_EXACT, FLAG_WALK_PORTABLE), ("f64", P.F64, 0)]:
+        with engine(len(m), precision=prec, theta=FR.DEEP_THETA, max_depth=FR.DEEP_DEPTH, reference_compat=False, flags=flags) as e:
+            e.upload(p, np.zeros_like(p), m)
+            acc, phi, cnt = e.field(pts, with_counts=True)
+        assert np.array_equal(cnt, d.counts), (label, cnt, d.counts)
+        ea = np.linalg.norm(acc - d.forces, axis=1)
+        ep = np.abs(phi - r.phi)
+        print(label, "max err / bound: accel %.3f phi %.3f" % ((ea / ba)[fin].max(), (ep / bp).max()))
+        assert (ea[fin] <= ba[fin]).all(), (label, float((ea / ba)[fin].max()))
+        assert (ep <= bp).all(), (label, float((ep / bp).max()))
+        assert np.array_equal(np.isfinite(acc).all(axis=1), fin) and np.isfinite(phi).all()
+
+
 # ---- 2. F32 and MIXED by class ---------------------------------------------------------------------------------------
 def class_terms(d, k):
     """(err model, flip budget) per point as parity_classes.classify forms them, unit masses."""

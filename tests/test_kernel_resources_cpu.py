@@ -15,44 +15,24 @@ code objects; this file checks them for EVERY instantiat
     the GPU (<= 3,072 groups x 4 waves), where 6 waves per SIMD hold the whole launch: their ceiling is the
     architectural one.
   * <= 64 VGPRs (8 waves per SIMD by the vector file)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gpu-nbody-simulation_amd", "csrc", "bh_walk_fast.hip")
+import kernel_meta as KM
+
 KERNEL = re.compile(r"_ZN2bh16walk_fast_kernelILb([01])ELb([01])ELi(\d+)ELb([01])EEEvNS_12WalkFastArgsE")   # <LDS_STACK, STATS, SPLIT, ASM>
 ONE_WAVE_ASM = "_ZN2bh16walk_fast_kernelILb0ELb0ELi1ELb1EEEvNS_12WalkFastArgsE"
 
 
 @pytest.fixture(scope="module")
-def compiled(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("walk") / "walk.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-Wall",
-                        "-Wno-unused-function", "-o", str(out), SRC], cwd=os.path.dirname(SRC), capture_output=True,
-                       text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out.read_text(), r.stderr
+def compiled():
+    return KM.assembly("bh_walk_fast.hip", diagnostics=True)
 
 
 def _kernels(text):
     """name -> metadata dict of every walk_fast_kernel instantiation in the code object's notes."""
-    res = {}
-    for m in re.finditer(r"\.name:\s+(_ZN2bh16walk_fast_kernel\S+)\n", text):
-        meta = text[m.start():m.start() + 3000]
-        val = lambda key: int(re.search(key + r":\s+(\d+)", meta).group(1))
-        res[m.group(1)] = {
-            "sgpr": val(r"\.sgpr_count"), "vgpr": val(r"\.vgpr_count"), "sgpr_spill": val(r"\.sgpr_spill_count"),
-            "vgpr_spill": val(r"\.vgpr_spill_count"), "scratch": val(r"\.private_segment_fixed_size"),
-            "dynamic_stack": re.search(r"\.uses_dynamic_stack:\s+(\w+)", meta).group(1),
-        }
-    return res
+    return KM.kernels(text, r"_ZN2bh16walk_fast_kernel\S+")
 
 
 def test_every_assembly_walk_kernel_has_no_scratch_no_spills_and_fits_its_sgpr_ceiling(compiled):
@@ -89,16 +69,8 @@ def test_the_one_wave_kernel_really_is_the_hand_written_loop(compiled):
 
 
 @pytest.fixture(scope="module")
-def engine_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(os.path.dirname(SRC), "bh_engine.hip")
-    out = tmp_path_factory.mktemp("engine") / "engine.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        "-w", "-o", str(out), src], cwd=os.path.dirname(src), capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out.read_text()
+def engine_asm():
+    return KM.assembly("bh_engine.hip")[0]
 
 
 F64_KERNEL = re.compile(r"_ZN2bh15walk_f64_kernelILb([01])ELb([01])ELb([01])ELb([01])EEEv")    # <COMPAT, STATS, DEEP, ASM>
@@ -111,13 +83,7 @@ def test_every_fp64_assembly_walk_kernel_has_no_scratch_no_spills_and_fits_its_c
     stack tiers): no scratch, no spills, <= 80 SGPRs and <= 64 VGPRs -- 8 resident waves per SIMD: with one quad in flight per
     wave this walk answers to residency (measured at N = 1M, profiles/r04_f64/walk_ab.txt: 0.704 ms at 7 waves, 0.800 at 5,
     0.834 at 4, 1.088 at 3) --; and the loop in the code object is the hand-written one."""
-    ks = {}
-    for m in re.finditer(r"\.name:\s+(_ZN2bh15walk_f64_kernel\S+)\n", engine_asm):
-        meta = engine_asm[m.start():m.start() + 3000]
-        val = lambda key: int(re.search(key + r":\s+(\d+)", meta).group(1))
-        ks[m.group(1)] = {"sgpr": val(r"\.sgpr_count"), "vgpr": val(r"\.vgpr_count"), "sgpr_spill": val(r"\.sgpr_spill_count"),
-                          "vgpr_spill": val(r"\.vgpr_spill_count"), "scratch": val(r"\.private_segment_fixed_size"),
-                          "dynamic_stack": re.search(r"\.uses_dynamic_stack:\s+(\w+)", meta).group(1)}
+    ks = KM.kernels(engine_asm, r"_ZN2bh15walk_f64_kernel\S+")
     asm = {k: v for k, v in ks.items() if F64_KERNEL.match(k).group(4) == "1"}
     assert sorted((F64_KERNEL.match(k).group(1), F64_KERNEL.match(k).group(3)) for k in asm) == [("0", "0"), ("0", "1"), ("1", "0"), ("1", "1")]
     for name, r in asm.items():
@@ -145,13 +111,7 @@ def test_every_bit_exact_assembly_walk_kernel_has_no_scratch_no_spills_and_fits_
     launcher reaches (reference_compat on / off): no scratch, no spills, <= 80 SGPRs and <= 64 VGPRs (8 resident waves per
     SIMD); the loop in the code object is the hand-written one -- one 16-dword request per pair of children, the threshold
     compare narrowing EXEC, the compiler's division expansion only out of line."""
-    ks = {}
-    for m in re.finditer(r"\.name:\s+(_ZN2bh17walk_exact_kernel\S+)\n", engine_asm):
-        meta = engine_asm[m.start():m.start() + 3000]
-        val = lambda key: int(re.search(key + r":\s+(\d+)", meta).group(1))
-        ks[m.group(1)] = {"sgpr": val(r"\.sgpr_count"), "vgpr": val(r"\.vgpr_count"), "sgpr_spill": val(r"\.sgpr_spill_count"),
-                          "vgpr_spill": val(r"\.vgpr_spill_count"), "scratch": val(r"\.private_segment_fixed_size"),
-                          "dynamic_stack": re.search(r"\.uses_dynamic_stack:\s+(\w+)", meta).group(1)}
+    ks = KM.kernels(engine_asm, r"_ZN2bh17walk_exact_kernel\S+")
     asm = {k: v for k, v in ks.items() if EXACT_KERNEL.match(k).group(4) == "1"}
     assert sorted(EXACT_KERNEL.match(k).group(1) for k in asm) == ["0", "1"]
     for name, r in asm.items():
@@ -171,27 +131,13 @@ def test_every_bit_exact_assembly_walk_kernel_has_no_scratch_no_spills_and_fits_
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
 
 
-def test_no_build_or_fp64_walk_kernel_uses_scratch(tmp_path):
+def test_no_build_or_fp64_walk_kernel_uses_scratch(engine_asm):
     """Every kernel of the engine unit (tree build, sorts, LET, exact and fp64 walks) keeps its working set in registers
     and LDS: private_segment_fixed_size == 0 and no vector-register spills.  (Round 3: bucket_sort_kernel, whose 1,024-thread workgroups
     cap it at 128 VGPRs, spilled 52 bytes per lane after the run fix-up of its short sort was added with two more
     arrays per key; nothing failed -- the kernel was just slower than it had to be.)"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(os.path.dirname(SRC), "bh_engine.hip")
-    out = tmp_path / "engine.s"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        "-w", "-o", str(out), src], cwd=os.path.dirname(src), capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = out.read_text()
-    seen = 0
-    for m in re.finditer(r"\.name:\s+(\S+)\n", text):
-        meta = text[m.start():m.start() + 3000]
-        if ".private_segment_fixed_size" not in meta:
-            continue
-        val = lambda key: int(re.search(key + r":\s+(\d+)", meta).group(1))
-        seen += 1
-        assert val(r"\.private_segment_fixed_size") == 0, m.group(1)
-        assert val(r"\.vgpr_spill_count") == 0, m.group(1)      # (SGPRs spilled to VGPR lanes cost a v_writelane, not memory)
-    assert seen >= 40                                              # (all instantiations were looked at)
+    ks = KM.kernels(engine_asm)
+    for name, r in ks.items():
+        assert r["scratch"] == 0, name
+        assert r["vgpr_spill"] == 0, name                        # (SGPRs spilled to VGPR lanes cost a v_writelane, not memory)
+    assert len(ks) >= 40                                           # (all instantiations were looked at)
