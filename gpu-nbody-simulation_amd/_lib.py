@@ -130,6 +130,11 @@ SIGNATURES = {
     "bh_let_walk_local": (C.c_int, [_ctx]),
     "bh_let_walk_remote": (C.c_int, [_ctx, C.c_int32]),
     "bh_let_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "bh_let_bounds_quiet": (C.c_int, [_ctx]),
+    "bh_let_build_quiet": (C.c_int, [_ctx]),
+    "bh_let_potential": (C.c_int, [_ctx]),
+    "bh_let_get_potential": (C.c_int, [_ctx, _dp, C.POINTER(C.c_uint32)]),
+    "bh_let_energy": (C.c_int, [_ctx, _dp]),
     "bh_set_ids": (C.c_int, [_ctx, C.POINTER(C.c_int64)]),
     "bh_get_ids": (C.c_int, [_ctx, C.POINTER(C.c_int64)]),
     "bh_orb_histogram": (C.c_int, [_ctx, C.POINTER(bh_orb_cuts), C.c_int32, C.POINTER(_vp), C.POINTER(C.c_int64)]),

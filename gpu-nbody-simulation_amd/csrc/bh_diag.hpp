@@ -1,5 +1,5 @@
 // bh_diag.hpp -- on-device diagnostics: the potential walk and the energy / momentum reductions (bh_compute_potential,
-// bh_energy).  The reference has no potential or energy at all: its only outputs are positions, forces and the quadtree
+// bh_energy; in the distributed step bh_let_potential, bh_let_energy).  The reference has no potential or energy at all: its only outputs are positions, forces and the quadtree
 // files.  Included by bh_engine.hip, so it is compiled with -ffp-contract=off: every fused multiply-add below is written out.
 //
 // Potential walk.  phi_i = -G sum_j M_j / d_ij over EXACTLY the terms the precision's force walk takes for body i: the
@@ -83,6 +83,42 @@ __global__ __launch_bounds__(kBlock) void potential_f32_kernel(const QuadF *__re
         sum += (double)(m * ri);
         ++cnt;
     });
+    if (valid) {
+        const uint32_t slot = perm[s];
+        phi[slot] = -G * sum;
+        if (counts) counts[slot] = cnt;
+    }
+}
+
+// ---- forest of the distributed step (LET mode, bh_let.hpp): the own tree, then every peer's received tree ------------
+// The trees in the order of the one-wave forest force walk (bh_walk_fast.hip): the own tree from quad 0 -- own buckets body by
+// body, a body at the walker's place gives nothing -- then the received locally-essential tree of every peer in rank order,
+// the own rank skipped, from its root quad forest_base + t * let_cap (remote buckets arrive as aggregates, links past a
+// truncated block are cut by the packer: the walk never leaves the forest array).  Same term and accumulation as
+// potential_f32_kernel; one traversal per tree from an empty stack, so a lane's sum is its own nodes in that fixed order.
+// Writes phi and counts at the body's device slot perm[s], nothing else.
+__global__ __launch_bounds__(kBlock) void forest_potential_f32_kernel(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
+                                                                      const float2 *__restrict__ spos, const float *__restrict__ smass,
+                                                                      const uint32_t *__restrict__ perm, int64_t n, double G,
+                                                                      const TreeCounters *ctr, int32_t n_trees, int32_t self_rank,
+                                                                      int64_t forest_base, int64_t let_cap, double *__restrict__ phi,
+                                                                      uint32_t *__restrict__ counts)
+{
+    if (ctr->overflow) return;
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = s < n;
+    const float2 p = valid ? spos[s] : float2{0.f, 0.f};
+    double sum = 0.0;
+    uint32_t cnt = 0;
+    for (int32_t t = -1; t < n_trees; ++t) {                       // (wave-uniform: kernel arguments only)
+        if (t == self_rank) continue;
+        const int32_t root = (t < 0) ? 0 : (int32_t)(forest_base + (int64_t)t * let_cap);
+        walk_quads_f32_from(quads, aux, spos, smass, root, p, valid, [&](float m, float, float, float d2) {
+            const float ri = __builtin_amdgcn_rsqf(d2);
+            sum += (double)(m * ri);
+            ++cnt;
+        });
+    }
     if (valid) {
         const uint32_t slot = perm[s];
         phi[slot] = -G * sum;

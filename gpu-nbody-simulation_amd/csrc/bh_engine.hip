@@ -144,6 +144,10 @@ struct bh_ctx {
     uint32_t *phi_counts = nullptr;
     double *diag_part = nullptr, *diag_out = nullptr, *slots_save = nullptr;
     bool phi_current = false;           // phi holds the potential of the current state
+    // LET mode: the quiet builds of the distributed diagnostics (bh_let_bounds_quiet, bh_let_build_quiet)
+    bool let_moved = false;             // an integrating walk has moved the bodies since the last bh_let_build
+    uint32_t *perm_save = nullptr;      // allocated on first use: the permutation of the last force walk's build
+    const uint32_t *cost_perm = nullptr;   // non-null: group_cost is indexed through this, not through perm (a quiet build since)
     // direct sums and the force check (bh_direct.hpp), allocated on first use: caller index -> slot, one launch's targets and
     // results (capacity of them), and the check walk's own force / count / group-cost outputs and a copy of the walk counters
     uint32_t *slot_of = nullptr;
@@ -531,6 +535,7 @@ static int enqueue_build_items(bh_ctx *c)
 
 int enqueue_build(bh_ctx *c)
 {
+    c->cost_perm = nullptr;                  // (the quiet LET build puts its copy back afterwards)
     // keys per thread in the sort / scan kernels: launches of few bodies take smaller tiles (more
     // workgroups, fewer sequential rounds in each); BH_BUILD_ITEMS = 2, 4 or 8 overrides
     int items = c->build_items;
@@ -756,7 +761,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     if (full && c->let_mode) w.partial = c->partial;
     const bool want_slots = full && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
     if (want_slots) { clean_slots(c); w.slots = c->bslots; }
-    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; }    // (the positions change)
+    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; c->let_moved = true; }    // (the positions change)
 
     const WalkChoice k = choose_walk(c, w);
     if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
@@ -774,7 +779,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     }
     if (rc) return rc;
     BH_HIP(c, hipGetLastError());
-    if (!c->tree64() && w.lo == 0 && w.hi == c->n) c->group_cost_valid = true;
+    if (!c->tree64() && w.lo == 0 && w.hi == c->n) { c->group_cost_valid = true; c->cost_perm = nullptr; }
     return BH_OK;
 }
 
@@ -799,6 +804,7 @@ void forget_body_set(bh_ctx *c)
     c->orig_identity = true;
     c->builds = 0;
     c->group_cost_valid = false;
+    c->cost_perm = nullptr;
 }
 
 // bh_upload / bh_initialize: the state arrays hold n new bodies in caller order
@@ -1208,7 +1214,8 @@ static int diag_check(bh_ctx *c, const char *what)
 {
     if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(what) + " before bh_upload");
     if (c->let_mode || c->world > 1)
-        return fail(c, BH_ERR_STATE, std::string(what) + ": the distributed schemes (LET mode, world > 1) have no potential / energy");
+        return fail(c, BH_ERR_STATE, std::string(what) + ": single GPU only -- in LET mode bh_let_potential / bh_let_energy give the potential "
+                                     "and the energy sums; the replicated scheme (world > 1) and the other diagnostics have no distributed form");
     return BH_OK;
 }
 
@@ -1310,12 +1317,9 @@ int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
     return counts_to_caller_order(c, c->phi_counts, counts);
 }
 
-int bh_energy(bh_ctx *c, bh_energy_t *out)
+// the eight sums of bh_diag.hpp over the state and phi, in the two fixed-shape passes: q on the host when this returns
+static int energy_sums(bh_ctx *c, double (&q)[kDiagQuantities])
 {
-    if (!c || !out) return fail(c, BH_ERR_ARG, "bh_energy: null argument");
-    if (int rc = diag_check(c, "bh_energy")) return rc;
-    if (!c->phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
-    BH_HIP(c, hipSetDevice(c->device));
     with_state(c, [&](auto r2) {
         using Real2 = decltype(r2);
         using Real = decltype(r2.x);
@@ -1325,9 +1329,19 @@ int bh_energy(bh_ctx *c, bh_energy_t *out)
     });
     hipLaunchKernelGGL(energy_final_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->diag_part, c->diag_out);
     BH_HIP(c, hipGetLastError());
-    double q[kDiagQuantities];
     BH_HIP(c, hipMemcpyAsync(q, c->diag_out, sizeof(q), hipMemcpyDeviceToHost, c->stream));
     BH_HIP(c, hipStreamSynchronize(c->stream));
+    return BH_OK;
+}
+
+int bh_energy(bh_ctx *c, bh_energy_t *out)
+{
+    if (!c || !out) return fail(c, BH_ERR_ARG, "bh_energy: null argument");
+    if (int rc = diag_check(c, "bh_energy")) return rc;
+    if (!c->phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
+    BH_HIP(c, hipSetDevice(c->device));
+    double q[kDiagQuantities];
+    if (int rc = energy_sums(c, q)) return rc;
     bh_energy_t e{};
     e.mass = q[0];
     e.com[0] = q[0] != 0.0 ? q[1] / q[0] : 0.0;
@@ -1887,11 +1901,13 @@ int bh_let_configure(bh_ctx *c, int32_t rank, int32_t world, int64_t let_cap, in
     return BH_OK;
 }
 
-int bh_let_bounds(bh_ctx *c)
+// quiet: the walk's records stay for the next bh_let_bounds (a step after the diagnostic describes itself by the same boxes)
+static int let_bounds(bh_ctx *c, bool quiet, const char *who)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_bounds: call bh_let_configure first");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_let_bounds before bh_upload");
+    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, std::string(who) + ": call bh_let_configure first");
+    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
     BH_HIP(c, hipSetDevice(c->device));
+    const int from_walk = c->partial_count;
     if (c->partial_count <= 0) {
         const unsigned nbb = kLetBoxes * kLetBoxParts;
         with_state(c, [&](auto r2) {
@@ -1903,10 +1919,14 @@ int bh_let_bounds(bh_ctx *c)
     }
     hipLaunchKernelGGL(let_local_bounds_kernel, dim3(kLetBoxes), dim3(kWave), 0, c->stream, c->partial,
                        c->partial_count, c->lbounds);
-    c->partial_count = 0; c->slots_valid = false;
+    c->partial_count = (quiet && from_walk > 0) ? from_walk : 0;
+    c->slots_valid = false;
     BH_HIP(c, hipGetLastError());
     return BH_OK;
 }
+
+int bh_let_bounds(bh_ctx *c) { return let_bounds(c, false, "bh_let_bounds"); }
+int bh_let_bounds_quiet(bh_ctx *c) { return let_bounds(c, true, "bh_let_bounds_quiet"); }
 
 int bh_let_pointers(bh_ctx *c, void **lbounds, void **all_bounds, void **send, void **recv, int64_t *block_bytes,
                     int32_t *boxes_per_rank)
@@ -1921,29 +1941,48 @@ int bh_let_pointers(bh_ctx *c, void **lbounds, void **all_bounds, void **send, v
     return BH_OK;
 }
 
-int bh_let_build(bh_ctx *c)
+// quiet (the distributed diagnostics): the local tree by enqueue_quiet_build -- no re-order, build count and samples_n put
+// back --, the walk counters of bh_stats copied aside and back (let_box_kernel clears them), the bh_let_build timings left
+// alone, and the permutation the last force walk's group costs are indexed through kept for bh_orb_histogram.  The LET
+// size counters take this build's sizes like any other's.
+static int let_build(bh_ctx *c, bool quiet, const char *who)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_build: call bh_let_configure first");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_let_build before bh_upload");
+    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, std::string(who) + ": call bh_let_configure first");
+    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
     BH_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    (void)hipEventRecord(c->ev_let[0], st);
+    const uint32_t *cost_perm = c->cost_perm;
+    if (quiet) {
+        if (int rc = copy_walk_counters(c, true)) return rc;
+        if (c->group_cost_valid && c->tree_valid && !cost_perm && c->n > 0) {
+            if (!c->perm_save) { if (int rc = dev_alloc(c, &c->perm_save, (size_t)std::max<int64_t>(c->cfg.capacity, 1))) return rc; }
+            BH_HIP(c, hipMemcpyAsync(c->perm_save, c->perm, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            cost_perm = c->perm_save;
+        }
+    } else {
+        (void)hipEventRecord(c->ev_let[0], st);
+    }
     hipLaunchKernelGGL(let_box_kernel, dim3(1), dim3(64), 0, st, c->all_bounds, c->world * kLetBoxes, c->box, c->ctr,
                        c->let_ctr, c->Dm);
-    int rc = enqueue_build(c);
+    int rc = quiet ? enqueue_quiet_build(c, false) : enqueue_build(c);
     if (rc) return rc;
-    (void)hipEventRecord(c->ev_let[1], st);
+    if (quiet) c->cost_perm = cost_perm;
+    else (void)hipEventRecord(c->ev_let[1], st);
     const int64_t nq = c->quads_local;
     hipLaunchKernelGGL(let_mark_alloc_kernel, dim3(blocks_for(4 * nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->all_bounds,
                        c->world, c->rank, c->ctr, c->internal_cap, c->needmask, c->let_tsum, c->let_outidx, nq);
     hipLaunchKernelGGL(let_pack_kernel, dim3(blocks_for(nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->needmask,
                        c->let_outidx, nq, c->world, c->rank, c->ctr, c->internal_cap, c->let_send,
                        (uint32_t)c->let_cap, c->forest_base + (int64_t)c->rank * c->let_cap, c->let_tsum, c->let_ctr);
-    (void)hipEventRecord(c->ev_let[2], st);
-    c->let_timed = true;
+    if (quiet) { if (int rc2 = copy_walk_counters(c, false)) return rc2; }
+    else { (void)hipEventRecord(c->ev_let[2], st); c->let_timed = true; }
+    c->let_moved = false;
     BH_HIP(c, hipGetLastError());
     return BH_OK;
 }
+
+int bh_let_build(bh_ctx *c) { return let_build(c, false, "bh_let_build"); }
+int bh_let_build_quiet(bh_ctx *c) { return let_build(c, true, "bh_let_build_quiet"); }
 
 int bh_let_walk(bh_ctx *c)
 {
@@ -1984,6 +2023,64 @@ int bh_let_forces(bh_ctx *c)
     if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_forces before bh_let_build");
     BH_HIP(c, hipSetDevice(c->device));
     return enqueue_walk(c, false, false);
+}
+
+// ---- diagnostics of the distributed step (bh_diag.hpp: forest_potential_f32_kernel and the reductions) ----------------
+// The forest the last bh_let_build left and the caller completed with the peers' blocks, walked by the potential kernel: it
+// writes phi and its own counts, so force, body_counts, group_cost, partial, the walk counters and the timings stay the last
+// force walk's.
+static int let_diag_check(bh_ctx *c, const char *what)
+{
+    if (!c->let_mode)
+        return fail(c, BH_ERR_STATE, std::string(what) + ": LET mode only (bh_let_configure; BH_PRECISION_F32 / MIXED) -- "
+                                     "a single context has bh_compute_potential / bh_energy");
+    return BH_OK;
+}
+
+int bh_let_potential(bh_ctx *c)
+{
+    if (!c) return BH_ERR_ARG;
+    if (int rc = let_diag_check(c, "bh_let_potential")) return rc;
+    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_potential before bh_let_build");
+    if (c->let_moved) return fail(c, BH_ERR_STATE, "bh_let_potential: the bodies have moved since the last bh_let_build");
+    BH_HIP(c, hipSetDevice(c->device));
+    int rc = diag_alloc(c);
+    if (!rc && c->n > 0) {
+        hipLaunchKernelGGL(forest_potential_f32_kernel, dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream, c->qf, c->aux,
+                           c->spos, c->smass, c->perm, c->n, c->cfg.G, c->ctr, (int32_t)c->world, (int32_t)c->rank, c->forest_base,
+                           c->let_cap, c->phi, c->phi_counts);
+        BH_HIP(c, hipGetLastError());
+    }
+    if (!rc) rc = check_overflow(c);
+    c->phi_current = rc == BH_OK;
+    return rc;
+}
+
+int bh_let_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
+{
+    if (!c || !phi) return fail(c, BH_ERR_ARG, "bh_let_get_potential: null array");
+    if (int rc = let_diag_check(c, "bh_let_get_potential")) return rc;
+    if (!c->phi_current) return fail(c, BH_ERR_STATE, "bh_let_get_potential: no potential of the current state (bh_let_potential)");
+    BH_HIP(c, hipSetDevice(c->device));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    const int64_t n = c->n;
+    if (n == 0) return BH_OK;
+    BH_HIP(c, hipMemcpy(phi, c->phi, n * sizeof(double), hipMemcpyDeviceToHost));
+    int rc = to_caller_order(c, phi, 1);
+    if (rc || !counts) return rc;
+    return counts_to_caller_order(c, c->phi_counts, counts);
+}
+
+int bh_let_energy(bh_ctx *c, double *sums)
+{
+    if (!c || !sums) return fail(c, BH_ERR_ARG, "bh_let_energy: null argument");
+    if (int rc = let_diag_check(c, "bh_let_energy")) return rc;
+    if (!c->phi_current) { if (int rc = bh_let_potential(c)) return rc; }
+    BH_HIP(c, hipSetDevice(c->device));
+    double q[kDiagQuantities];
+    if (int rc = energy_sums(c, q)) return rc;
+    for (int k = 0; k < kDiagQuantities; ++k) sums[k] = q[k];
+    return BH_OK;
 }
 
 // ---- device-side migration and re-balancing (bh_migrate.hpp) ----------------------------------------
@@ -2034,7 +2131,7 @@ int bh_orb_histogram(bh_ctx *c, const bh_orb_cuts *cuts, int32_t level, void **h
         // weights: the cost of the body's 64-body group in the last full walk; they are indexed by sorted
         // position, so the bodies are visited through the last build's permutation
         const bool weighted = c->group_cost_valid && c->tree_valid;
-        const uint32_t *perm = weighted ? c->perm : nullptr;
+        const uint32_t *perm = weighted ? (c->cost_perm ? c->cost_perm : c->perm) : nullptr;   // (the last force walk's order)
         const uint32_t *cost = weighted ? c->group_cost : nullptr;
         const unsigned g = blocks_for(c->n, kBlock);
         with_state(c, [&](auto r2) {

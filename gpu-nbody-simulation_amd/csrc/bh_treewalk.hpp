@@ -128,11 +128,15 @@ __device__ __forceinline__ void walk_nodes_f64(const NodeD *__restrict__ gd, con
 }
 
 // ---- QuadF tree (BH_PRECISION_F32, BH_PRECISION_MIXED): walk_fast_kernel's eval and bucket ---------------------------
-// term(m, dx, dy, d2), d2 > 0: an accepted node or a bucket body.
+// term(m, dx, dy, d2), d2 > 0: an accepted node or a bucket body.  walk_quads_f32_from walks the tree whose root quad is
+// `root`: 0 for the context's own tree, the first quad of a received block for a peer's locally-essential tree (bh_let.hpp:
+// its child links are already indices into `quads`, its depth-cap buckets already aggregates, so `aux` is only ever read
+// for the own tree).  Every call starts from an empty stack: a lane's terms of one tree do not depend on the trees walked
+// before it.
 template <typename Term>
-__device__ __forceinline__ void walk_quads_f32(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
-                                               const float2 *__restrict__ spos, const float *__restrict__ smass, const float2 p,
-                                               const bool valid, Term term)
+__device__ __forceinline__ void walk_quads_f32_from(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
+                                                    const float2 *__restrict__ spos, const float *__restrict__ smass,
+                                                    const int32_t root, const float2 p, const bool valid, Term term)
 {
     const int lane = lane_id();
     LaneStack st;
@@ -174,7 +178,7 @@ __device__ __forceinline__ void walk_quads_f32(const QuadF *__restrict__ quads, 
         for (int c = 0; c < 4; ++c) eval(cq[q].xy[2 * c], cq[q].xy[2 * c + 1], cq[q].m[c], cq[q].thr[c], cq[q].child[c], mask);
     };
 
-    eval_quad(0, __ballot(valid));                                 // quad 0: the root in slot 0
+    eval_quad(root, __ballot(valid));                              // the root quad: the root in slot 0
     while (st.sp > 0) {
         int32_t base;
         uint64_t mask;
@@ -182,6 +186,15 @@ __device__ __forceinline__ void walk_quads_f32(const QuadF *__restrict__ quads, 
         if (base > 0) eval_quad(base, mask);
         else if (base <= -2) bucket(-base - 2, mask);              // (-1, a leaf, is never pushed)
     }
+}
+
+// the context's own tree: root quad 0
+template <typename Term>
+__device__ __forceinline__ void walk_quads_f32(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
+                                               const float2 *__restrict__ spos, const float *__restrict__ smass, const float2 p,
+                                               const bool valid, Term term)
+{
+    walk_quads_f32_from(quads, aux, spos, smass, 0, p, valid, term);
 }
 
 }  // namespace bh

@@ -273,6 +273,20 @@ def padded_root_box(xmin, xmax, ymin, ymax):
 
 
 
+def combine_energy_sums(rows):
+    """BhEnergy of the whole system from the ranks' shares, rows[r] = rank r's eight raw sums of
+    engine.let_energy_sums() (sum m, sum m x, sum m y, sum m vx, sum m vy, sum Lz, sum m |v|^2, sum m phi) followed by its
+    body count, in rank order.  Every quantity is added over the ranks with math.fsum -- the correctly rounded sum of the
+    W values, the same bits wherever and in whatever order it is formed -- and only then halved or divided."""
+    import math
+    from .engine import BhEnergy
+    q = [math.fsum(r[k] for r in rows) for k in range(8)]
+    n = sum(int(r[8]) for r in rows)
+    kinetic, potential = 0.5 * q[6], 0.5 * q[7]
+    com = (q[1] / q[0], q[2] / q[0]) if q[0] != 0.0 else (0.0, 0.0)
+    return BhEnergy(kinetic, potential, kinetic + potential, (q[3], q[4]), q[5], com, q[0], n)
+
+
 def init_process_group_from_env(backend: str | None = None):
     """RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run exports them."""
     rank = int(os.environ.get("RANK", "0"))
@@ -352,6 +366,8 @@ class LetStepper:
     step: local boxes -> all_gather (256 B per rank) -> local tree under the global box + one
     compact LET per peer -> all_to_all of fixed-size blocks -> forest walk (own tree + received
     LETs) + integrate.  No replicated work, two collectives, no host synchronisation.
+    potential() and energy() are the run's instruments: computed on the devices over the same forest,
+    combined deterministically, and without effect on the steps that follow.
 
     The blocks are fixed-size so that no count has to reach the host inside a step; autotune()
     sizes them once from measured LET sizes, and check() (call it outside timed regions, every so
@@ -400,8 +416,12 @@ class LetStepper:
         for rehearsing the multi-rank logic where RCCL cannot run (several ranks on one GPU)."""
         return self.lbounds.is_cuda and dist.is_initialized() and dist.get_backend() == "gloo"
 
-    def _exchange_bounds(self) -> None:
-        self.eng.let_bounds()
+    def _exchange_bounds(self, quiet: bool = False) -> None:
+        """quiet: for a diagnostic between two steps (engine.let_bounds(quiet=True))."""
+        if quiet:
+            self.eng.let_bounds(quiet=True)
+        else:
+            self.eng.let_bounds()
         if dist.is_initialized() and self.world > 1:
             if self._staged():
                 self.eng.sync()
@@ -413,6 +433,18 @@ class LetStepper:
         else:
             assert self.world == 1
             self.all_bounds.copy_(self.lbounds)
+
+    def _exchange_blocks(self) -> None:
+        """The all_to_all of the LET blocks, in line: block q of send -> block rank of q's recv."""
+        if not dist.is_initialized():
+            return                                            # (no process group: world 1, no peer)
+        if self._staged():
+            self.eng.sync()
+            out = torch.empty(self.recv.numel(), dtype=self.recv.dtype)
+            dist.all_to_all_single(out, self.send.cpu())
+            self.recv.copy_(out)
+        else:
+            dist.all_to_all_single(self.recv, self.send)
 
     def _mark(self, marks) -> None:
         if marks is not None:
@@ -446,19 +478,7 @@ class LetStepper:
         self._mark(marks)
         self.eng.let_build()
         self._mark(marks)
-        if dist.is_initialized() and self._staged():
-            self.eng.sync()
-            out = torch.empty(self.recv.numel(), dtype=self.recv.dtype)
-            dist.all_to_all_single(out, self.send.cpu())
-            self.recv.copy_(out)
-            if self.overlap:                                  # (nothing to overlap with here; same two launches)
-                self.eng.let_walk_local()
-                self._mark(marks)
-                self._mark(marks)
-                self.eng.let_walk_remote(integrate)
-                self._mark(marks)
-                return
-        elif dist.is_initialized() and self.overlap:
+        if dist.is_initialized() and self.overlap and not self._staged():
             # block q of send -> block rank of q's recv, on the collective's own stream; the local-tree
             # walk does not need it, the second walk launch waits for it
             work = dist.all_to_all_single(self.recv, self.send, async_op=True)
@@ -469,9 +489,8 @@ class LetStepper:
             self.eng.let_walk_remote(integrate)
             self._mark(marks)
             return
-        elif dist.is_initialized():
-            dist.all_to_all_single(self.recv, self.send)
-        if self.overlap:                                      # (no process group: world 1)
+        self._exchange_blocks()
+        if self.overlap:                                      # (staged, or no process group: nothing to overlap with; same two launches)
             self.eng.let_walk_local()
             self._mark(marks)
             self._mark(marks)
@@ -484,6 +503,44 @@ class LetStepper:
         else:
             self.eng.let_forces()
         self._mark(marks)
+
+    # -- diagnostics: potential and energy of the whole system, no rank holding more than its own bodies --------
+    def _quiet_forest(self) -> None:
+        """The forest of the CURRENT state on every rank -- bounds, all_gather, local tree + LETs, all_to_all, as in step()
+        -- by the engine's quiet bounds and build: the steps that follow are bit for bit what they would have been, and
+        rebalance() sees the cost weights of the last force walk.  (The LET size counters include this build.)"""
+        self._exchange_bounds(quiet=True)
+        self.eng.let_build(quiet=True)
+        self._exchange_blocks()
+
+    def potential(self, with_counts: bool = False):
+        """Potential per unit mass of this rank's bodies, in the order of ids / engine.download(), over exactly the
+        terms the step's forest force walk takes (with_counts: also the number of terms per body).  Collective: every
+        rank must call it.  Ends with check(): raises if a LET outgrew let_cap -- the potential is then as invalid as a
+        step's forces (check() reads the LET size counters, which starts a new observation interval)."""
+        self._quiet_forest()
+        out = self.eng.let_potential(with_counts)
+        self.check()
+        return out
+
+    def energy(self):
+        """BhEnergy of the WHOLE system, the same bits on every rank.  Each rank reduces its own bodies on the device
+        (engine.let_energy_sums: eight raw fp64 sums); the W x 8 sums and the W body counts are all-gathered and each
+        quantity is added over the ranks on the host with math.fsum -- the correctly rounded sum, so no order of the
+        backend's enters (an all_reduce(SUM) would leave the order, and the last bits, to the backend).  Collective;
+        ends with check() like potential()."""
+        self._quiet_forest()
+        mine = torch.tensor([*self.eng.let_energy_sums(), float(self.eng.n)], dtype=torch.float64)
+        if dist.is_initialized() and self.world > 1:
+            if self.lbounds.is_cuda and not self._staged():      # RCCL takes device tensors, gloo host tensors
+                mine = mine.to(self.lbounds.device)
+            rows = torch.empty(self.world * mine.numel(), dtype=torch.float64, device=mine.device)
+            dist.all_gather_into_tensor(rows, mine)
+            rows = rows.cpu()
+        else:
+            rows = mine
+        self.check()
+        return combine_energy_sums(rows.reshape(-1, 9).tolist())
 
     @property
     def ids(self):

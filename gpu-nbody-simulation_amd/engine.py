@@ -399,8 +399,9 @@ class BarnesHutEngine:
         self._check(self._lib.bh_let_configure(self._h, rank, world, let_cap, forest_base))
         self._let_world = world
 
-    def let_bounds(self) -> None:
-        self._check(self._lib.bh_let_bounds(self._h))
+    def let_bounds(self, quiet: bool = False) -> None:
+        """quiet: for a diagnostic between two steps -- the walk's bounds records stay for the next let_bounds()."""
+        self._check((self._lib.bh_let_bounds_quiet if quiet else self._lib.bh_let_bounds)(self._h))
 
     def let_pointers(self):
         """(lbounds, all_bounds, send, recv, block_bytes, boxes_per_rank): device pointers for the two
@@ -411,8 +412,10 @@ class BarnesHutEngine:
                                               C.byref(k)))
         return a.value, b.value, s.value, r.value, nb.value, k.value
 
-    def let_build(self) -> None:
-        self._check(self._lib.bh_let_build(self._h))
+    def let_build(self, quiet: bool = False) -> None:
+        """quiet: for a diagnostic between two steps -- no re-order, and everything a later step reads from an earlier
+        one (build count, sort samples, walk counters, the order the ORB cost weights are indexed by) is put back."""
+        self._check((self._lib.bh_let_build_quiet if quiet else self._lib.bh_let_build)(self._h))
 
     def let_walk(self) -> None:
         self._check(self._lib.bh_let_walk(self._h))
@@ -425,6 +428,24 @@ class BarnesHutEngine:
 
     def let_walk_remote(self, integrate: bool = True) -> None:
         self._check(self._lib.bh_let_walk_remote(self._h, 1 if integrate else 0))
+
+    def let_potential(self, with_counts: bool = False):
+        """Potential per unit mass of this rank's bodies (the order of download() / ids()) over the forest force walk's
+        terms: the own tree, then the received LETs in rank order.  Needs what let_forces() needs: a let_build() of the
+        current state and the peers' blocks delivered.  with_counts: also the terms summed per body."""
+        self._check(self._lib.bh_let_potential(self._h))
+        phi = np.zeros(max(self.n, 1))
+        cnt = np.zeros(max(self.n, 1), dtype=np.uint32) if with_counts else None
+        self._check(self._lib.bh_let_get_potential(self._h, _dptr(phi),
+                                                   cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if with_counts else None))
+        return (phi[:self.n], cnt[:self.n]) if with_counts else phi[:self.n]
+
+    def let_energy_sums(self) -> np.ndarray:
+        """This rank's share of (sum m, sum m x, sum m y, sum m vx, sum m vy, sum Lz, sum m |v|^2, sum m phi): raw fp64
+        sums of the deterministic device reduction (runs let_potential() unless the potential is current)."""
+        q = np.zeros(8)
+        self._check(self._lib.bh_let_energy(self._h, _dptr(q)))
+        return q
 
     def let_counts(self, with_overflow: bool = False):
         """Per peer, the largest LET of any let_build since the previous let_counts / let_configure (waits

@@ -238,7 +238,7 @@ int bh_get_interaction_counts(bh_ctx *ctx, uint32_t *counts);
  * (`occ == i`, and `occ + 2 == -i` under reference_compat), depth-cap aggregates, fp32 bucket leaves body by body.
  * d is the force walk's distance: sqrt(d2) + 1e-15 in the fp64 precisions (project.cu:630-634), the fp32 walk's
  * 1 / rsq(d2) in BH_PRECISION_F32 / MIXED (fp32 terms, fp64 sums).  Single GPU: a context in LET mode or with
- * world > 1 gets BH_ERR_STATE.
+ * world > 1 gets BH_ERR_STATE (LET mode has bh_let_potential / bh_let_energy, below).
  * The diagnostics do not perturb the run: a following bh_step computes the trajectory bit for bit as it would have
  * without them, in every precision.  They build their own tree of the current state (which bh_export_tree then
  * exports) but leave the forces, interaction counts, step timings and walk_launches of the last force walk as they
@@ -389,6 +389,42 @@ int bh_let_forces(bh_ctx *ctx);
 int bh_let_walk_local(bh_ctx *ctx);
 int bh_let_walk_remote(bh_ctx *ctx, int32_t integrate);
 int bh_let_counts(bh_ctx *ctx, uint32_t *counts, int32_t *overflow);
+/* --- diagnostics of the distributed step: potential and energy sums of a rank ---------------------
+ * The single-context diagnostics above refuse a context in LET mode; these are their forest forms (fp32 and mixed
+ * precision, as LET mode itself).  No rank ever holds more than its own bodies: a rank computes the potential of ITS
+ * bodies over the forest it holds, and its share of the eight sums; the host combines the ranks' shares.
+ * bh_let_potential: phi_i = -G sum M / d over exactly the terms the forest force walk takes for body i -- the own tree
+ *   from quad 0 (fp32 acceptance, own depth-cap buckets body by body, a body at d2 == 0 gives nothing), then the
+ *   received LET of every peer in rank order, the own rank skipped (remote buckets are aggregates) -- with the fp32
+ *   walk's term m * rsq(d2) in fp32, summed per body in fp64 in that fixed order: two calls on the same forest return
+ *   the same bits.  It walks the forest of the last bh_let_build, completed by the caller with the peers' blocks: the
+ *   preconditions of bh_let_forces.  BH_ERR_STATE outside LET mode (so in every precision without LET), before
+ *   bh_let_build, and when an integrating walk has moved the bodies since that build.  One wavefront per 64 bodies in
+ *   one launch, whatever shape the force walk takes.  It writes the potential and its own term counts only: forces,
+ *   interaction counts, group costs (the ORB weights), the bounds records, bh_stats' walk counters and the timings stay
+ *   the last force walk's.  A truncated block (bh_let_counts reports the overflow) is walked as safely as the force
+ *   walk walks it -- links past the block are cut -- and is as wrong.  The buffers are allocated on first use
+ *   (bh_stats.device_bytes grows then, not before).
+ * bh_let_get_potential: phi[n_local] (per unit mass) and, if counts != NULL, the terms summed per body -- equal to the
+ *   forest force walk's bh_get_interaction_counts -- in the rank's caller order (the order of bh_download / bh_get_ids).
+ *   BH_ERR_STATE unless a bh_let_potential of the current state exists: the potential stops being current at
+ *   bh_let_walk, bh_let_walk_remote with integrate, bh_upload, bh_initialize and bh_migrate_unpack.
+ * bh_let_energy: runs bh_let_potential unless the potential is current, then this rank's share of
+ *   sums[8] = sum m, sum m x, sum m y, sum m vx, sum m vy, sum m (x vy - y vx), sum m |v|^2, sum m phi
+ *   by the deterministic two-pass reduction of bh_energy -- RAW sums, nothing halved or divided: the caller adds the
+ *   ranks' shares (in a fixed order, compensated, if every rank is to get the same bits) and only then forms
+ *   kinetic = 1/2 sum m |v|^2, potential = 1/2 sum m phi, com = sum m x / sum m.  A rank without bodies returns zeros.
+ * bh_let_bounds_quiet / bh_let_build_quiet: bh_let_bounds and bh_let_build for a diagnostic between two steps -- same
+ *   boxes, tree, LETs and LET size counters, but everything a later step reads from an earlier one is put back: the
+ *   walk's bounds records stay for the next bh_let_bounds, the state is never re-ordered, the build count (re-order
+ *   cadence) and the sort's sample state are restored, bh_stats' walk counters and bh_let_build timings are left alone,
+ *   and bh_orb_histogram keeps weighting every body by the cost of its group in the last FORCE walk.  The steps that
+ *   follow compute bit for bit the trajectory they would have computed without the diagnostic. */
+int bh_let_bounds_quiet(bh_ctx *ctx);
+int bh_let_build_quiet(bh_ctx *ctx);
+int bh_let_potential(bh_ctx *ctx);
+int bh_let_get_potential(bh_ctx *ctx, double *phi, uint32_t *counts);
+int bh_let_energy(bh_ctx *ctx, double sums[8]);
 /* --- device-side body migration and re-balancing for the LET scheme -------
  * The reference is single-GPU (project.cu:918-1024 keeps every body on one device); this is new design.
  * Ownership is defined by an orthogonal-recursive-bisection cut tree over the global root box: the node
