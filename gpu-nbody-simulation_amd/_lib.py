@@ -108,6 +108,8 @@ SIGNATURES = {
     "bh_direct_forces": (C.c_int, [_ctx, C.POINTER(C.c_int64), C.c_int64, _dp]),
     "bh_force_check": (C.c_int, [_ctx, C.POINTER(C.c_int64), C.c_int64, _dp, _dp]),
     "bh_field_at": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_uint32)]),
+    "bh_set_softening": (C.c_int, [_ctx, C.c_double]),
+    "bh_get_softening": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

@@ -9,6 +9,8 @@
 //               summed per lane with Neumaier compensation, times -G at the end.
 //   F32 / MIXED: the fp32 walk's d2 from the fp32 sorted positions, its 1/d = v_rsq_f32(d2), the fp32 term M / d,
 //               accumulated in fp64.
+//   Plummer softening (bh_set_softening): the terms above at s2 = d2 + eps2 -- sqrt(s2) + 1e-15, v_rsq_f32(d2 + eps2) -- on the
+//               unchanged term set; eps2 = 0 adds 0.0 / 0.f, the identity, and is the unsoftened potential bit for bit.
 //
 // Reductions.  One fp64 term per body for each of: m, m x, m y, m vx, m vy, m (x vy - y vx), m |v|^2, m phi.  kDiagParts
 // workgroups take fixed grid-strided bodies, each lane keeps a Neumaier (sum, compensation) pair per quantity, and the
@@ -43,8 +45,9 @@ __device__ __forceinline__ void neumaier_fold(double &s, double &c, double s2, d
 template <bool COMPAT, int ACCEPT>
 __global__ __launch_bounds__(kBlock) void potential_f64_kernel(const NodeD *__restrict__ gd, const LinkD *__restrict__ ld,
                                                                const uint32_t *__restrict__ perm, const double2 *__restrict__ pos,
-                                                               int64_t n, double theta, double G, const TreeCounters *ctr,
-                                                               double *__restrict__ phi, uint32_t *__restrict__ counts)
+                                                               int64_t n, double theta, double G, double eps2,
+                                                               const TreeCounters *ctr, double *__restrict__ phi,
+                                                               uint32_t *__restrict__ counts)
 {
     if (ctr->overflow) return;
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void potential_f64_kernel(const NodeD *__re
     double sum = 0.0, comp = 0.0;
     uint32_t cnt = 0;
     walk_nodes_f64<ACCEPT, true>(
-        gd, ld, p, valid, theta,
+        gd, ld, p, valid, theta, eps2,
         [&](int32_t occ) { return occ == body32 || (COMPAT && occ == alt32); },   // project.cu:623-626, 646
         [&](double m, double, double, double, double d) { neumaier_add(sum, comp, m / d); ++cnt; });
     if (valid) {
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void potential_f64_kernel(const NodeD *__re
 __global__ __launch_bounds__(kBlock) void potential_f32_kernel(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
                                                                const float2 *__restrict__ spos, const float *__restrict__ smass,
                                                                const uint32_t *__restrict__ perm, int64_t n, double G,
-                                                               const TreeCounters *ctr, double *__restrict__ phi,
+                                                               float eps2, const TreeCounters *ctr, double *__restrict__ phi,
                                                                uint32_t *__restrict__ counts)
 {
     if (ctr->overflow) return;
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void potential_f32_kernel(const QuadF *__re
     double sum = 0.0;
     uint32_t cnt = 0;
     walk_quads_f32(quads, aux, spos, smass, p, valid, [&](float m, float, float, float d2) {
-        const float ri = __builtin_amdgcn_rsqf(d2);
+        const float ri = __builtin_amdgcn_rsqf(d2 + eps2);
         sum += (double)(m * ri);
         ++cnt;
     });
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void potential_f32_kernel(const QuadF *__re
 __global__ __launch_bounds__(kBlock) void forest_potential_f32_kernel(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
                                                                       const float2 *__restrict__ spos, const float *__restrict__ smass,
                                                                       const uint32_t *__restrict__ perm, int64_t n, double G,
-                                                                      const TreeCounters *ctr, int32_t n_trees, int32_t self_rank,
+                                                                      float eps2, const TreeCounters *ctr, int32_t n_trees, int32_t self_rank,
                                                                       int64_t forest_base, int64_t let_cap, double *__restrict__ phi,
                                                                       uint32_t *__restrict__ counts)
 {
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void forest_potential_f32_kernel(const Quad
         if (t == self_rank) continue;
         const int32_t root = (t < 0) ? 0 : (int32_t)(forest_base + (int64_t)t * let_cap);
         walk_quads_f32_from(quads, aux, spos, smass, root, p, valid, [&](float m, float, float, float d2) {
-            const float ri = __builtin_amdgcn_rsqf(d2);
+            const float ri = __builtin_amdgcn_rsqf(d2 + eps2);
             sum += (double)(m * ri);
             ++cnt;
         });

@@ -7,6 +7,9 @@
 //     d = sqrt(d2);  k = ((G*m_i)*m_j) / (d2*d);  sx += k*dx;  sy += k*dy
 // in fp64 with IEEE sqrt and division (correctly rounded) in every precision.  An fp32 state is widened exactly, so the
 // result is the direct sum of the state the device holds.  Coincident bodies give inf / NaN where the reference does.
+// Plummer softening (bh_set_softening): s2 = d2 + eps2, d = sqrt(s2), k = ((G*m_i)*m_j) / (s2*d), same order, j == i still
+// skipped by index; distinct coincident bodies then give a finite zero force.  d2 >= +0 or NaN here, so d2 + 0.0 is d2 bit
+// for bit: the one kernel serves eps2 = 0 as the contract above.
 //
 // Launch shape: one lane per target, 256-lane workgroups, every target in one launch (n_threads does not apply).  The
 // j-bodies go through LDS in tiles of kDirectTile caller indices (x, y, m as fp64: 24 KB); every lane of the workgroup
@@ -37,7 +40,7 @@ template <typename Real2, typename Real>
 __global__ __launch_bounds__(kBlock) void direct_forces_kernel(const Real2 *__restrict__ pos, const Real *__restrict__ mass,
                                                                const uint32_t *__restrict__ slot_of,
                                                                const int64_t *__restrict__ targets, int64_t t0,
-                                                               int64_t n_targets, int64_t n, double G,
+                                                               int64_t n_targets, int64_t n, double G, double eps2,
                                                                double2 *__restrict__ out)
 {
     __shared__ double2 tp[kDirectTile];
@@ -74,8 +77,9 @@ __global__ __launch_bounds__(kBlock) void direct_forces_kernel(const Real2 *__re
             d2 += dx * dx;
             const double dy = pj.y - yi;
             d2 += dy * dy;
-            const double d = sqrt(d2);
-            const double f = (gmi * tm[k]) / (d2 * d);
+            const double s2 = d2 + eps2;
+            const double d = sqrt(s2);
+            const double f = (gmi * tm[k]) / (s2 * d);
             if (k != self) {
                 sx += f * dx;
                 sy += f * dy;

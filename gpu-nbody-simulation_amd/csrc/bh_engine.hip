@@ -61,6 +61,10 @@ struct bh_ctx {
     bool tree64() const { return mode == Mode::Exact || mode == Mode::F64; }
     bool state64() const { return mode != Mode::F32; }    // fp64 state arrays
     bool compat = true;
+    // Plummer softening (bh_set_softening; 0 = none, and always 0 in Mode::Exact): the length, its square for the fp64
+    // kernels, and (float)eps2 for the fp32 walks -- 0.f there selects the unsoftened kernels
+    double eps = 0.0, eps2 = 0.0;
+    float eps2f = 0.f;
     bool exact_thresholds = false; // Mode::Exact: nodes carry exact d2 thresholds for the walk's acceptance test (off: BH_FLAG_WALK_PORTABLE)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -644,10 +648,16 @@ int launch_walk_f64(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
         wa.mass = (const double *)c->mass; wa.force_out = (double2 *)c->force; wa.lo = plo; wa.hi = phi;
         wa.G = c->cfg.G; wa.dt = c->cfg.dt; wa.integrate = w.integrate ? 1 : 0; wa.ctr = c->ctr;
         wa.body_counts = w.stats ? c->body_counts : nullptr; wa.slots = w.slots; wa.bpw = k.bpw;
+        wa.eps2 = c->eps2;
         dispatch([&](auto compat, auto deep_stack) {
             constexpr bool CP = decltype(compat)::value, DP = decltype(deep_stack)::value;
             auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kF64Block), 0, c->stream, wa); };
-            if (w.stats) go(walk_f64_kernel<CP, true, DP, false>);
+            if (c->eps2 != 0.0) {                                    // softened terms: the same loops with one v_add_f64
+                if (w.stats) go(walk_f64_soft_kernel<CP, true, DP, false>);
+                else if (k.use_asm) go(walk_f64_soft_kernel<CP, false, DP, true>);
+                else go(walk_f64_soft_kernel<CP, false, DP, false>);
+            }
+            else if (w.stats) go(walk_f64_kernel<CP, true, DP, false>);
             else if (k.use_asm) go(walk_f64_kernel<CP, false, DP, true>);
             else go(walk_f64_kernel<CP, false, DP, false>);
         }, c->compat, deep);
@@ -706,6 +716,7 @@ int launch_walk_f32(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
     a.n_trees = c->let_mode ? c->world : 0; a.self_rank = c->let_mode ? c->rank : -1;
     a.part = w.part; a.acc_part = c->acc_part;
     a.forest_base = c->forest_base; a.let_cap = c->let_cap;
+    a.eps2 = c->eps2f;
     c->exp.walk_args(a);
     a.group_cost = (w.lo == 0 && w.hi == c->n) ? c->group_cost : nullptr;
     a.bucket_consts = c->walk_consts;
@@ -968,6 +979,30 @@ void bh_destroy(bh_ctx *c)
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+int bh_set_softening(bh_ctx *c, double eps)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(eps >= 0.0) || !std::isfinite(eps))
+        return fail(c, BH_ERR_ARG, "bh_set_softening: the softening length must be finite and >= 0");
+    if (eps != 0.0 && c->mode == Mode::Exact)
+        return fail(c, BH_ERR_ARG, "bh_set_softening: BH_PRECISION_F64_EXACT reproduces the reference's results bit for bit and the "
+                                   "reference has no softening -- use BH_PRECISION_F64, MIXED or F32 for a softened run");
+    const double eps2 = eps * eps;
+    if (!std::isfinite(eps2)) return fail(c, BH_ERR_ARG, "bh_set_softening: the square of the softening length overflows");
+    c->eps = eps;
+    c->eps2 = eps2;
+    c->eps2f = (float)eps2;             // (0.f for a tiny eps: the fp32 walks then run their unsoftened kernels)
+    c->phi_current = false;             // phi holds the potential of another law until it is recomputed
+    return BH_OK;
+}
+
+int bh_get_softening(bh_ctx *c, double *eps)
+{
+    if (!c || !eps) return fail(c, BH_ERR_ARG, "bh_get_softening: null argument");
+    *eps = c->eps;
+    return BH_OK;
 }
 
 int bh_set_stream(bh_ctx *c, void *hip_stream)
@@ -1276,7 +1311,7 @@ static int enqueue_potential(bh_ctx *c)
             constexpr bool CP = decltype(compat)::value;
             auto go = [&](auto kern) {
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, c->stream, c->gd, c->ld, c->perm, pos, c->n, c->cfg.theta,
-                                   c->cfg.G, c->ctr, c->phi, c->phi_counts);
+                                   c->cfg.G, c->eps2, c->ctr, c->phi, c->phi_counts);
             };
             if (accept == kAcceptThr) go(potential_f64_kernel<CP, kAcceptThr>);
             else if (accept == kAcceptExactThr) go(potential_f64_kernel<CP, kAcceptExactThr>);
@@ -1284,7 +1319,7 @@ static int enqueue_potential(bh_ctx *c)
         }, c->compat);
     } else {
         hipLaunchKernelGGL(potential_f32_kernel, dim3(grid), dim3(kBlock), 0, c->stream, c->qf, c->aux, c->spos, c->smass, c->perm,
-                           c->n, c->cfg.G, c->ctr, c->phi, c->phi_counts);
+                           c->n, c->cfg.G, c->eps2f, c->ctr, c->phi, c->phi_counts);
     }
     BH_HIP(c, hipGetLastError());
     return BH_OK;
@@ -1398,7 +1433,8 @@ static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targe
             using Real2 = decltype(r2);
             using Real = decltype(r2.x);
             hipLaunchKernelGGL((direct_forces_kernel<Real2, Real>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
-                               (const Real2 *)c->pos, (const Real *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->direct_out);
+                               (const Real2 *)c->pos, (const Real *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->eps2,
+                               c->direct_out);
         });
         BH_HIP(c, hipGetLastError());
         BH_HIP(c, hipMemcpyAsync(out + 2 * t0, c->direct_out, k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
@@ -1513,14 +1549,14 @@ static int enqueue_field(bh_ctx *c, int64_t k)
     if (c->tree64()) {
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, c->gd, c->ld, c->field_order, c->field_points, k, c->cfg.theta,
-                               c->cfg.G, c->ctr, c->field_accel, c->field_phi, c->field_counts);
+                               c->cfg.G, c->eps2, c->ctr, c->field_accel, c->field_phi, c->field_counts);
         };
         if (c->mode == Mode::F64) go(field_f64_kernel<kAcceptThr>);
         else if (c->exact_thresholds) go(field_f64_kernel<kAcceptExactThr>);
         else go(field_f64_kernel<kAcceptSize>);
     } else {
         hipLaunchKernelGGL(field_f32_kernel, dim3(grid), dim3(kBlock), 0, st, c->qf, c->aux, c->spos, c->smass, c->field_order,
-                           c->field_points, k, c->cfg.G, c->ctr, c->field_accel, c->field_phi, c->field_counts);
+                           c->field_points, k, c->cfg.G, c->eps2f, c->ctr, c->field_accel, c->field_phi, c->field_counts);
     }
     BH_HIP(c, hipGetLastError());
     return BH_OK;
@@ -2047,7 +2083,7 @@ int bh_let_potential(bh_ctx *c)
     int rc = diag_alloc(c);
     if (!rc && c->n > 0) {
         hipLaunchKernelGGL(forest_potential_f32_kernel, dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream, c->qf, c->aux,
-                           c->spos, c->smass, c->perm, c->n, c->cfg.G, c->ctr, (int32_t)c->world, (int32_t)c->rank, c->forest_base,
+                           c->spos, c->smass, c->perm, c->n, c->cfg.G, c->eps2f, c->ctr, (int32_t)c->world, (int32_t)c->rank, c->forest_base,
                            c->let_cap, c->phi, c->phi_counts);
         BH_HIP(c, hipGetLastError());
     }

@@ -9,6 +9,8 @@
 //               inf * 0, a non-finite acceleration.
 //   F32 / MIXED: the point is rounded to fp32 here; ri = v_rsq_f32(d2), w = m ri ri ri, the terms w dx, w dy and m ri in
 //               fp32, summed in fp64 and multiplied by G in fp64 at the end.  A node or bucket body at d2 == 0 gives nothing.
+//   Plummer softening (bh_set_softening): the same expressions at s2 = d2 + eps2 -- d = sqrt(s2) + 1e-15, f = (G M) / s2;
+//               ri = v_rsq_f32(d2 + eps2) -- on the unchanged term set.  eps2 = 0 adds 0.0 / 0.f: the unsoftened field bit for bit.
 //
 // Order of the points.  One wavefront walks 64 points together and opens the union of their walks, so the points are
 // put in Morton order first: field_keys_kernel maps a point to 16 bits per axis in the tree's root box (clamped: points
@@ -66,9 +68,9 @@ __global__ __launch_bounds__(kBlock) void field_keys_kernel(const double2 *__res
 template <int ACCEPT>
 __global__ __launch_bounds__(kBlock) void field_f64_kernel(const NodeD *__restrict__ gd, const LinkD *__restrict__ ld,
                                                            const uint32_t *__restrict__ order, const double2 *__restrict__ points,
-                                                           int64_t k, double theta, double G, const TreeCounters *ctr,
-                                                           double2 *__restrict__ accel, double *__restrict__ phi,
-                                                           uint32_t *__restrict__ counts)
+                                                           int64_t k, double theta, double G, double eps2,
+                                                           const TreeCounters *ctr, double2 *__restrict__ accel,
+                                                           double *__restrict__ phi, uint32_t *__restrict__ counts)
 {
     if (ctr->overflow) return;
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -78,10 +80,10 @@ __global__ __launch_bounds__(kBlock) void field_f64_kernel(const NodeD *__restri
     double ax = 0.0, ay = 0.0, ph = 0.0;
     uint32_t cnt = 0;
     walk_nodes_f64<ACCEPT, false>(
-        gd, ld, p, valid, theta, [](int32_t) { return false; },
-        [&](double m, double dx, double dy, double d2, double d) {
+        gd, ld, p, valid, theta, eps2, [](int32_t) { return false; },
+        [&](double m, double dx, double dy, double s2, double d) {
             const double gm = G * m;
-            const double f = gm / d2;                              // project.cu:651-658 with m_i = 1
+            const double f = gm / s2;                              // project.cu:651-658 with m_i = 1
             ax += f * (dx / d);
             ay += f * (dy / d);
             ph += gm / d;
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void field_f64_kernel(const NodeD *__restri
 __global__ __launch_bounds__(kBlock) void field_f32_kernel(const QuadF *__restrict__ quads, const NodeAux *__restrict__ aux,
                                                            const float2 *__restrict__ spos, const float *__restrict__ smass,
                                                            const uint32_t *__restrict__ order, const double2 *__restrict__ points,
-                                                           int64_t k, double G, const TreeCounters *ctr,
+                                                           int64_t k, double G, float eps2, const TreeCounters *ctr,
                                                            double2 *__restrict__ accel, double *__restrict__ phi,
                                                            uint32_t *__restrict__ counts)
 {
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void field_f32_kernel(const QuadF *__restri
     uint32_t cnt = 0;
     // the fp32 walk's term of a mass m at (dx, dy), d2 > 0 (walk_fast_kernel: rsq, m ri ri ri)
     walk_quads_f32(quads, aux, spos, smass, p, valid, [&](const float m, const float dx, const float dy, const float d2) {
-        const float ri = __builtin_amdgcn_rsqf(d2);
+        const float ri = __builtin_amdgcn_rsqf(d2 + eps2);
         const float mri = m * ri;
         const float w = mri * ri * ri;
         ax += (double)(w * dx);

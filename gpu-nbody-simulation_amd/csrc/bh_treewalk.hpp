@@ -62,16 +62,20 @@ struct LaneStack {
 };
 
 // ---- fp64 tree (NodeD / LinkD): the root alone, then quads of four siblings ------------------------------------------
-// self(occ): the leaf with this occupant is the walker's own and is skipped.  term(m, dx, dy, d2, d), d = sqrt(d2) + 1e-15
-// (project.cu:634): an accepted node.  Acceptance is decided on d2.  EAGER_D false (the field, whose term is a square root
+// self(occ): the leaf with this occupant is the walker's own and is skipped.  term(m, dx, dy, s2, d), s2 = d2 + eps2,
+// d = sqrt(s2) + 1e-15 (project.cu:634 at eps2 = 0): an accepted node.  Acceptance is decided on the geometric d2 -- eps2,
+// the square of the Plummer softening length (bh_set_softening), enters the term only; d2 + 0.0 is d2 bit for bit (d2 >= +0
+// or NaN), so eps2 = 0 is the unsoftened walk.  kAcceptSize keeps the geometric d for its criterion; the term takes that one
+// again where eps2 = 0 and a softened d of its own otherwise.  EAGER_D false (the field, whose term is a square root
 // and four divisions): d and the term run under the accepting lanes only, behind a wave-uniform test that skips them
-// where no lane accepts -- except that kAcceptSize, whose criterion itself needs d, forms d for every node.  EAGER_D true
+// where no lane accepts -- except that kAcceptSize, whose criterion itself needs it, forms the geometric d for every node
+// (and with eps2 > 0 the term's d under the accepting lanes as well).  EAGER_D true
 // (the potential, whose term is one division): d for every node and no such test -- deciding first was measured never
 // faster for the fp64 potential walk and 2 to 10 % slower at 65,536 bodies ("One traversal").  d is
 // a function of d2 alone, so where it is formed changes no bit.
 template <int ACCEPT, bool EAGER_D, typename Self, typename Term>
 __device__ __forceinline__ void walk_nodes_f64(const NodeD *__restrict__ gd, const LinkD *__restrict__ ld, const double2 p,
-                                               const bool valid, const double theta, Self self, Term term)
+                                               const bool valid, const double theta, const double eps2, Self self, Term term)
 {
     const int lane = lane_id();
     LaneStack st;
@@ -91,11 +95,16 @@ __device__ __forceinline__ void walk_nodes_f64(const NodeD *__restrict__ gd, con
         const double dx = q.cx - p.x, dy = q.cy - p.y;
         const double d2 = (ACCEPT == kAcceptThr) ? fma(dx, dx, dy * dy) : dx * dx + dy * dy;
         const bool leaf = k.child < 0;
-        double d = 0.0;
+        const double s2 = d2 + eps2;
+        double d = 0.0, dg = 0.0;
+        if (ACCEPT == kAcceptSize) dg = sqrt(d2) + 1e-15;          // project.cu:643: the criterion itself needs the geometric d
+        // the term's d: with eps2 = 0 (wave-uniform) s2 is d2 bit for bit, and kAcceptSize's dg serves again -- one square
+        // root per node, as before there was a softening; otherwise a root of its own
+        auto term_d = [&] { return (ACCEPT == kAcceptSize && eps2 == 0.0) ? dg : sqrt(s2) + 1e-15; };      // project.cu:634
         bool take;
-        if (EAGER_D || ACCEPT == kAcceptSize) d = sqrt(d2) + 1e-15;    // project.cu:634
+        if (EAGER_D) d = term_d();
         if (ACCEPT == kAcceptSize) {
-            take = leaf ? !self(k.occ) : q.size / d < theta;       // project.cu:643: the criterion itself needs d
+            take = leaf ? !self(k.occ) : q.size / dg < theta;
         } else if (ACCEPT == kAcceptThr) {
             take = leaf ? !self(k.occ) : q.size < d2;
         } else {
@@ -104,11 +113,11 @@ __device__ __forceinline__ void walk_nodes_f64(const NodeD *__restrict__ gd, con
         const bool mine = ((mask >> lane) & 1ull) != 0ull;
         const bool acc = mine && take;
         if (EAGER_D) {
-            if (acc) term(q.m, dx, dy, d2, d);
+            if (acc) term(q.m, dx, dy, s2, d);
         } else if (__ballot(acc) != 0ull) {                        // wave-uniform: no lane takes it, no sqrt and no division
             if (acc) {
-                if (ACCEPT != kAcceptSize) d = sqrt(d2) + 1e-15;
-                term(q.m, dx, dy, d2, d);
+                d = term_d();
+                term(q.m, dx, dy, s2, d);
             }
         }
         if (!leaf) {
@@ -128,7 +137,8 @@ __device__ __forceinline__ void walk_nodes_f64(const NodeD *__restrict__ gd, con
 }
 
 // ---- QuadF tree (BH_PRECISION_F32, BH_PRECISION_MIXED): walk_fast_kernel's eval and bucket ---------------------------
-// term(m, dx, dy, d2), d2 > 0: an accepted node or a bucket body.  walk_quads_f32_from walks the tree whose root quad is
+// term(m, dx, dy, d2), d2 > 0: an accepted node or a bucket body (the geometric d2: a softened term adds eps2 itself).
+// walk_quads_f32_from walks the tree whose root quad is
 // `root`: 0 for the context's own tree, the first quad of a received block for a peer's locally-essential tree (bh_let.hpp:
 // its child links are already indices into `quads`, its depth-cap buckets already aggregates, so `aux` is only ever read
 // for the own tree).  Every call starts from an empty stack: a lane's terms of one tree do not depend on the trees walked

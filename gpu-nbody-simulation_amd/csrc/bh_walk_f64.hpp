@@ -104,7 +104,11 @@ constexpr int kF64Block = BH_F64_BLOCK;
 #define BH64_PRIO_UP ""
 #define BH64_PRIO_DOWN ""
 #endif
-#define BH64_FORCE(M)                                                                               \
+// EPS: "" or BH64_EPS_ADD (Plummer softening: s2 = d2 + eps2 in place, after every decision has been taken on d2)
+#define BH64_EPS_NONE ""
+#define BH64_EPS_ADD "v_add_f64 v[28:29], v[28:29], %[eps2]\n"
+#define BH64_FORCE(M, EPS)                                                                          \
+    EPS                                                                                             \
     "v_rsq_f64_e32 v[30:31], v[28:29]\n"                                                            \
     "s_nop 0\n"                                                                                     \
     "v_mul_f64 v[32:33], v[28:29], v[30:31]\n"              /* t = d2 y0                */         \
@@ -117,7 +121,7 @@ constexpr int kF64Block = BH_F64_BLOCK;
     "v_mul_f64 v[34:35], v[34:35], v[32:33]\n"              /* w = M / (d2 d)           */         \
     "v_fma_f64 v[36:37], v[34:35], v[24:25], v[36:37]\n"                                            \
     "v_fma_f64 v[38:39], v[34:35], v[26:27], v[38:39]\n"
-#define BH64_CHILD(CX, CY, M, MHI, THR, CS, TAG)                                                    \
+#define BH64_CHILD(CX, CY, M, MHI, THR, CS, TAG, EPS)                                               \
     "s_cmp_gt_i32 " MHI ", 0x3cd203af\n"                    /* m > 1e-15 for sure */                \
     "s_cbranch_scc0 Lrare" TAG "_%=\n"                                                              \
     "Lcont" TAG "_%=:\n"                                                                            \
@@ -136,7 +140,7 @@ constexpr int kF64Block = BH_F64_BLOCK;
     "s_mov_b64 s[68:69], s[70:71]\n"                                                                \
     "Lforce" TAG "_%=:\n"                                                                           \
     "s_cbranch_execz Lskip" TAG "_%=\n"                                                             \
-    BH64_FORCE(M)                                                                                   \
+    BH64_FORCE(M, EPS)                                                                              \
     "Lskip" TAG "_%=:\n"                                                                            \
     "s_mov_b64 exec, s[64:65]\n"                                                                    \
     "Lnext" TAG "_%=:\n"
@@ -185,7 +189,7 @@ constexpr int kF64Block = BH_F64_BLOCK;
     "s_branch Lload_%=\n"                                                                           \
     "LpopHi_%=:\n"                                                                                  \
     "v_readfirstlane_b32 s66, v45\n v_readfirstlane_b32 s64, v46\n v_readfirstlane_b32 s65, v47\n"
-#define BH64_LOOP(POP, COMPAT_CMP, PUSHCHK, HI_STUBS)                                               \
+#define BH64_LOOP(POP, COMPAT_CMP, PUSHCHK, HI_STUBS, EPS)                                          \
     "v_mov_b32_e32 v20, %[pxl]\n v_mov_b32_e32 v21, %[pxh]\n"                                       \
     "v_mov_b32_e32 v22, %[pyl]\n v_mov_b32_e32 v23, %[pyh]\n"                                       \
     "v_mov_b32_e32 v36, %[sxl]\n v_mov_b32_e32 v37, %[sxh]\n"                                       \
@@ -216,10 +220,10 @@ constexpr int kF64Block = BH_F64_BLOCK;
     "s_mov_b64 exec, s[64:65]\n"                                                                    \
     "s_waitcnt lgkmcnt(0)\n"                                                                        \
     BH64_PRIO_DOWN                                                                                  \
-    BH64_CHILD("s[24:25]", "s[26:27]", "s[28:29]", "s29", "s[30:31]", "s56", "0")                   \
-    BH64_CHILD("s[32:33]", "s[34:35]", "s[36:37]", "s37", "s[38:39]", "s58", "1")                   \
-    BH64_CHILD("s[40:41]", "s[42:43]", "s[44:45]", "s45", "s[46:47]", "s60", "2")                   \
-    BH64_CHILD("s[48:49]", "s[50:51]", "s[52:53]", "s53", "s[54:55]", "s62", "3")                   \
+    BH64_CHILD("s[24:25]", "s[26:27]", "s[28:29]", "s29", "s[30:31]", "s56", "0", EPS)              \
+    BH64_CHILD("s[32:33]", "s[34:35]", "s[36:37]", "s37", "s[38:39]", "s58", "1", EPS)              \
+    BH64_CHILD("s[40:41]", "s[42:43]", "s[44:45]", "s45", "s[46:47]", "s60", "2", EPS)              \
+    BH64_CHILD("s[48:49]", "s[50:51]", "s[52:53]", "s53", "s[54:55]", "s62", "3", EPS)              \
     "s_branch Lloop_%=\n"                                                                           \
     BH64_STUBS("s28", "s29", "s56", "s57", "0", COMPAT_CMP, PUSHCHK)                                \
     BH64_STUBS("s36", "s37", "s58", "s59", "1", COMPAT_CMP, PUSHCHK)                                \
@@ -232,10 +236,10 @@ constexpr int kF64Block = BH_F64_BLOCK;
     "v_mov_b32_e32 %[sxl], v36\n v_mov_b32_e32 %[sxh], v37\n"                                       \
     "v_mov_b32_e32 %[syl], v38\n v_mov_b32_e32 %[syh], v39\n"
 #define BH64_HI_STUBS BH64_PUSH_HI("s56", "0") BH64_PUSH_HI("s58", "1") BH64_PUSH_HI("s60", "2") BH64_PUSH_HI("s62", "3")
-#define BH64_OPERANDS                                                                               \
+#define BH64_OPERANDS(EXTRA_IN)                                                                     \
     : [sxl] "+v"(sxl), [sxh] "+v"(sxh), [syl] "+v"(syl), [syh] "+v"(syh), "+{s72}"(first), "+{s[68:69]}"(mask)         \
     : [gd] "s"(gd), [ld] "s"(ld), [ntiny] "s"(ntiny), [pxl] "v"(pxl), [pxh] "v"(pxh), [pyl] "v"(pyl), [pyh] "v"(pyh),  \
-      [body] "v"(body)                                                                              \
+      [body] "v"(body) EXTRA_IN                                                                     \
     : BH64_GUARD_CLOBBER                                                                            \
       "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s32", "s33", "s34", "s35", "s36", "s37", "s38", "s39",   \
       "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55",   \
@@ -246,19 +250,27 @@ constexpr int kF64Block = BH_F64_BLOCK;
 
 // Walks the subtree below quad `first` (node id of its first sibling) for the lanes in `mask`; the sums continue from
 // (sx, sy).  gd / ld: the node and link arrays; byte offsets are 32-bit (the caller checks node_cap * 32 < 4 GiB).
-template <bool COMPAT, bool DEEP>
+// SOFT: eps2 (> 0) in a pair of VGPRs -- the vector file has sixteen to spare, the scalar file none.
+#define BH64_NO_EXTRA
+#define BH64_EPS_IN , [eps2] "v"(eps2)
+#define BH64_WALK(POP, COMPAT_CMP, PUSHCHK, HI_STUBS)                                                                  \
+    do {                                                                                                               \
+        if constexpr (SOFT) asm volatile(BH64_LOOP(POP, COMPAT_CMP, PUSHCHK, HI_STUBS, BH64_EPS_ADD) BH64_OPERANDS(BH64_EPS_IN)); \
+        else asm volatile(BH64_LOOP(POP, COMPAT_CMP, PUSHCHK, HI_STUBS, BH64_EPS_NONE) BH64_OPERANDS(BH64_NO_EXTRA)); \
+    } while (0)
+template <bool COMPAT, bool DEEP, bool SOFT>
 __device__ __forceinline__ void walk64_asm(const char BH64_CONSTANT *gd, const char BH64_CONSTANT *ld, int32_t first, uint64_t mask,
-                                           double px, double py, int32_t body, double &sx, double &sy)
+                                           double px, double py, int32_t body, double eps2, double &sx, double &sy)
 {
     const double ntiny = -1e-15;
     int32_t pxl = __double2loint(px), pxh = __double2hiint(px), pyl = __double2loint(py), pyh = __double2hiint(py);
     int32_t sxl = __double2loint(sx), sxh = __double2hiint(sx), syl = __double2loint(sy), syh = __double2hiint(sy);
     if constexpr (DEEP) {
-        if constexpr (COMPAT) asm volatile(BH64_LOOP(BH64_POP_DEEP, BH64_COMPAT_ON, BH64_PUSHCHK, BH64_HI_STUBS) BH64_OPERANDS);
-        else asm volatile(BH64_LOOP(BH64_POP_DEEP, BH64_COMPAT_OFF, BH64_PUSHCHK, BH64_HI_STUBS) BH64_OPERANDS);
+        if constexpr (COMPAT) BH64_WALK(BH64_POP_DEEP, BH64_COMPAT_ON, BH64_PUSHCHK, BH64_HI_STUBS);
+        else BH64_WALK(BH64_POP_DEEP, BH64_COMPAT_OFF, BH64_PUSHCHK, BH64_HI_STUBS);
     } else {
-        if constexpr (COMPAT) asm volatile(BH64_LOOP(BH64_POP_FAST, BH64_COMPAT_ON, BH64_NOCHK, "") BH64_OPERANDS);
-        else asm volatile(BH64_LOOP(BH64_POP_FAST, BH64_COMPAT_OFF, BH64_NOCHK, "") BH64_OPERANDS);
+        if constexpr (COMPAT) BH64_WALK(BH64_POP_FAST, BH64_COMPAT_ON, BH64_NOCHK, "");
+        else BH64_WALK(BH64_POP_FAST, BH64_COMPAT_OFF, BH64_NOCHK, "");
     }
     sx = w64_f64(sxl, sxh);
     sy = w64_f64(syl, syh);
@@ -281,206 +293,26 @@ struct WalkF64Args {
     uint32_t *body_counts;         // counting variant: accepted force evaluations per body, may be null
     double *slots;                 // bh_bounds.hpp: bounds records the new positions fold into (next root box), may be null
     int32_t bpw, pad1;             // bodies per wavefront, a power of two <= 64 (see walk_exact_kernel): few bodies, short chains
+    double eps2;                   // Plummer softening: eps * eps; read by walk_f64_soft_kernel only
 };
 
+// SOFT (Plummer softening, bh_set_softening): an accepted term is taken at s2 = d2 + eps2 -- one fp64 add, then the same
+// sequence on s2: y = 1 / sqrt(s2) by v_rsq_f64 and the Newton step, 1 / s2 = y^2, 1 / d = y - 1e-15 y^2 (the offset stays:
+// eps -> 0 is continuous with the unsoftened walk).  Every decision -- the cut-off, the occupant test, thr < d2 -- stays on the
+// geometric d2, so the term set does not depend on eps.  The body is one text, bh_walk_f64_body.hpp, compiled into two
+// kernels: walk_f64_kernel (SOFT = false: instruction for instruction the code it was before) and walk_f64_soft_kernel.
 template <bool COMPAT, bool STATS, bool DEEP = false, bool ASM = false>
 __global__ __launch_bounds__(kF64Block) void walk_f64_kernel(WalkF64Args a)
 {
-    static_assert(!ASM || !STATS, "the assembly loop carries no counters");
-#if defined(BH64_LDS_PAD) && BH64_LDS_PAD
-    __shared__ int s_pad[BH64_LDS_PAD / 4];
-    if (a.dt == -12345.0) s_pad[threadIdx.x] = 1;                // (never true: keeps the array alive)
-    asm volatile("" ::"v"(s_pad[0]));
-#endif
-    if (a.ctr->overflow) return;
-    const int lane = lane_id();
-    const int64_t s = a.lo + ((int64_t)blockIdx.x * (kF64Block / kWave) + wave_id()) * a.bpw + lane;
-    const bool valid = lane < a.bpw && s < a.hi;
-    const int64_t body = valid ? (int64_t)a.perm[s] : -1;
-    const double2 p = valid ? a.pos[body] : double2{0.0, 0.0};
-    const double mi = valid ? a.mass[body] : 0.0;
-    const NodeD *gd = a.gd;
-    const LinkD *ld = a.ld;
-    double sx = 0.0, sy = 0.0;                       // sum of M * d_vec / (d2 * d)
-    unsigned long long n_vis = 0, n_int = 0, n_wave = 0, n_quad = 0, n_acc = 0;
-    uint32_t my_int = 0;
+    constexpr bool SOFT = false;
+#include "bh_walk_f64_body.hpp"
+}
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    const char BH64_CONSTANT *cg = (const char BH64_CONSTANT *)gd;
-    const char BH64_CONSTANT *cl = (const char BH64_CONSTANT *)ld;
-#pragma clang diagnostic pop
-    // (all three requests of a quad are issued together and waited for once: left to itself the compiler issues the second
-    // half and the links only after the first half has arrived and its first node has passed the empty test -- two round
-    // trips per quad)
-    auto load_quad = [&](int32_t first) {
-        Quad64 q;
-        const char BH64_CONSTANT *pn = cg + (int64_t)first * 32;
-        const char BH64_CONSTANT *pl = cl + (int64_t)first * 8;
-        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\t"
-                     "s_load_dwordx16 %1, %3, 0x40\n\t"
-                     "s_load_dwordx8 %2, %4, 0x0\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&s"(q.a), "=&s"(q.b), "=&s"(q.l)
-                     : "s"(pn), "s"(pl)
-                     : "memory");
-        return q;
-    };
-
-    int32_t v_base = 0, v_lo = 0, v_hi = 0, v_base2 = 0, v_lo2 = 0, v_hi2 = 0;   // register-lane stack, 128 entries
-    int sp = 0;
-    int32_t h_idx = 0;                                // hand-off slot of the quad being evaluated: < 0 = free (a child index is > 0)
-    uint64_t h_mask = 0;
-
-    auto push = [&](int32_t child, uint64_t open) {
-        if (!DEEP || sp < kWave) {
-            v_base = bh64_writelane_i32(child, sp, v_base);
-            v_lo = bh64_writelane_i32((int32_t)(uint32_t)open, sp, v_lo);
-            v_hi = bh64_writelane_i32((int32_t)(uint32_t)(open >> 32), sp, v_hi);
-        } else if (sp < 2 * kWave) {
-            v_base2 = bh64_writelane_i32(child, sp - kWave, v_base2);
-            v_lo2 = bh64_writelane_i32((int32_t)(uint32_t)open, sp - kWave, v_lo2);
-            v_hi2 = bh64_writelane_i32((int32_t)(uint32_t)(open >> 32), sp - kWave, v_hi2);
-        }
-        ++sp;                                         // (beyond 128 cannot happen: 3 * 31 + 1 entries at max_depth 32)
-    };
-    auto pop = [&](int32_t &base, uint64_t &mask) {
-        --sp;
-        if (!DEEP || sp < kWave) {
-            base = __builtin_amdgcn_readlane(v_base, sp);
-            mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(v_hi, sp) << 32) | (uint32_t)__builtin_amdgcn_readlane(v_lo, sp);
-        } else {
-            base = __builtin_amdgcn_readlane(v_base2, sp - kWave);
-            mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(v_hi2, sp - kWave) << 32) |
-                   (uint32_t)__builtin_amdgcn_readlane(v_lo2, sp - kWave);
-        }
-    };
-
-    // one node for the lanes in `mask` (all arguments but the position wave-uniform): the statement of BH64_CHILD
-    const int32_t body32 = (int32_t)body;                         // (perm is 32-bit; -1 on padding lanes)
-    const int32_t compat32 = -2 - body32;                         // occ + 2 == -body, project.cu:646
-    auto eval = [&](double cx, double cy, double m, double thr, int32_t child, int32_t occ, uint64_t mask) {
-        // m <= 1e-15 (project.cu:617) on the bit pattern, with scalar integer compares
-        {
-            const int32_t mh = __double2hiint(m);
-            if (__builtin_expect(mh <= 0x3CD203AF, 0)) {
-                if (mh < 0x3CD203AF) return;
-                if ((uint32_t)__double2loint(m) <= 0x9EE75616u) return;
-            }
-        }
-        const double dx = cx - p.x, dy = cy - p.y;
-        const double d2 = fma(dx, dx, dy * dy);
-        uint64_t takem, open;
-        if (child < 0) {                                          // a leaf: everybody but its occupant (project.cu:623-626, 646)
-            uint64_t self = __builtin_amdgcn_ballot_w64(occ == body32);
-            if (COMPAT) self |= __builtin_amdgcn_ballot_w64(occ == compat32);
-            takem = mask & ~self;
-            open = 0;
-        } else {                                                  // size / d < theta (project.cu:643) as thr < d2, see the header
-            const uint64_t acc = __builtin_amdgcn_ballot_w64(thr < d2);
-            takem = mask & acc;
-            open = mask & ~acc;
-        }
-        if (open != 0) {
-            if (h_idx < 0) { h_idx = child; h_mask = open; }
-            else push(child, open);
-        }
-        if (takem != 0) {
-            // M / (d2 * d):  1 / d2 = y * y,  1 / d = 1 / (sqrt(d2) + 1e-15) = y - 1e-15 y^2 to second order; added for the
-            // accepting lanes only (the others may hold inf / NaN here: a body's own leaf has d2 = 0)
-            const double y0 = __builtin_amdgcn_rsq(d2);
-            const double t = d2 * y0;
-            const double e = fma(-t, y0, 1.0);
-            const double h = y0 * e;
-            const double y = fma(h, 0.5, y0);
-            const double a = y * y;
-            const double b = fma(a, -1e-15, y);
-            const double w = (a * m) * b;
-            if ((takem >> lane) & 1ull) { sx = fma(w, dx, sx); sy = fma(w, dy, sy); }
-        }
-        if (STATS) { n_vis += __popcll(mask); ++n_wave; n_int += __popcll(takem); n_acc += takem != 0; my_int += (uint32_t)((takem >> lane) & 1ull); }
-    };
-    auto node_of = [&](const Quad64 &q, int k, double &cx, double &cy, double &m, double &thr) {
-        const w64_v16i &t = (k < 2) ? q.a : q.b;
-        const int o = (k & 1) * 8;
-        cx = w64_f64(t[o + 0], t[o + 1]); cy = w64_f64(t[o + 2], t[o + 3]);
-        m = w64_f64(t[o + 4], t[o + 5]); thr = w64_f64(t[o + 6], t[o + 7]);
-    };
-
-    // the root (node 0) alone, then quads of four siblings
-    {
-        const NodeD r = gd[0];
-        const LinkD k = ld[0];
-        h_idx = -1;
-        eval(r.cx, r.cy, r.m, r.size, k.child, k.occ, __ballot(valid));
-    }
-    int32_t na = h_idx;
-    uint64_t nam = h_mask;
-    if (ASM) {
-        if (na >= 0) walk64_asm<COMPAT, DEEP>(cg, cl, na, nam, p.x, p.y, body32, sx, sy);
-    } else {
-        for (;;) {
-            int32_t base;
-            uint64_t mask;
-            if (na >= 0) { base = na; mask = nam; }
-            else if (sp > 0) pop(base, mask);
-            else break;
-            const Quad64 q = load_quad(base);
-            if (STATS) ++n_quad;
-            h_idx = -1;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                double cx, cy, m, thr;
-                node_of(q, k, cx, cy, m, thr);
-                eval(cx, cy, m, thr, q.l[2 * k], q.l[2 * k + 1], mask);
-            }
-            na = h_idx; nam = h_mask;
-        }
-    }
-
-    // Epilogue.  Its arguments are read AGAIN from the kernarg segment through a laundered pointer: the compiler otherwise
-    // keeps the ones used here alive in SGPRs across the traversal loop -- 82 SGPRs, 7 resident waves per SIMD; at most 80
-    // is 8, and this walk answers to residency (measured, profiles/r04_f64/walk_ab.txt: 8 / 7 / 5 / 4 / 3 waves).
-    const WalkF64Args BH64_CONSTANT *ka;
-    {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-        ka = (const WalkF64Args BH64_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr();
-#pragma clang diagnostic pop
-    }
-    asm volatile("" : "+s"(ka));
-    const WalkF64Args BH64_CONSTANT &e = *ka;
-    double2 np = p;
-    if (valid) {
-        const double gm = e.G * mi;                               // (G * masses[i]) * nodeMass / d2 * d_vec / d, project.cu:651-658
-        const double fx = gm * sx, fy = gm * sy;
-        e.force_out[body] = double2{fx, fy};
-        if (e.integrate) {
-            const double ax = e.G * sx, ay = e.G * sy;            // F / m_i (updateAccVelPos, project.cu:827-834)
-            double2 v = e.vel[body];
-            v.x = fma(ax, e.dt, v.x);  v.y = fma(ay, e.dt, v.y);
-            e.vel[body] = v;
-            np.x = fma(v.x, e.dt, np.x);  np.y = fma(v.y, e.dt, np.y);
-            e.pos[body] = np;
-        }
-        if (STATS && e.body_counts) e.body_counts[body] = my_int;
-    }
-    if (e.slots) {                                                // min/max of the new positions per workgroup (next root box)
-        if (kF64Block == kWave) {
-            const double xlo = wave_min(valid ? np.x : (double)INFINITY), xhi = wave_max(valid ? np.x : -(double)INFINITY);
-            const double ylo = wave_min(valid ? np.y : (double)INFINITY), yhi = wave_max(valid ? np.y : -(double)INFINITY);
-            if (lane == 0) bounds_to_slot(xlo, xhi, ylo, yhi, e.slots, blockIdx.x);
-        } else {
-            block_bounds(valid, np.x, np.y, e.slots);
-        }
-    }
-    if (STATS && lane == 0) {
-        atomicAdd(&e.ctr->visits, n_vis);
-        atomicAdd(&e.ctr->interactions, n_int);
-        atomicAdd(&e.ctr->wave_nodes, n_wave);
-        atomicAdd(&e.ctr->wave_quads, n_quad);
-        atomicAdd(&e.ctr->wave_accepts, n_acc);
-    }
+template <bool COMPAT, bool STATS, bool DEEP = false, bool ASM = false>
+__global__ __launch_bounds__(kF64Block) void walk_f64_soft_kernel(WalkF64Args a)
+{
+    constexpr bool SOFT = true;
+#include "bh_walk_f64_body.hpp"
 }
 
 }  // namespace bh

@@ -28,7 +28,9 @@ struct WalkFastArgs {
     int64_t lo, hi;            // sorted range walked by this launch
     float G, dt;
     int integrate, to_sorted;
-    uint32_t nblocks, pad0;        // nblocks: filled by the launcher
+    uint32_t nblocks;              // filled by the launcher
+    float eps2;                    // Plummer softening: (float)(eps * eps), the product formed in fp64; 0 = none (the unsoftened
+                                   // kernels).  Added to d2 in the magnitude of an accepted term only, never in a decision.
     const void *bucket_consts;     // device block {aux, spos, smass, 0}: the assembly loop's bucket path reads its pointers here
     uint32_t *group_cost;          // per 64-body group: loop iterations of its walk (load-balancing weight), may be null
     int32_t pair_limit;            // one-wave walk: two stack entries per iteration while sp <= pair_limit

@@ -374,8 +374,10 @@ class LetStepper:
     often) raises if a LET has outgrown its block since."""
 
     def __init__(self, engine, rank: int, world: int, let_cap: int, device: torch.device | None = None,
-                 ids=None, overlap: bool = False):
+                 ids=None, overlap: bool = False, softening: float = 0.0):
         """ids: global identifiers of this rank's bodies in upload order (kept through repartition()).
+        softening: Plummer softening length of the run (engine.set_softening), a property of the whole run: it is given
+        here once, set on this rank's engine, and checked to be the same on every rank (one all_gather; ValueError if not).
         overlap: walk the local tree while the LETs are in flight (two walk launches instead of one).
         The second launch costs 15-35 us per step on one MI355X (scripts/let_emulate.py: 0.280 -> 0.301
         ms per rank at N = 1M on 8 ranks); whether the hidden all_to_all is worth more can only be
@@ -384,6 +386,25 @@ class LetStepper:
         _bind_engine_stream(engine, device)
         if ids is not None:
             engine.set_ids(ids)                       # the engine owns the ids: they migrate with the bodies
+        self.softening = float(softening)
+        every = [self.softening]
+        if dist.is_initialized() and world > 1:
+            # gathered before anything is judged, so that every rank raises together: a rank that raised alone would leave
+            # its peers waiting in the collective
+            mine = torch.tensor([self.softening], dtype=torch.float64)
+            if dist.get_backend() != "gloo":
+                mine = mine.to(device)
+            every = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            every = [float(t.item()) for t in every]
+        if not all(0.0 <= e < float("inf") for e in every):      # (a NaN fails the comparison)
+            raise ValueError(f"softening must be finite and >= 0, got {softening!r} (all ranks: {every})")
+        if any(e != self.softening for e in every):
+            raise ValueError(f"the ranks disagree on the softening length: {every} (rank {rank} has {self.softening})")
+        if hasattr(engine, "set_softening"):
+            engine.set_softening(self.softening)
+        elif self.softening != 0.0:
+            raise ValueError("this engine has no softening")
         self.cuts = None                              # OrbCuts of the last rebalance()
         self.overlap = overlap and hasattr(engine, "let_walk_local")
         # the received blocks must start at the same quad index on every rank (a sender writes links in

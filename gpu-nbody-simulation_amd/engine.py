@@ -50,6 +50,8 @@ class BhConfig:
     n_threads: int = 0              # N_THREADS, project.cu:5-7: bodies walked at a time (passes of whole workgroups); 0 = all
     flags: int = 0
     node_capacity: int = 0
+    softening: float = 0.0          # Plummer softening length (bh_set_softening); 0: the reference's unsoftened law.  Not a
+                                    # field of the C struct: applied through the setter once the context exists
 
 
 @dataclass
@@ -165,6 +167,12 @@ class BarnesHutEngine:
             raise BhError(rc, (self._lib.bh_last_error(None) or b"").decode())
         self._h = h
         self.n = 0
+        if cfg.softening != 0.0:
+            try:
+                self.set_softening(cfg.softening)
+            except BhError:
+                self.close()
+                raise
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
@@ -248,6 +256,21 @@ class BarnesHutEngine:
         c = np.zeros(max(self.n, 1), dtype=np.uint32)
         self._check(self._lib.bh_get_interaction_counts(self._h, c.ctypes.data_as(C.POINTER(C.c_uint32))))
         return c[:self.n]
+
+    # -- Plummer softening ------------------------------------------------------------------
+    def set_softening(self, eps: float) -> None:
+        """Softening length eps >= 0 of every term evaluated from now on: force G m M (dx, dy) / (d2 + eps^2)^(3/2),
+        potential -G M / sqrt(d2 + eps^2), in the force walks, the potential, the field, the direct sum and the force
+        check.  Acceptance and the self / coincident-body tests stay on the geometric distance, so the set of terms does
+        not depend on eps.  0 (the default) is the unsoftened law; Precision.F64_EXACT refuses any other value.  The
+        potential has to be recomputed after a change."""
+        self._check(self._lib.bh_set_softening(self._h, float(eps)))
+
+    @property
+    def softening(self) -> float:
+        eps = C.c_double()
+        self._check(self._lib.bh_get_softening(self._h, C.byref(eps)))
+        return eps.value
 
     # -- diagnostics ------------------------------------------------------------------------
     def potential(self, with_counts: bool = False):

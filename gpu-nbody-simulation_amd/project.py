@@ -74,7 +74,7 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      reference_compat: bool = True, out_dir: str = ".", device: int = 0,
                      positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0,
                      force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
-                     field_file: str | None = None, field_grid=None, field_box=None):
+                     field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -91,7 +91,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     field_file: after the last step, also write the Barnes-Hut field of the final state (BarnesHutEngine.field) on the
     cell-centred field_grid = (NX, NY) grid over field_box = (xmin, xmax, ymin, ymax) (None: the bounding box of the final
     positions): the line `# x,y,ax,ay,phi`, then one row per point (%.17g), y the outer axis.  Not part of
-    gpu_parallel_duration_us."""
+    gpu_parallel_duration_us.
+    softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
+    the reference's unsoftened law, the only one Precision.F64_EXACT takes."""
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -102,7 +104,7 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     gpu_parallel_us = 0.0
     with BarnesHutEngine(BhConfig(capacity=max(n, 1), theta=theta, G=g, dt=delta_t, max_depth=max_depth,
                                   precision=precision, reference_compat=reference_compat,
-                                  device=device, n_threads=n_threads)) as eng:
+                                  device=device, n_threads=n_threads, softening=softening)) as eng:
         eng.upload(positions, velocities, masses)
         traj = None
         absolute_t = 0.0
@@ -257,6 +259,9 @@ def _parse(argv):
     ap.add_argument("--max-depth", type=int, default=QUADTREE_MAX_DEPTH)
     ap.add_argument("--theta", type=float, default=THETA)
     ap.add_argument("--no-compat", action="store_true", help="bucket leaves instead of the depth-cap artefact")
+    ap.add_argument("--softening", type=float, default=None, metavar="EPS",
+                    help="Plummer softening length of the forces and diagnostics (needs --precision f32: the default "
+                         "precision reproduces the reference bit for bit, and the reference has no softening)")
     ap.add_argument("-o", dest="ignored_output", help="accepted and ignored (nvcc line compatibility)")
     ap.add_argument("source", nargs="?", help="accepted and ignored (nvcc line compatibility)")
     a = ap.parse_args(argv)
@@ -264,6 +269,12 @@ def _parse(argv):
         ap.error("--field-file and --field-grid go together")
     if a.field_box is not None and a.field_file is None:
         ap.error("--field-box needs --field-file")
+    if a.softening is not None:
+        if not (a.softening >= 0.0 and a.softening < float("inf")):
+            ap.error("--softening: the length must be finite and >= 0")
+        if a.softening != 0.0 and a.precision == "f64":
+            ap.error("--softening needs --precision f32: --precision f64 reproduces the reference's results bit for bit, "
+                     "and the reference has no softening")
     # project.cu:1-11.  N_THREADS: the reference's default is 1,024 CUDA threads striding over the bodies; here it
     # caps the bodies walked at a time ONLY when given (-DN_THREADS=... / --n-threads, as the scaling scripts do):
     # unset, a step walks all bodies in one launch.
@@ -318,7 +329,8 @@ def main(argv=None) -> int:
         precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32,
         reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
         energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
-        force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box)
+        force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box,
+        softening=a.softening or 0.0)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

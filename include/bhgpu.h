@@ -307,6 +307,34 @@ int bh_force_check(bh_ctx *ctx, const int64_t *targets, int64_t n_targets, doubl
  * Device buffers for one launch are allocated on first use (bh_stats.device_bytes grows then). */
 int bh_field_at(bh_ctx *ctx, const double *points, int64_t n_points, double *accel, double *phi, uint32_t *counts);
 
+/* --- Plummer softening (opt-in; additive entry points, the ABI version stays 4) -----------------------
+ * bh_set_softening: a softening length eps >= 0 for every term the context evaluates from then on; 0 (the default) is
+ * the reference's unsoftened law, and every launch then takes the kernels it has always taken.  With d2 = dx^2 + dy^2
+ * the geometric squared distance a walk computes and s2 = d2 + eps^2:
+ *   decisions stay on d2 -- the acceptance compare, the fp32 leaf test d2 > 0 (the body itself or an exactly coincident
+ *     body contributes nothing), the `mass <= 1e-15` cut-off, the self skip by index.  The term set, and so every
+ *     per-body interaction and term count, is the same for any eps on the same state;
+ *   only the magnitude of an accepted term uses s2: force G m_i M (dx, dy) / s2^(3/2), potential -G M / sqrt(s2).
+ *   BH_PRECISION_F32 / MIXED (force walk, bucket leaves body by body, forest walk, potential, field): eps2 =
+ *     (float)(eps * eps), the product formed in fp64; ri = rsq(d2 + eps2), one fp32 add, then w = m ri ri ri, w dx, w dy,
+ *     m ri as before.  An eps2 that rounds to 0.f runs the unsoftened kernels.
+ *   BH_PRECISION_F64 (force walk): s2 = d2 + eps * eps, one fp64 add, then the walk's sequence on s2: y = 1 / sqrt(s2) by
+ *     the reciprocal square root and one Newton step, 1 / s2 = y^2, 1 / d = y - 1e-15 y^2 (the 1e-15 offset stays, so
+ *     eps -> 0 is continuous with the unsoftened walk).
+ *   fp64 potential and field: d = sqrt(s2) + 1e-15, a += ((G M) / s2) * (dx / d), phi -= (G M) / d, IEEE sqrt and
+ *     division (BH_FLAG_WALK_PORTABLE nodes: size / d < theta keeps the geometric d).
+ *   bh_direct_forces, and so bh_force_check: d = sqrt(s2), ((G m_i) m_j) / (s2 d), same order, j == i skipped by index;
+ *     distinct coincident bodies give a finite zero force.
+ *   BH_PRECISION_F64_EXACT: its contract is the reference's bits and the reference has no softening -- eps != 0 is
+ *     BH_ERR_ARG there (eps = 0 is accepted).
+ * May be called at any time between calls and takes effect at the next walk; it marks the potential as not current
+ * (bh_get_potential / bh_let_get_potential return BH_ERR_STATE until it is recomputed).  In a distributed run eps is a
+ * property of the run: the caller gives every rank's context the same value.
+ * BH_ERR_ARG: eps negative or not finite, or eps != 0 in BH_PRECISION_F64_EXACT.
+ * bh_get_softening: the length last set (0 by default). */
+int bh_set_softening(bh_ctx *ctx, double eps);
+int bh_get_softening(bh_ctx *ctx, double *eps);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
