@@ -711,7 +711,7 @@ int launch_walk_f32(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
     a.state64 = c->state64() ? 1 : 0;             // mixed precision: pos/vel point at double2 arrays
     a.sstate = c->sstate;
     a.acc_out = (float2 *)c->force; a.ctr = c->ctr;
-    a.lo = w.lo; a.hi = w.hi; a.G = (float)c->cfg.G; a.dt = (float)c->cfg.dt;
+    a.lo = w.lo; a.hi = w.hi; a.G = (float)c->cfg.G; a.dt = (float)c->cfg.dt; a.dt64 = c->cfg.dt;
     a.integrate = w.integrate ? 1 : 0; a.to_sorted = w.to_sorted ? 1 : 0;
     a.n_trees = c->let_mode ? c->world : 0; a.self_rank = c->let_mode ? c->rank : -1;
     a.part = w.part; a.acc_part = c->acc_part;

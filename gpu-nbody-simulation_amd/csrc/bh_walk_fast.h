@@ -49,6 +49,8 @@ struct WalkFastArgs {
     double *slots;                 // bh_bounds.hpp: bounds records the new positions fold into (next root box), may be null
     uint32_t *body_counts;         // counting variant (BH_FLAG_WALK_STATS): accepted force evaluations per body, added
                                    // atomically at the body's device slot (the engine zeroes it); may be null
+    double dt64;                   // the time step unrounded: what the state64 (mixed precision) epilogue integrates with.  LAST, so
+                                   // that nothing ahead of it moves (the assembly loops load their arguments by offset)
 };
 
 // split: 1 = one wave per 64 bodies; 2/4/8 = that many waves share each 64-body group (few bodies; more than 8 -> 8).

@@ -349,13 +349,13 @@
         if (e.acc_out) e.acc_out[body] = float2{gx, gy};
         if (e.integrate && e.state64) {
             // mixed precision: the fp32 acceleration advances the fp64 state (updateAccVelPos,
-            // project.cu:819-836, in the state's precision)
+            // project.cu:819-836, in the state's precision) with the fp64 time step
             double2 *pos64 = reinterpret_cast<double2 *>(e.pos), *vel64 = reinterpret_cast<double2 *>(e.vel);
             double2 v = vel64[body];
             const double2 q = pos64[body];
-            v.x = fma((double)gx, (double)e.dt, v.x);
-            v.y = fma((double)gy, (double)e.dt, v.y);
-            np64 = double2{fma(v.x, (double)e.dt, q.x), fma(v.y, (double)e.dt, q.y)};
+            v.x = fma((double)gx, e.dt64, v.x);
+            v.y = fma((double)gy, e.dt64, v.y);
+            np64 = double2{fma(v.x, e.dt64, q.x), fma(v.y, e.dt64, q.y)};
             vel64[body] = v;
             pos64[body] = np64;
         } else if (e.integrate) {
