@@ -66,6 +66,10 @@ class bh_energy_t(C.Structure):
     ]
 
 
+class bh_timestep_t(C.Structure):
+    _fields_ = [("dt", C.c_double), ("a_max", C.c_double), ("worst", C.c_int64), ("n_bodies", C.c_int64)]
+
+
 ORB_BINS = 4096
 ORB_MAX_CUTS = 63
 
@@ -110,6 +114,10 @@ SIGNATURES = {
     "bh_field_at": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_uint32)]),
     "bh_set_softening": (C.c_int, [_ctx, C.c_double]),
     "bh_get_softening": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
+    "bh_kick": (C.c_int, [_ctx, C.c_double]),
+    "bh_drift": (C.c_int, [_ctx, C.c_double]),
+    "bh_timestep": (C.c_int, [_ctx, C.c_double, C.c_double, C.POINTER(bh_timestep_t)]),
+    "bh_step_kdk": (C.c_int, [_ctx, C.c_int32]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

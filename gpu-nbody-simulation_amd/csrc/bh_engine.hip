@@ -23,6 +23,7 @@
 #include "bh_init.hpp"
 #include "bh_let.hpp"
 #include "bh_migrate.hpp"
+#include "bh_split.hpp"
 #include "bh_walk_fast.h"
 
 using namespace bh;
@@ -148,6 +149,11 @@ struct bh_ctx {
     uint32_t *phi_counts = nullptr;
     double *diag_part = nullptr, *diag_out = nullptr, *slots_save = nullptr;
     bool phi_current = false;           // phi holds the potential of the current state
+    // the split operators (bh_split.hpp): the force buffer holds the accelerations (fp64 tree: the forces) of the CURRENT
+    // positions of ALL bodies, slot for slot -- set by bh_compute_forces and bh_step_kdk, cleared by whatever moves or
+    // re-orders the bodies or changes the law; the records of bh_timestep are allocated on first use
+    bool forces_current = false;
+    TsRecord *ts_part = nullptr, *ts_out = nullptr;
     // LET mode: the quiet builds of the distributed diagnostics (bh_let_bounds_quiet, bh_let_build_quiet)
     bool let_moved = false;             // an integrating walk has moved the bodies since the last bh_let_build
     uint32_t *perm_save = nullptr;      // allocated on first use: the permutation of the last force walk's build
@@ -772,7 +778,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     if (full && c->let_mode) w.partial = c->partial;
     const bool want_slots = full && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
     if (want_slots) { clean_slots(c); w.slots = c->bslots; }
-    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; c->let_moved = true; }    // (the positions change)
+    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; c->let_moved = true; c->forces_current = false; }    // (the positions change)
 
     const WalkChoice k = choose_walk(c, w);
     if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
@@ -811,6 +817,7 @@ void forget_body_set(bh_ctx *c)
     c->partial_count = 0; c->slots_valid = false;
     c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
     c->phi_current = false;
+    c->forces_current = false;
     c->tree_valid = false;
     c->orig_identity = true;
     c->builds = 0;
@@ -831,6 +838,9 @@ int new_bodies(bh_ctx *c, int64_t n)
     }
     return BH_OK;
 }
+
+// a non-integrating walk of this context covers every body (one GPU; a LET context and a rank of the replicated scheme do not)
+bool forces_cover_all(const bh_ctx *c) { return !c->let_mode && c->world == 1; }
 
 }  // namespace
 
@@ -991,6 +1001,7 @@ int bh_set_softening(bh_ctx *c, double eps)
                                    "reference has no softening -- use BH_PRECISION_F64, MIXED or F32 for a softened run");
     const double eps2 = eps * eps;
     if (!std::isfinite(eps2)) return fail(c, BH_ERR_ARG, "bh_set_softening: the square of the softening length overflows");
+    if (eps != c->eps) c->forces_current = false;             // the force buffer holds the forces of another law
     c->eps = eps;
     c->eps2 = eps2;
     c->eps2f = (float)eps2;             // (0.f for a tiny eps: the fp32 walks then run their unsoftened kernels)
@@ -1146,6 +1157,7 @@ int bh_build_tree(bh_ctx *c)
     if (!c) return BH_ERR_ARG;
     if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_build_tree before bh_upload");
     BH_HIP(c, hipSetDevice(c->device));
+    c->forces_current = false;               // (a build that is not quiet: no force walk follows it)
     int rc = enqueue_build(c);
     if (rc) return rc;
     return check_overflow(c);
@@ -1156,11 +1168,51 @@ int bh_compute_forces(bh_ctx *c)
     if (!c) return BH_ERR_ARG;
     if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_compute_forces before bh_upload");
     BH_HIP(c, hipSetDevice(c->device));
+    c->forces_current = false;
     int rc = enqueue_build(c);
     if (rc) return rc;
     rc = enqueue_walk(c, false, false);
     if (rc) return rc;
-    return check_overflow(c);
+    rc = check_overflow(c);
+    c->forces_current = rc == BH_OK && forces_cover_all(c);
+    return rc;
+}
+
+// the events of a batch of `nsteps` timed steps: one pair per step around the walk kernel (bounded pool); returns how many
+// steps get a pair through *want
+static int step_events(bh_ctx *c, int32_t nsteps, int *want)
+{
+    *want = std::min<int>(nsteps, 4096);
+    while ((int)c->ev.size() < 2 * *want) {
+        hipEvent_t e;
+        BH_HIP(c, hipEventCreate(&e));
+        c->ev.push_back(e);
+    }
+    return BH_OK;
+}
+
+// step s of a batch of nsteps: the build and the walk with their events (the last step's build carries the group times)
+static int enqueue_timed_step(bh_ctx *c, int s, int nsteps, int want, bool integrate)
+{
+    if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[0], c->stream));
+    c->time_groups = (s == nsteps - 1);
+    int rc = enqueue_build(c);
+    c->time_groups = false;
+    if (rc) return rc;
+    if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[1], c->stream));
+    if (s < want) BH_HIP(c, hipEventRecord(c->ev[2 * s], c->stream));
+    rc = enqueue_walk(c, integrate, false);
+    if (rc) return rc;
+    if (s < want) BH_HIP(c, hipEventRecord(c->ev[2 * s + 1], c->stream));
+    return BH_OK;
+}
+
+static void steps_enqueued(bh_ctx *c, int32_t nsteps, int want)
+{
+    c->steps_done += nsteps;
+    c->last_nsteps = nsteps;
+    c->timed_pairs = want;
+    c->step_timed = nsteps > 0;
 }
 
 int bh_step(bh_ctx *c, int32_t nsteps)
@@ -1168,31 +1220,167 @@ int bh_step(bh_ctx *c, int32_t nsteps)
     if (!c || nsteps < 0) return BH_ERR_ARG;
     if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_step before bh_upload");
     BH_HIP(c, hipSetDevice(c->device));
-    // one event pair per step around the walk kernel (bounded pool)
-    const int want = std::min<int>(nsteps, 4096);
-    while ((int)c->ev.size() < 2 * want) {
-        hipEvent_t e;
-        BH_HIP(c, hipEventCreate(&e));
-        c->ev.push_back(e);
-    }
+    int want = 0;
+    if (int rc = step_events(c, nsteps, &want)) return rc;
     BH_HIP(c, hipEventRecord(c->ev_step[0], c->stream));
-    for (int s = 0; s < nsteps; ++s) {
-        if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[0], c->stream));
-        c->time_groups = (s == nsteps - 1);
-        int rc = enqueue_build(c);
-        c->time_groups = false;
-        if (rc) return rc;
-        if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[1], c->stream));
-        if (s < want) BH_HIP(c, hipEventRecord(c->ev[2 * s], c->stream));
-        rc = enqueue_walk(c, true, false);
-        if (rc) return rc;
-        if (s < want) BH_HIP(c, hipEventRecord(c->ev[2 * s + 1], c->stream));
-    }
+    for (int s = 0; s < nsteps; ++s)
+        if (int rc = enqueue_timed_step(c, s, nsteps, want, true)) return rc;
     BH_HIP(c, hipEventRecord(c->ev_step[1], c->stream));
-    c->steps_done += nsteps;
-    c->last_nsteps = nsteps;
-    c->timed_pairs = want;
-    c->step_timed = nsteps > 0;
+    steps_enqueued(c, nsteps, want);
+    return BH_OK;
+}
+
+// ---- the split operators (bh_split.hpp): kick, drift, the time-step criterion, and the leapfrog built from them
+static int split_check(bh_ctx *c, const char *what)
+{
+    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(what) + " before bh_upload");
+    if (c->let_mode || c->world > 1)
+        return fail(c, BH_ERR_STATE, std::string(what) + ": single GPU only (not in LET mode or with world > 1)");
+    return BH_OK;
+}
+
+static int need_forces(bh_ctx *c, const char *what)
+{
+    if (c->forces_current) return BH_OK;
+    return fail(c, BH_ERR_STATE, std::string(what) + ": the force buffer does not hold the accelerations of the current positions "
+                                 "(bh_compute_forces first; a step, bh_drift, bh_upload, bh_build_tree and a new softening length outdate them)");
+}
+
+// v += a h on the force buffer; h == 0 launches nothing
+static int enqueue_kick(bh_ctx *c, double h)
+{
+    const int64_t n = c->n;
+    if (n == 0 || h == 0.0) return BH_OK;
+    const dim3 grid(blocks_for(n, kBlock)), block(kBlock);
+    switch (c->mode) {
+    case Mode::F32:
+        hipLaunchKernelGGL(kick_f32_kernel, grid, block, 0, c->stream, (const float2 *)c->force, (float2 *)c->vel, n, (float)h);
+        break;
+    case Mode::Mixed:
+        hipLaunchKernelGGL(kick_mixed_kernel, grid, block, 0, c->stream, (const float2 *)c->force, (double2 *)c->vel, n, h);
+        break;
+    case Mode::F64:
+        hipLaunchKernelGGL(kick_f64_kernel, grid, block, 0, c->stream, (const double2 *)c->force, (const double *)c->mass,
+                           (double2 *)c->vel, n, h);
+        break;
+    case Mode::Exact:
+        hipLaunchKernelGGL(kick_exact_kernel, grid, block, 0, c->stream, (const double2 *)c->force, (const double *)c->mass,
+                           (double2 *)c->vel, n, h);
+        break;
+    }
+    BH_HIP(c, hipGetLastError());
+    return BH_OK;
+}
+
+// p += v h; whatever describes the old positions stops being current.  The bounds are NOT folded here: the next build takes
+// its root box from bounds_partial (slots_valid = false).
+static int enqueue_drift(bh_ctx *c, double h)
+{
+    const int64_t n = c->n;
+    c->forces_current = false;
+    c->phi_current = false;
+    c->tree_valid = false;
+    c->slots_valid = false;
+    if (n == 0 || h == 0.0) return BH_OK;
+    const dim3 grid(blocks_for(n, kBlock)), block(kBlock);
+    switch (c->mode) {
+    case Mode::F32:
+        hipLaunchKernelGGL(drift_f32_kernel, grid, block, 0, c->stream, (const float2 *)c->vel, (float2 *)c->pos, n, (float)h);
+        break;
+    case Mode::Mixed:
+    case Mode::F64:
+        hipLaunchKernelGGL(drift_f64_kernel, grid, block, 0, c->stream, (const double2 *)c->vel, (double2 *)c->pos, n, h);
+        break;
+    case Mode::Exact:
+        hipLaunchKernelGGL(drift_exact_kernel, grid, block, 0, c->stream, (const double2 *)c->vel, (double2 *)c->pos, n, h);
+        break;
+    }
+    BH_HIP(c, hipGetLastError());
+    return BH_OK;
+}
+
+int bh_kick(bh_ctx *c, double h)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!std::isfinite(h)) return fail(c, BH_ERR_ARG, "bh_kick: h must be finite");
+    if (int rc = split_check(c, "bh_kick")) return rc;
+    if (int rc = need_forces(c, "bh_kick")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    return enqueue_kick(c, h);
+}
+
+int bh_drift(bh_ctx *c, double h)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!std::isfinite(h)) return fail(c, BH_ERR_ARG, "bh_drift: h must be finite");
+    if (int rc = split_check(c, "bh_drift")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    return enqueue_drift(c, h);
+}
+
+int bh_timestep(bh_ctx *c, double eta, double length, bh_timestep_t *out)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!out) return fail(c, BH_ERR_ARG, "bh_timestep: null output");
+    if (!std::isfinite(eta) || std::isnan(length)) return fail(c, BH_ERR_ARG, "bh_timestep: eta must be finite (and length a number)");
+    if (int rc = split_check(c, "bh_timestep")) return rc;
+    if (!(length > 0.0)) length = c->eps;                      // "use the softening length"
+    if (!(length > 0.0) || !std::isfinite(length))
+        return fail(c, BH_ERR_ARG, "bh_timestep: needs a finite length > 0, or a softening length to take its place");
+    if (int rc = need_forces(c, "bh_timestep")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (!c->ts_part) {
+        int rc = dev_alloc(c, &c->ts_part, (size_t)kTsParts);
+        if (!rc) rc = dev_alloc(c, &c->ts_out, 1);
+        if (rc) { dev_free(c, c->ts_part); dev_free(c, c->ts_out); c->ts_part = c->ts_out = nullptr; return rc; }
+    }
+    const uint32_t *orig = (c->tree64() || c->orig_identity) ? nullptr : c->orig;
+    if (c->tree64())
+        hipLaunchKernelGGL((timestep_partial_kernel<double2>), dim3(kTsParts), dim3(kBlock), 0, c->stream, (const double2 *)c->force,
+                           (const double *)c->mass, orig, c->n, c->ts_part);
+    else
+        hipLaunchKernelGGL((timestep_partial_kernel<float2>), dim3(kTsParts), dim3(kBlock), 0, c->stream, (const float2 *)c->force,
+                           (const double *)nullptr, orig, c->n, c->ts_part);
+    hipLaunchKernelGGL(timestep_final_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->ts_part, c->ts_out);
+    BH_HIP(c, hipGetLastError());
+    TsRecord r{};
+    BH_HIP(c, hipMemcpyAsync(&r, c->ts_out, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    bh_timestep_t t{};
+    t.n_bodies = c->n;
+    if (r.a2 < 0.0) { t.a_max = 0.0; t.worst = -1; }           // no bodies
+    else { t.a_max = std::sqrt(r.a2); t.worst = r.index; }
+    t.dt = t.a_max == 0.0 ? (double)INFINITY : std::isinf(t.a_max) ? 0.0 : eta * std::sqrt(length / t.a_max);
+    *out = t;
+    return BH_OK;
+}
+
+// nsteps of kick-drift-kick at cfg.dt.  Between two drifts the two half kicks of neighbouring steps are one whole kick on
+// the same forces, and a whole kick followed by the drift is the fused epilogue: so the inner nsteps - 1 steps ARE bh_step's
+// (same kernels, same batch), between an opening half kick + drift and a closing force walk + half kick.
+int bh_step_kdk(bh_ctx *c, int32_t nsteps)
+{
+    if (!c || nsteps < 0) return BH_ERR_ARG;
+    if (int rc = split_check(c, "bh_step_kdk")) return rc;
+    if (nsteps == 0) return BH_OK;
+    BH_HIP(c, hipSetDevice(c->device));
+    const double dt = c->cfg.dt;
+    int want = 0;
+    if (int rc = step_events(c, nsteps, &want)) return rc;
+    BH_HIP(c, hipEventRecord(c->ev_step[0], c->stream));
+    if (!c->forces_current) {                                  // (else: the closing forces of the previous call)
+        int rc = enqueue_build(c);
+        if (!rc) rc = enqueue_walk(c, false, false);
+        if (rc) return rc;
+    }
+    if (int rc = enqueue_kick(c, 0.5 * dt)) return rc;
+    if (int rc = enqueue_drift(c, dt)) return rc;
+    for (int s = 0; s < nsteps; ++s)                           // the last one is the closing force walk
+        if (int rc = enqueue_timed_step(c, s, nsteps, want, s < nsteps - 1)) return rc;
+    if (int rc = enqueue_kick(c, 0.5 * dt)) return rc;
+    BH_HIP(c, hipEventRecord(c->ev_step[1], c->stream));
+    steps_enqueued(c, nsteps, want);
+    c->forces_current = forces_cover_all(c);
     return BH_OK;
 }
 
@@ -1878,7 +2066,7 @@ int bh_scatter_sorted(bh_ctx *c)
                            c->perm, c->sstate, (float2 *)c->pos, (float2 *)c->vel, c->n);
         BH_HIP(c, hipGetLastError());
     }
-    c->slots_valid = false; c->phi_current = false;
+    c->slots_valid = false; c->phi_current = false; c->forces_current = false;
     c->steps_done += 1;
     return BH_OK;
 }

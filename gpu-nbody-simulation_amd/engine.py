@@ -96,6 +96,15 @@ class BhEnergy:
 
 
 @dataclass
+class BhTimestep:
+    """bh_timestep_t: the criterion dt = eta * sqrt(length / a_max) over the accelerations of the last compute_forces()."""
+    dt: float
+    a_max: float                 # the largest |a| (inf when some acceleration is not finite; dt is 0 then)
+    worst: int                   # caller index of the body that has it (-1: no bodies)
+    n_bodies: int
+
+
+@dataclass
 class BhForceError:
     """Relative Barnes-Hut force error rel_i = |F_tree - F_dir| / |F_dir| over a set of bodies (force_error_stats)."""
     n: int                       # bodies in the statistics
@@ -233,6 +242,56 @@ class BarnesHutEngine:
 
     def sync(self) -> None:
         self._check(self._lib.bh_sync(self._h))
+
+    # -- kick, drift, time-step criterion, leapfrog ---------------------------------------------
+    def kick(self, h: float) -> None:
+        """v += a h from the accelerations of the last compute_forces() (BhError -5 when they are not those of the
+        current positions).  The arithmetic per precision: include/bhgpu.h."""
+        self._check(self._lib.bh_kick(self._h, float(h)))
+
+    def drift(self, h: float) -> None:
+        """p += v h.  The forces, the potential and the tree stop being current."""
+        self._check(self._lib.bh_drift(self._h, float(h)))
+
+    def timestep(self, eta: float, length: float | None = None) -> BhTimestep:
+        """dt = eta * sqrt(length / a_max) over the accelerations of the last compute_forces(), reduced on the device;
+        length None: the softening length."""
+        t = _lib.bh_timestep_t()
+        self._check(self._lib.bh_timestep(self._h, float(eta), 0.0 if length is None else float(length), C.byref(t)))
+        return BhTimestep(t.dt, t.a_max, t.worst, t.n_bodies)
+
+    def step_kdk(self, nsteps: int = 1) -> None:
+        """nsteps kick-drift-kick leapfrog steps at cfg.dt: velocities and positions are synchronised on return, and the
+        closing forces serve the next call.  nsteps + 1 walks (nsteps when the forces were current)."""
+        self._check(self._lib.bh_step_kdk(self._h, nsteps))
+
+    def step_adaptive(self, t_end: float, eta: float, length: float | None = None, dt_max: float | None = None,
+                      t: float = 0.0):
+        """Kick-drift-kick steps with dt = min(timestep(eta, length).dt, dt_max, t_end - t) chosen anew before every step,
+        from t until t == t_end exactly.  Returns (t, steps).  Raises BhError when a step comes out 0 or not finite
+        (coincident bodies; no acceleration at all and no dt_max)."""
+        t, t_end, steps = float(t), float(t_end), 0
+        while t < t_end:
+            try:
+                ts = self.timestep(eta, length)
+            except BhError as e:
+                if e.code != -5:
+                    raise
+                self._check(self._lib.bh_compute_forces(self._h))       # the forces were not current
+                ts = self.timestep(eta, length)
+            dt = ts.dt if dt_max is None else min(ts.dt, float(dt_max))
+            last = not (dt < t_end - t)
+            if last:
+                dt = t_end - t
+            if not (dt > 0.0 and dt < float("inf")):
+                raise BhError(-1, f"step_adaptive: time step {dt!r} at t = {t!r} (a_max = {ts.a_max!r}, body {ts.worst})")
+            self.kick(0.5 * dt)
+            self.drift(dt)
+            self._check(self._lib.bh_compute_forces(self._h))
+            self.kick(0.5 * dt)
+            t = t_end if last else t + dt
+            steps += 1
+        return t, steps
 
     def build_tree(self) -> None:
         self._check(self._lib.bh_build_tree(self._h))

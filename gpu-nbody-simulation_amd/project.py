@@ -74,7 +74,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      reference_compat: bool = True, out_dir: str = ".", device: int = 0,
                      positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0,
                      force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
-                     field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0):
+                     field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0,
+                     integrator: str = "euler"):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -93,7 +94,12 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     positions): the line `# x,y,ax,ay,phi`, then one row per point (%.17g), y the outer axis.  Not part of
     gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
-    the reference's unsoftened law, the only one Precision.F64_EXACT takes."""
+    the reference's unsoftened law, the only one Precision.F64_EXACT takes.
+    integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
+    outputs as one BarnesHutEngine.step_kdk, so every line of the energy, force-error and positions files, and the state
+    returned, has velocities and positions at the same time."""
+    if integrator not in ("euler", "kdk"):
+        raise ValueError("integrator must be 'euler' or 'kdk'")
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -137,16 +143,18 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         if ferr is not None:
             samplers.append((force_error_every, sample_force_error))
 
+        advance_engine = eng.step if integrator == "euler" else eng.step_kdk
+
         def steps(k):
             nonlocal gpu_parallel_us, absolute_t
             if k <= 0:
                 return
             if traj is None:
-                eng.step(k)
+                advance_engine(k)
                 gpu_parallel_us += eng.stats().last_step_ms * k * 1e3
                 return
             for _ in range(k):
-                eng.step(1)
+                advance_engine(1)
                 gpu_parallel_us += eng.stats().last_step_ms * 1e3
                 absolute_t += delta_t
                 _write_frame(traj, absolute_t, eng.download()[0])
@@ -262,6 +270,9 @@ def _parse(argv):
     ap.add_argument("--softening", type=float, default=None, metavar="EPS",
                     help="Plummer softening length of the forces and diagnostics (needs --precision f32: the default "
                          "precision reproduces the reference bit for bit, and the reference has no softening)")
+    ap.add_argument("--integrator", choices=["euler", "kdk"], default="euler",
+                    help="euler: the reference's fused kick-drift; kdk: synchronised kick-drift-kick leapfrog, one "
+                         "step_kdk per batch between two outputs")
     ap.add_argument("-o", dest="ignored_output", help="accepted and ignored (nvcc line compatibility)")
     ap.add_argument("source", nargs="?", help="accepted and ignored (nvcc line compatibility)")
     a = ap.parse_args(argv)
@@ -330,7 +341,7 @@ def main(argv=None) -> int:
         reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
         energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
         force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box,
-        softening=a.softening or 0.0)
+        softening=a.softening or 0.0, integrator=a.integrator)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -335,6 +335,63 @@ int bh_field_at(bh_ctx *ctx, const double *points, int64_t n_points, double *acc
 int bh_set_softening(bh_ctx *ctx, double eps);
 int bh_get_softening(bh_ctx *ctx, double *eps);
 
+/* --- kick, drift, a time-step criterion and the KDK leapfrog (opt-in; additive entry points, the ABI version stays 4) ---
+ * bh_step advances the state by the reference's fused kick-drift at cfg.dt (updateAccVelPos, project.cu:819-836:
+ * v += a dt; p += v dt, symplectic Euler): first order, and the velocities a download returns sit half a step away from the
+ * positions.  These entry points advance velocities and positions SEPARATELY, from the forces the device already holds.
+ * "The forces are current" below means: the force buffer holds the accelerations of the current positions of all bodies.
+ *   That is so after a completed bh_compute_forces (whatever n_threads) and after bh_step_kdk.  It stops being so at any
+ *   integrating walk (bh_step, bh_step_local), bh_drift, bh_upload, bh_initialize, bh_migrate_unpack, a bh_set_softening
+ *   that changes the length, and bh_build_tree (a build that may re-order the state without a force walk after it).
+ *   bh_kick keeps it (the positions do not move), and so do the diagnostics -- bh_energy, bh_compute_potential,
+ *   bh_field_at, bh_direct_forces, bh_force_check: they leave the force buffer and the device order alone.
+ * bh_kick: v += a h for every body, a the acceleration in the force buffer.  One lane per device slot.
+ *   BH_PRECISION_F32:       v' = fma32(a, (float)h, v), a the fp32 acceleration the walk wrote.
+ *   BH_PRECISION_MIXED:     v' = fma64((double)a32, h, v), the fp64 h unrounded.
+ *   BH_PRECISION_F64:       a = F / m_i, one IEEE division (the buffer holds the force (G m_i) * sum), v' = fma64(a, h, v).
+ *   BH_PRECISION_F64_EXACT: a = F / m_i, v' = v + a * h, unfused: updateAccelerations and updateVelocities
+ *                           (project.cu:795-809) in their order.
+ *   In the two fp64 precisions a body of mass exactly 0 gets a = 0 / 0, a NaN velocity, as in the reference.
+ *   The potential stays current (it does not depend on the velocities).
+ * bh_drift: p += v h.  F32: p' = fma32(v, (float)h, p); MIXED and F64: p' = fma64(v, h, p); F64_EXACT: p' = p + v * h,
+ *   unfused.  The forces and the potential stop being current, the tree is invalid until the next build, and that build
+ *   takes its root box from a pass over the positions (the drift folds no bounds).
+ * Both: any finite h is valid, negative included; h = 0 launches nothing and leaves the arrays bit for bit as they were
+ *   (bh_drift's state rules apply all the same).  The arithmetic is per body and does not depend on the device
+ *   order.  bh_compute_forces, bh_kick(dt), bh_drift(dt) is bit for bit bh_step(1) in F32,
+ *   MIXED and F64_EXACT; in F64 the fused step uses a = G * sum where the kick divides (G m_i) * sum by m_i (equal when
+ *   the division is exact, e.g. masses that are powers of two).
+ * bh_timestep: the criterion dt = eta * sqrt(length / a_max) over the same accelerations, reduced on the device.  Per body
+ *   a2 = ax^2 + ay^2 in fp64 (fp32 accelerations widened first; fp64 precisions: a = F / m_i); a_max = sqrt(max a2); worst =
+ *   the caller index of the maximum, the smallest such index on a tie.  length <= 0: the softening length (BH_ERR_ARG if
+ *   that is 0 too).  A non-finite a2 (coincident bodies, a massless body in an fp64 precision) gives a_max = +inf, dt = 0 and
+ *   worst = the smallest caller index with a non-finite a2; a_max == 0 gives dt = +inf; no bodies: a_max = 0, dt = +inf,
+ *   worst = -1.  The maximum does not depend on the order of the reduction: two calls return the same bits.  Only the result
+ *   words reach the host; the call waits for the stream.
+ * bh_step_kdk: nsteps kick-drift-kick (leapfrog) steps at cfg.dt, asynchronous like bh_step:
+ *     forces of the current state (skipped when they are current), bh_kick(dt/2), bh_drift(dt);
+ *     nsteps - 1 fused steps -- the body of bh_step, the same kernels in the same batch: between two drifts the two half
+ *       kicks are one whole kick on the same forces;
+ *     forces, bh_kick(dt/2).
+ *   On return velocities and positions are at the same time, so bh_energy is second order in dt; the forces are current,
+ *   so a following bh_step_kdk costs nsteps walks, not nsteps + 1; steps_done advances by nsteps; bh_stats' step timings
+ *   describe the call (last_step_ms = the whole call / nsteps, the per-step records end at each force walk).  nsteps = 0 is a
+ *   no-op.  All four precisions; in BH_PRECISION_F64_EXACT every operation is the reference's, but the reference has no
+ *   leapfrog, so there are no reference bits to match.  A tree that outgrows node_capacity is reported by bh_sync, as
+ *   for bh_step.
+ * Errors: BH_ERR_ARG for a null context or output, a non-finite h or eta, nsteps < 0.  BH_ERR_STATE before upload, in LET
+ *   mode and with world > 1 (all four), and for bh_kick / bh_timestep when the forces are not current.  n = 0 is valid. */
+typedef struct bh_timestep_t {
+    double  dt;          /* eta * sqrt(length / a_max)                                       */
+    double  a_max;       /* the largest |a|                                                  */
+    int64_t worst;       /* caller index of the body that has it (-1: no bodies)             */
+    int64_t n_bodies;
+} bh_timestep_t;
+int bh_kick(bh_ctx *ctx, double h);
+int bh_drift(bh_ctx *ctx, double h);
+int bh_timestep(bh_ctx *ctx, double eta, double length, bh_timestep_t *out);
+int bh_step_kdk(bh_ctx *ctx, int32_t nsteps);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
