@@ -25,6 +25,7 @@
 #include "bh_migrate.hpp"
 #include "bh_split.hpp"
 #include "bh_walk_fast.h"
+#include "bh_run_state.hpp"
 
 using namespace bh;
 
@@ -40,18 +41,9 @@ struct ExpHooks {
 };
 #endif
 
-namespace {
+static thread_local std::string g_create_error;
 
-thread_local std::string g_create_error;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-}  // namespace
-
-struct bh_ctx {
+struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_state.hpp)
     bh_config cfg{};
     int Dm = 0;
     // cfg.precision: BH_PRECISION_F64_EXACT, BH_PRECISION_F64 (the exact mode's tree and state, the throughput walk of
@@ -71,7 +63,6 @@ struct bh_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int64_t n = 0;
-    bool uploaded = false, tree_valid = false;
     int64_t internal_cap = 0, node_cap = 0;
     int64_t bfs_max = 12288;       // bit-exact walk: one wavefront per body (walk_exact_bfs_kernel) for launches up to here (BH_EXACT_BFS_MAX;
                                    // walk ms against the cooperative walk: 0.021 / 0.072 at N = 1,024, 0.042 / 0.108 at 4,096, 0.126 / 0.223
@@ -81,16 +72,11 @@ struct bh_ctx {
     bool walk_asm = true;          // BH_WALK_ASM=0: the C++ loop everywhere (A/B)
     int sort_bucket = 1;           // 1: bucket sort when the previous build's sorted positions are this body set's
                                    // (BH_SORT_BUCKET=0: always the LSD passes; 2: always the bucket sort, tests)
-    bool last_sort_bucket = false, last_sort_packed = false;   // what the last build's sort was (bh_stats bytes)
-    int64_t samples_n = -1;        // spos holds the sorted positions of a build of this many bodies (-1: none)
     uint64_t *splitters = nullptr;
     uint16_t *sort_dig = nullptr;  // bucket of every key (written by the histogram, read by the scatter)
     int build_items = 0;           // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
     bool hilbert = false;                // fp32 mode: Hilbert-ordered keys (BH_HILBERT=0 disables, A/B)
-    int partial_count = 0;         // LET mode: > 0: partial[] holds per-workgroup min/max of the current positions
     double *bslots = nullptr;      // kBoundSlots running bounds records (bh_bounds.hpp)
-    bool slots_valid = false;      // the last walk folded the bounds of the current positions into bslots
-    bool slots_dirty = true;       // bslots may hold something else than +-inf (written, not yet consumed by keys_kernel)
 
     // state (double2/double or float2/float).  Exact mode: caller order.  fp32 / mixed: DEVICE order --
     // every reorder_every-th build the bodies are physically permuted into that build's sorted order
@@ -99,9 +85,7 @@ struct bh_ctx {
     void *pos = nullptr, *vel = nullptr, *mass = nullptr, *force = nullptr;
     void *pos2 = nullptr, *vel2 = nullptr, *mass2 = nullptr, *force2 = nullptr;
     uint32_t *orig = nullptr, *orig2 = nullptr;
-    bool orig_identity = true;
     int reorder_every = 16;        // BH_REORDER_EVERY; 0 = never
-    int64_t builds = 0;            // builds since the last upload
     // sorted-order copies (fp32 mode)
     float2 *spos = nullptr;
     float4 *sstate = nullptr;      // sorted-order {x, y, vx, vy}: the replicated scheme's one exchange buffer
@@ -141,31 +125,24 @@ struct bh_ctx {
     int64_t *gid = nullptr;             // 64-bit id per body, caller order
     uint32_t *group_cost = nullptr;     // cost of every 64-body group in the last walk (sorted order)
     const void **walk_consts = nullptr; // device block {aux, spos, smass, 0} for the assembly walk's bucket path
-    bool aux_full = false;              // aux[] holds every node's record (after an export), not only the buckets'
-    bool group_cost_valid = false;
     uint32_t *body_counts = nullptr;    // BH_FLAG_WALK_STATS: accepted force evaluations per body (device slot order)
     // diagnostics (bh_diag.hpp), allocated on first use: potential and terms per body (state order), reduction records
     double *phi = nullptr;
     uint32_t *phi_counts = nullptr;
-    double *diag_part = nullptr, *diag_out = nullptr, *slots_save = nullptr;
-    bool phi_current = false;           // phi holds the potential of the current state
-    // the split operators (bh_split.hpp): the force buffer holds the accelerations (fp64 tree: the forces) of the CURRENT
-    // positions of ALL bodies, slot for slot -- set by bh_compute_forces and bh_step_kdk, cleared by whatever moves or
-    // re-orders the bodies or changes the law; the records of bh_timestep are allocated on first use
-    bool forces_current = false;
+    double *diag_part = nullptr, *diag_out = nullptr;
+    // the split operators (bh_split.hpp; is.forces_current): the records of bh_timestep are allocated on first use
     TsRecord *ts_part = nullptr, *ts_out = nullptr;
-    // LET mode: the quiet builds of the distributed diagnostics (bh_let_bounds_quiet, bh_let_build_quiet)
-    bool let_moved = false;             // an integrating walk has moved the bodies since the last bh_let_build
-    uint32_t *perm_save = nullptr;      // allocated on first use: the permutation of the last force walk's build
-    const uint32_t *cost_perm = nullptr;   // non-null: group_cost is indexed through this, not through perm (a quiet build since)
+    // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
+    double *slots_save = nullptr;
+    TreeCounters *ctr_save = nullptr;
+    uint32_t *perm_save = nullptr;
     // direct sums and the force check (bh_direct.hpp), allocated on first use: caller index -> slot, one launch's targets and
-    // results (capacity of them), and the check walk's own force / count / group-cost outputs and a copy of the walk counters
+    // results (capacity of them), and the check walk's own force / count / group-cost outputs
     uint32_t *slot_of = nullptr;
     int64_t *direct_targets = nullptr;
     double2 *direct_out = nullptr;
     void *check_force = nullptr;
     uint32_t *check_counts = nullptr, *check_cost = nullptr;
-    TreeCounters *ctr_save = nullptr;
     // the field at arbitrary points (bh_field.hpp), allocated on first use: one block for a launch of up to field_cap points --
     // the points, their results, two key arrays and the sorted order, the sort's count matrix and row totals
     char *field_block = nullptr;
@@ -186,11 +163,9 @@ struct bh_ctx {
     hipEvent_t ev_grp[3] = {nullptr, nullptr, nullptr};   // after keys / sort / scan of the last timed build
     hipEvent_t ev_let[3] = {nullptr, nullptr, nullptr};   // bh_let_build: start, local tree built, LETs packed
     bool let_timed = false;
-    bool time_groups = false;      // set by bh_step around its last build
     int64_t steps_done = 0;
     int32_t last_nsteps = 0;
     int timed_pairs = 0;
-    int64_t walk_launches = 0;     // walk kernel launches of the last enqueue_walk
     bool step_timed = false;
 
     std::vector<void *> allocs;
@@ -315,15 +290,10 @@ static void launch_nodes_fast(bh_ctx *c, bool full_aux, hipStream_t st)
                            dim3(kBlock), 0, st, c->keys_sorted, c->coarse, c->cnt, c->cell_first, c->spos, c->smass, c->box,
                            c->terms, c->n, c->Dm, c->cfg.theta, c->internal_cap, c->qf, c->aux, c->ctr);
     }, c->compat, full_aux);
-    c->aux_full = full_aux;
 }
 
 // before the bounds are folded into the slot records (bh_bounds.hpp): every record +-inf
-void clean_slots(bh_ctx *c)
-{
-    if (c->slots_dirty) hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots);
-    c->slots_dirty = true;
-}
+void clean_slots(bh_ctx *c) { if (c->carry.slots_dirty) hipLaunchKernelGGL(bounds_slots_reset, dim3(1), dim3(kWave), 0, c->stream, c->bslots); }
 
 // Stable LSD radix sort of n keys over key bits [0, bits): kSortBits-wide digits, wave-private ranking, digit-sorted
 // write-out, tiles of kBlock * SI keys.  Pass p reads keys[cur] / vals[cur] and writes keys[cur ^ 1] / vals[cur ^ 1], cur = 0
@@ -354,7 +324,7 @@ int enqueue_lsd_passes(hipStream_t st, uint64_t *const keys[2], uint32_t *const 
 }
 
 template <bool TREE64, bool STATE64 = TREE64, int ITEMS = kItems>
-int enqueue_build_t(bh_ctx *c)
+int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
 {
     constexpr int TILE = kBlock * ITEMS;
     static_assert(!TREE64 || STATE64, "an fp64 tree is built from fp64 state");
@@ -369,7 +339,7 @@ int enqueue_build_t(bh_ctx *c)
     // 1. root box (ComputeRootBounds, project.cu:536-573): the min/max of the positions is in the bounds slot records
     //    (bh_bounds.hpp) -- folded by the previous step's walk, or here by bounds_partial when no walk has left it --
     //    and keys_kernel reduces and pads it (LET mode: let_box_kernel has set the global box and cleared the counters)
-    const bool from_walk = c->slots_valid;
+    const bool from_walk = c->carry.slots_valid;
     double *slots = c->external_box ? nullptr : c->bslots;
     if (slots) {
         if (!from_walk) {
@@ -377,9 +347,8 @@ int enqueue_build_t(bh_ctx *c)
             clean_slots(c);
             hipLaunchKernelGGL((bounds_partial<Real2>), dim3(nbb), dim3(kBlock), 0, st, pos, n, slots);
         }
-        c->slots_valid = false;
-        if (n > 0) c->slots_dirty = false;                       // (prep_kernel puts them back to +-inf)
     }
+    BuildDone done{n, slots != nullptr, false, false, false, false};
 
     if (n > 0) {
         // 2. keys by fp64 bisection, 3. stable radix sort
@@ -393,14 +362,14 @@ int enqueue_build_t(bh_ctx *c)
         // counting pass it saves: N = 12,288 measured 0.100 ms per build this way against 0.090 at N = 16,384 the other way.
         // BH_SORT_BUCKET=2 keeps the splitter path at every size, for the tests that compare it with the LSD passes.)
         const bool single = pack && n >= 2 && n <= 4 * kBsThreads && c->sort_bucket == 1;
-        const bool bucket = !single && pack && n >= 2 && n <= kBucketMaxNBig && (c->sort_bucket == 2 || (c->sort_bucket == 1 && c->samples_n == n));
+        const bool bucket = !single && pack && n >= 2 && n <= kBucketMaxNBig && (c->sort_bucket == 2 || (c->sort_bucket == 1 && c->carry.samples_n == n));
         const int nb = (n <= kBucketMaxN) ? kBuckets : kBucketsBig;
         // sample positions behind the splitters: two per bucket where the key workgroups run long enough to hide the
         // sample workgroups (256 buckets: above 262k bodies; 1,024 buckets: above 3M), one per bucket otherwise
         const int ns = (nb == kBuckets) ? ((n > (int64_t)1 << 18) ? 2 * kBuckets : kBuckets)
                                         : ((n > (int64_t)3 << 20) ? kMaxSplitSamples : kBucketsBig);
         static_assert(kBucketMaxN == (int64_t)1 << 20 && kBucketMaxNBig == (int64_t)1 << 22, "BASELINE configs 3 and 4 fit");
-        c->last_sort_bucket = bucket || single; c->last_sort_packed = pack;
+        done.sort_bucket = bucket || single; done.sort_packed = pack;
         {
             const unsigned nkb = blocks_for(n, kBlock);
             auto keys_launch = [&](auto fs, auto pk, auto hil) {
@@ -415,7 +384,7 @@ int enqueue_build_t(bh_ctx *c)
             // (exact mode and BH_HILBERT=0: child-index keys, packed all the same)
             dispatch(keys_launch, slots != nullptr, pack, c->hilbert);
         }
-        if (c->time_groups) (void)hipEventRecord(c->ev_grp[0], st);
+        if (time_groups) (void)hipEventRecord(c->ev_grp[0], st);
         const unsigned nbl = blocks_for(n, ITEMS == kItems ? kSortTile : TILE);
         int cur = 0;
         if (single) {
@@ -452,21 +421,20 @@ int enqueue_build_t(bh_ctx *c)
         c->keys_sorted = c->keys[cur];
         c->perm = c->vals[cur];
         if constexpr (!TREE64) {
-            if (c->reorder_every > 0 && c->builds % c->reorder_every == 0) {
+            if (may_reorder && c->reorder_every > 0 && c->carry.builds % c->reorder_every == 0) {
                 hipLaunchKernelGGL((reorder_state_kernel<Real2, Real>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, st,
                                    c->perm, pos, static_cast<const Real2 *>(c->vel), mass,
-                                   static_cast<const float2 *>(c->force), c->orig_identity ? nullptr : c->orig,
+                                   static_cast<const float2 *>(c->force), c->is.orig_identity ? nullptr : c->orig,
                                    static_cast<Real2 *>(c->pos2), static_cast<Real2 *>(c->vel2),
                                    static_cast<Real *>(c->mass2), static_cast<float2 *>(c->force2), c->orig2, n);
                 std::swap(c->pos, c->pos2); std::swap(c->vel, c->vel2); std::swap(c->mass, c->mass2);
                 std::swap(c->force, c->force2); std::swap(c->orig, c->orig2);
-                c->orig_identity = false;
+                done.reordered = true;
                 pos = static_cast<const Real2 *>(c->pos);
                 mass = static_cast<const Real *>(c->mass);
             }
         }
-        c->builds += 1;
-        if (c->time_groups) (void)hipEventRecord(c->ev_grp[1], st);
+        if (time_groups) (void)hipEventRecord(c->ev_grp[1], st);
 
         // 4. cells owned by each sorted neighbour pair (+ fp32: sorted copies and prefix-sum terms),
         // 5. their ranks / the prefix sums
@@ -497,15 +465,14 @@ int enqueue_build_t(bh_ctx *c)
         };
         if (ITEMS == kItems && n <= (int64_t)1 << 21) scan_part(std::integral_constant<int, 4>{});
         else scan_part(std::integral_constant<int, ITEMS>{});
-        c->samples_n = n;                                        // spos (exact modes: perm): this build's sorted order
-        if (c->time_groups) (void)hipEventRecord(c->ev_grp[2], st);
+        if (time_groups) (void)hipEventRecord(c->ev_grp[2], st);
     } else {
         if (slots)          // no keys: one workgroup still writes the box and clears the counters
             hipLaunchKernelGGL((keys_kernel<Real2, false, false, true>), dim3(1), dim3(kBlock), 0, st, pos, c->box, c->keys[0],
                                c->vals[0], n, Dm, nullptr, nullptr, 0, 0, slots, c->ctr);
         c->keys_sorted = c->keys[0];
         c->perm = c->vals[0];
-        if (c->time_groups) for (auto e : c->ev_grp) (void)hipEventRecord(e, st);
+        if (time_groups) for (auto e : c->ev_grp) (void)hipEventRecord(e, st);
     }
 
     // 6. nodes (thread 0 writes the root when nothing is subdivided)
@@ -531,30 +498,33 @@ int enqueue_build_t(bh_ctx *c)
                                    c->self_node, c->cell_depth, c->ctr, c->internal_cap, d);
         }
     }
-    BH_HIP(c, hipGetLastError());
-    c->tree_valid = true;
+    const hipError_t err = hipGetLastError();
+    done.launched = err == hipSuccess;
+    c->build_completed(done);
+    BH_HIP(c, err);
     return BH_OK;
 }
 
 template <int ITEMS>
-static int enqueue_build_items(bh_ctx *c)
+static int enqueue_build_items(bh_ctx *c, bool may_reorder, bool time_groups)
 {
-    if (c->tree64()) return enqueue_build_t<true, true, ITEMS>(c);
-    return c->state64() ? enqueue_build_t<false, true, ITEMS>(c) : enqueue_build_t<false, false, ITEMS>(c);
+    if (c->tree64()) return enqueue_build_t<true, true, ITEMS>(c, may_reorder, time_groups);
+    return c->state64() ? enqueue_build_t<false, true, ITEMS>(c, may_reorder, time_groups)
+                        : enqueue_build_t<false, false, ITEMS>(c, may_reorder, time_groups);
 }
 
-int enqueue_build(bh_ctx *c)
+// may_reorder = false: a quiet build never permutes the state; time_groups: bh_step's last build records ev_grp
+int enqueue_build(bh_ctx *c, bool may_reorder = true, bool time_groups = false)
 {
-    c->cost_perm = nullptr;                  // (the quiet LET build puts its copy back afterwards)
     // keys per thread in the sort / scan kernels: launches of few bodies take smaller tiles (more
     // workgroups, fewer sequential rounds in each); BH_BUILD_ITEMS = 2, 4 or 8 overrides
     int items = c->build_items;
     if (items == 0) items = c->n <= kSmallBuildBodies ? 2 : c->n <= kMediumBuildBodies ? 4 : 8;
     if (c->n > (1 << 22)) items = 8;         // (scratch for small tiles is sized for 4M bodies)
     switch (items) {
-    case 2: return enqueue_build_items<2>(c);
-    case 4: return enqueue_build_items<4>(c);
-    default: return enqueue_build_items<kItems>(c);
+    case 2: return enqueue_build_items<2>(c, may_reorder, time_groups);
+    case 4: return enqueue_build_items<4>(c, may_reorder, time_groups);
+    default: return enqueue_build_items<kItems>(c, may_reorder, time_groups);
     }
 }
 
@@ -640,7 +610,7 @@ int each_pass(bh_ctx *c, const WalkRange &w, int per_group, Launch launch)
     for (int64_t plo = w.lo; plo < w.hi; plo += w.pass) {
         const int64_t phi = std::min(w.hi, plo + w.pass);
         if (int rc = launch(plo, phi, blocks_for(phi - plo, per_group))) return rc;
-        c->walk_launches += 1;
+        c->walk_launched();
     }
     return BH_OK;
 }
@@ -686,7 +656,7 @@ int launch_walk_exact_bfs(bh_ctx *c, const WalkRange &w)
                            (const double *)c->mass, (double2 *)c->force, w.lo, w.hi, c->cfg.G, c->cfg.dt, w.integrate ? 1 : 0,
                            c->ctr, w.slots, c->box);
     }, c->compat, cnt > 4096);
-    c->walk_launches += 1;
+    c->walk_launched();
     return BH_OK;
 }
 
@@ -749,7 +719,7 @@ int launch_walk_f32(bh_ctx *c, const WalkRange &w, const WalkChoice &k)
     }
     if (3 * c->Dm + 2 > kWave) split = 1;        // the level-synchronous walk's depth-first fallback has 64 entries
     const int per_record = walk_fast_split_effective(a, lds, split) ? kWave : kBlock;
-    if (w.partial) c->partial_count = (int)blocks_for(w.hi - w.lo, per_record);
+    if (w.partial) c->partials_recorded((int)blocks_for(w.hi - w.lo, per_record));
     return each_pass(c, w, per_record, [&](int64_t plo, int64_t phi, unsigned) -> int {
         a.lo = plo; a.hi = phi; a.partial = w.partial ? w.partial + 4 * ((plo - w.lo) / per_record) : nullptr;
         BH_HIP(c, launch_walk_fast(a, lds, w.stats, split, k.use_asm, c->stream));
@@ -764,7 +734,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     if (w.hi <= w.lo) return BH_OK;
     w.integrate = integrate; w.to_sorted = to_sorted; w.part = part;
     w.stats = (c->cfg.flags & BH_FLAG_WALK_STATS) != 0;
-    if (part != 2) c->walk_launches = 0;
+    c->walk_begins(part == 2);
     // N_THREADS (project.cu:5-7, 703: `body_i += N_THREADS`): at most that many bodies are walked at a time -- the
     // range is taken in passes of n_threads bodies, rounded up to whole 256-thread workgroups, one launch after the
     // other on the stream, as the reference's threads take their bodies one after the other.  0 (the default):
@@ -778,7 +748,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     if (full && c->let_mode) w.partial = c->partial;
     const bool want_slots = full && part == 0 && !c->let_mode && !c->external_box && c->n >= 2;
     if (want_slots) { clean_slots(c); w.slots = c->bslots; }
-    if (integrate) { c->slots_valid = want_slots; c->phi_current = false; c->let_moved = true; c->forces_current = false; }    // (the positions change)
+    if (integrate) c->positions_moved_by_walk(want_slots);
 
     const WalkChoice k = choose_walk(c, w);
     if (w.stats && (k.kind == WalkKind::F64 || k.kind == WalkKind::F32)) {      // (the bit-exact walks count no bodies)
@@ -796,7 +766,7 @@ int enqueue_walk(bh_ctx *c, bool integrate, bool to_sorted, int part = 0)
     }
     if (rc) return rc;
     BH_HIP(c, hipGetLastError());
-    if (!c->tree64() && w.lo == 0 && w.hi == c->n) { c->group_cost_valid = true; c->cost_perm = nullptr; }
+    if (!c->tree64() && w.lo == 0 && w.hi == c->n) c->group_costs_written();
     return BH_OK;
 }
 
@@ -811,26 +781,11 @@ int check_overflow(bh_ctx *c)
     return BH_OK;
 }
 
-// the state arrays hold another set of bodies, in caller order: nothing an earlier build, walk or potential left describes them
-void forget_body_set(bh_ctx *c)
-{
-    c->partial_count = 0; c->slots_valid = false;
-    c->samples_n = -1;                                        // new bodies: the next build sorts with the LSD passes
-    c->phi_current = false;
-    c->forces_current = false;
-    c->tree_valid = false;
-    c->orig_identity = true;
-    c->builds = 0;
-    c->group_cost_valid = false;
-    c->cost_perm = nullptr;
-}
-
 // bh_upload / bh_initialize: the state arrays hold n new bodies in caller order
-int new_bodies(bh_ctx *c, int64_t n)
+int upload_done(bh_ctx *c, int64_t n)
 {
     c->n = n;
-    forget_body_set(c);
-    c->uploaded = true;
+    c->new_bodies();
     c->steps_done = 0;
     if (c->gid && n > 0) {
         hipLaunchKernelGGL(iota_i64_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, c->gid, n);
@@ -842,11 +797,73 @@ int new_bodies(bh_ctx *c, int64_t n)
 // a non-integrating walk of this context covers every body (one GPU; a LET context and a rank of the replicated scheme do not)
 bool forces_cover_all(const bh_ctx *c) { return !c->let_mode && c->world == 1; }
 
+// BH_ERR_STATE with the caller's text unless a body set has been uploaded
+int need_upload(bh_ctx *c, const std::string &text) { return c->is.uploaded ? BH_OK : fail(c, BH_ERR_STATE, text); }
+
+// the LET calls' preconditions (c may be null): configured, and on demand bodies or a tree in the buffers
+enum LetNeed { kLetConfigured, kLetBodies, kLetTree };
+int let_check(bh_ctx *c, const char *who, LetNeed need)
+{
+    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, std::string(who) + ": call bh_let_configure first");
+    if (need == kLetBodies) return need_upload(c, std::string(who) + " before bh_upload");
+    return need == kLetTree && !c->is.tree_valid ? fail(c, BH_ERR_STATE, std::string(who) + " before bh_let_build") : BH_OK;
+}
+
+// host array with `per` values per body, read from the device in DEVICE order -> caller order (an fp64 tree never re-orders its
+// state: orig_identity holds there)
+template <typename T>
+int to_caller_order(bh_ctx *c, T *host, int per)
+{
+    if (c->is.orig_identity || c->n == 0) return BH_OK;
+    const int64_t n = c->n;
+    std::vector<uint32_t> o(n);
+    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<T> t(host, host + (size_t)per * n);
+    for (int64_t i = 0; i < n; ++i)
+        for (int k = 0; k < per; ++k) host[(size_t)per * o[i] + k] = t[(size_t)per * i + k];
+    return BH_OK;
+}
+
+// The quiet scope: quietly(c, options, body) runs a diagnostic's builds and walks without perturbing the run.  A build inside is
+// enqueue_build(c, false): it runs as a step's build would, except that it never re-orders the state.  Afterwards everything a
+// later build reads from an earlier one and everything the last real build and walk report is put back -- BuildCarry and LastRun
+// as whole structs (RunState::quiet_end), and the device-side copies the scope owns: always the bounds slot records the last walk
+// folded, the rest by option.  What a build leaves otherwise -- the sorted copies and splitter samples of THIS state, the tree
+// itself -- only changes the splitters of the next bucket sort, whose result is the same permutation whatever the splitters (the
+// keys carry the body index, so there are no ties).
+enum : unsigned {
+    kQuietCounters = 1,    // the walk counters of bh_stats (from `visits` on; keys_kernel and let_box_kernel clear them) are kept
+    kQuietOutputs = 2,     // a force walk runs inside: force, body_counts and group_cost are swapped for the check's buffers
+    kQuietCostPerm = 4,    // the permutation the last force walk's group costs are indexed through is kept for bh_orb_histogram
+};
+
+void swap_walk_outputs(bh_ctx *c) { std::swap(c->force, c->check_force); std::swap(c->body_counts, c->check_counts); std::swap(c->group_cost, c->check_cost); }
+template <typename Body>
+int quietly(bh_ctx *c, unsigned opts, Body body)
+{
+    constexpr size_t off = offsetof(TreeCounters, visits), ctr_bytes = sizeof(TreeCounters) - off, slot_doubles = (size_t)4 * kBoundSlots;
+    if ((opts & kQuietCounters) && !c->ctr_save) { if (int rc = dev_alloc(c, &c->ctr_save, 1)) return rc; }
+    if (!c->slots_save) { if (int rc = dev_alloc(c, &c->slots_save, slot_doubles)) return rc; }
+    RunState saved = *c;
+    if ((opts & kQuietCostPerm) && c->last.group_cost_valid && c->is.tree_valid && !c->last.cost_perm && c->n > 0) {
+        if (!c->perm_save) { if (int rc = dev_alloc(c, &c->perm_save, (size_t)std::max<int64_t>(c->cfg.capacity, 1))) return rc; }
+        BH_HIP(c, hipMemcpyAsync(c->perm_save, c->perm, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        saved.costs_indexed_through(c->perm_save);
+    }
+    if (opts & kQuietCounters) BH_HIP(c, hipMemcpyAsync((char *)c->ctr_save + off, (char *)c->ctr + off, ctr_bytes, hipMemcpyDeviceToDevice, c->stream));
+    BH_HIP(c, hipMemcpyAsync(c->slots_save, c->bslots, slot_doubles * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (opts & kQuietOutputs) swap_walk_outputs(c);
+    const int rc = body();
+    if (opts & kQuietOutputs) swap_walk_outputs(c);
+    c->quiet_end(saved);
+    BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_doubles * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (opts & kQuietCounters) BH_HIP(c, hipMemcpyAsync((char *)c->ctr + off, (char *)c->ctr_save + off, ctr_bytes, hipMemcpyDeviceToDevice, c->stream));
+    return rc;
+}
+
 }  // namespace
 
 // ================================================================================================
-static int download_pairs(bh_ctx *c, const void *dev, double *host, int64_t count, bool is64);
-static int to_caller_order(bh_ctx *c, double *host, int per);
 
 extern "C" {
 
@@ -1001,11 +1018,10 @@ int bh_set_softening(bh_ctx *c, double eps)
                                    "reference has no softening -- use BH_PRECISION_F64, MIXED or F32 for a softened run");
     const double eps2 = eps * eps;
     if (!std::isfinite(eps2)) return fail(c, BH_ERR_ARG, "bh_set_softening: the square of the softening length overflows");
-    if (eps != c->eps) c->forces_current = false;             // the force buffer holds the forces of another law
+    c->law_changed(eps != c->eps);      // (phi holds the potential of another law until it is recomputed)
     c->eps = eps;
     c->eps2 = eps2;
     c->eps2f = (float)eps2;             // (0.f for a tiny eps: the fp32 walks then run their unsoftened kernels)
-    c->phi_current = false;             // phi holds the potential of another law until it is recomputed
     return BH_OK;
 }
 
@@ -1048,7 +1064,7 @@ int bh_upload(bh_ctx *c, const double *pos, const double *vel, const double *mas
         BH_HIP(c, hipMemcpy(c->mass, t.data(), n * sizeof(float), hipMemcpyHostToDevice));
     }
     BH_HIP(c, hipMemset(c->force, 0, force_bytes(c, n)));
-    return new_bodies(c, n);
+    return upload_done(c, n);
 }
 
 static int download_pairs(bh_ctx *c, const void *dev, double *host, int64_t count, bool is64)
@@ -1063,31 +1079,11 @@ static int download_pairs(bh_ctx *c, const void *dev, double *host, int64_t coun
     return BH_OK;
 }
 
-// host array with `per` doubles per body, read from the device in DEVICE order -> caller order
-static int to_caller_order(bh_ctx *c, double *host, int per)
-{
-    if (c->tree64() || c->orig_identity || c->n == 0) return BH_OK;
-    const int64_t n = c->n;
-    std::vector<uint32_t> o(n);
-    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<double> t(host, host + (size_t)per * n);
-    for (int64_t i = 0; i < n; ++i)
-        for (int k = 0; k < per; ++k) host[(size_t)per * o[i] + k] = t[(size_t)per * i + k];
-    return BH_OK;
-}
-
-// one uint32 per body, read from the device in DEVICE order -> out in caller order (an fp64 tree never re-orders its
-// state: orig_identity holds there)
+// one uint32 per body, read from the device in DEVICE order -> out in caller order
 static int counts_to_caller_order(bh_ctx *c, const uint32_t *dev_counts, uint32_t *out)
 {
-    const int64_t n = c->n;
-    if (n == 0) return BH_OK;
-    if (c->orig_identity) { BH_HIP(c, hipMemcpy(out, dev_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return BH_OK; }
-    std::vector<uint32_t> t(n), o(n);
-    BH_HIP(c, hipMemcpy(t.data(), dev_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    BH_HIP(c, hipMemcpy(o.data(), c->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) out[o[i]] = t[i];
-    return BH_OK;
+    BH_HIP(c, hipMemcpy(out, dev_counts, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return to_caller_order(c, out, 1);
 }
 
 // a state array (`per` values per body) -> host, caller order
@@ -1117,13 +1113,13 @@ int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lowe
         BH_HIP(c, hipGetLastError());
     }
     BH_HIP(c, hipMemsetAsync(c->force, 0, force_bytes(c, n), c->stream));
-    return new_bodies(c, n);
+    return upload_done(c, n);
 }
 
 int bh_download_masses(bh_ctx *c, double *mass)
 {
     if (!c || !mass) return fail(c, BH_ERR_ARG, "bh_download_masses: null array");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_download_masses before bh_upload/bh_initialize");
+    if (int rc = need_upload(c, "bh_download_masses before bh_upload/bh_initialize")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     return download_state(c, c->mass, mass, 1);
@@ -1135,7 +1131,7 @@ int bh_sync(bh_ctx *c)
     BH_HIP(c, hipSetDevice(c->device));
     // also reports a tree that outgrew node_capacity during bh_step (the walk of such a step does
     // nothing, so the state is the last good one)
-    if (c->tree_valid) return check_overflow(c);
+    if (c->is.tree_valid) return check_overflow(c);
     BH_HIP(c, hipStreamSynchronize(c->stream));
     return BH_OK;
 }
@@ -1143,9 +1139,9 @@ int bh_sync(bh_ctx *c)
 int bh_download(bh_ctx *c, double *pos, double *vel)
 {
     if (!c || !pos) return fail(c, BH_ERR_ARG, "bh_download: null array");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_download before bh_upload");
+    if (int rc = need_upload(c, "bh_download before bh_upload")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    int rc = c->tree_valid ? check_overflow(c) : BH_OK;
+    int rc = c->is.tree_valid ? check_overflow(c) : BH_OK;
     if (rc) return rc;
     BH_HIP(c, hipStreamSynchronize(c->stream));
     rc = download_state(c, c->pos, pos, 2);
@@ -1155,9 +1151,9 @@ int bh_download(bh_ctx *c, double *pos, double *vel)
 int bh_build_tree(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_build_tree before bh_upload");
+    if (int rc = need_upload(c, "bh_build_tree before bh_upload")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    c->forces_current = false;               // (a build that is not quiet: no force walk follows it)
+    c->forces_outdated();                    // (a build that is not quiet: no force walk follows it)
     int rc = enqueue_build(c);
     if (rc) return rc;
     return check_overflow(c);
@@ -1166,15 +1162,12 @@ int bh_build_tree(bh_ctx *c)
 int bh_compute_forces(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_compute_forces before bh_upload");
+    if (int rc = need_upload(c, "bh_compute_forces before bh_upload")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    c->forces_current = false;
     int rc = enqueue_build(c);
-    if (rc) return rc;
-    rc = enqueue_walk(c, false, false);
-    if (rc) return rc;
-    rc = check_overflow(c);
-    c->forces_current = rc == BH_OK && forces_cover_all(c);
+    if (!rc) rc = enqueue_walk(c, false, false);
+    if (!rc) rc = check_overflow(c);
+    c->forces_computed(rc == BH_OK && forces_cover_all(c));        // (not current either when any of the three failed)
     return rc;
 }
 
@@ -1195,9 +1188,7 @@ static int step_events(bh_ctx *c, int32_t nsteps, int *want)
 static int enqueue_timed_step(bh_ctx *c, int s, int nsteps, int want, bool integrate)
 {
     if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[0], c->stream));
-    c->time_groups = (s == nsteps - 1);
-    int rc = enqueue_build(c);
-    c->time_groups = false;
+    int rc = enqueue_build(c, true, s == nsteps - 1);
     if (rc) return rc;
     if (s == nsteps - 1) BH_HIP(c, hipEventRecord(c->ev_build[1], c->stream));
     if (s < want) BH_HIP(c, hipEventRecord(c->ev[2 * s], c->stream));
@@ -1218,7 +1209,7 @@ static void steps_enqueued(bh_ctx *c, int32_t nsteps, int want)
 int bh_step(bh_ctx *c, int32_t nsteps)
 {
     if (!c || nsteps < 0) return BH_ERR_ARG;
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_step before bh_upload");
+    if (int rc = need_upload(c, "bh_step before bh_upload")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     int want = 0;
     if (int rc = step_events(c, nsteps, &want)) return rc;
@@ -1231,17 +1222,17 @@ int bh_step(bh_ctx *c, int32_t nsteps)
 }
 
 // ---- the split operators (bh_split.hpp): kick, drift, the time-step criterion, and the leapfrog built from them
-static int split_check(bh_ctx *c, const char *what)
+// uploaded, and one context holds every body: else BH_ERR_STATE, `what` + `why_single` for the second
+static int single_gpu_check(bh_ctx *c, const char *what, const char *why_single)
 {
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(what) + " before bh_upload");
-    if (c->let_mode || c->world > 1)
-        return fail(c, BH_ERR_STATE, std::string(what) + ": single GPU only (not in LET mode or with world > 1)");
-    return BH_OK;
+    if (int rc = need_upload(c, std::string(what) + " before bh_upload")) return rc;
+    return forces_cover_all(c) ? BH_OK : fail(c, BH_ERR_STATE, std::string(what) + why_single);
 }
+static int split_check(bh_ctx *c, const char *what) { return single_gpu_check(c, what, ": single GPU only (not in LET mode or with world > 1)"); }
 
 static int need_forces(bh_ctx *c, const char *what)
 {
-    if (c->forces_current) return BH_OK;
+    if (c->is.forces_current) return BH_OK;
     return fail(c, BH_ERR_STATE, std::string(what) + ": the force buffer does not hold the accelerations of the current positions "
                                  "(bh_compute_forces first; a step, bh_drift, bh_upload, bh_build_tree and a new softening length outdate them)");
 }
@@ -1277,10 +1268,7 @@ static int enqueue_kick(bh_ctx *c, double h)
 static int enqueue_drift(bh_ctx *c, double h)
 {
     const int64_t n = c->n;
-    c->forces_current = false;
-    c->phi_current = false;
-    c->tree_valid = false;
-    c->slots_valid = false;
+    c->positions_moved_by_drift();
     if (n == 0 || h == 0.0) return BH_OK;
     const dim3 grid(blocks_for(n, kBlock)), block(kBlock);
     switch (c->mode) {
@@ -1334,7 +1322,7 @@ int bh_timestep(bh_ctx *c, double eta, double length, bh_timestep_t *out)
         if (!rc) rc = dev_alloc(c, &c->ts_out, 1);
         if (rc) { dev_free(c, c->ts_part); dev_free(c, c->ts_out); c->ts_part = c->ts_out = nullptr; return rc; }
     }
-    const uint32_t *orig = (c->tree64() || c->orig_identity) ? nullptr : c->orig;
+    const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
     if (c->tree64())
         hipLaunchKernelGGL((timestep_partial_kernel<double2>), dim3(kTsParts), dim3(kBlock), 0, c->stream, (const double2 *)c->force,
                            (const double *)c->mass, orig, c->n, c->ts_part);
@@ -1368,7 +1356,7 @@ int bh_step_kdk(bh_ctx *c, int32_t nsteps)
     int want = 0;
     if (int rc = step_events(c, nsteps, &want)) return rc;
     BH_HIP(c, hipEventRecord(c->ev_step[0], c->stream));
-    if (!c->forces_current) {                                  // (else: the closing forces of the previous call)
+    if (!c->is.forces_current) {                                  // (else: the closing forces of the previous call)
         int rc = enqueue_build(c);
         if (!rc) rc = enqueue_walk(c, false, false);
         if (rc) return rc;
@@ -1380,7 +1368,7 @@ int bh_step_kdk(bh_ctx *c, int32_t nsteps)
     if (int rc = enqueue_kick(c, 0.5 * dt)) return rc;
     BH_HIP(c, hipEventRecord(c->ev_step[1], c->stream));
     steps_enqueued(c, nsteps, want);
-    c->forces_current = forces_cover_all(c);
+    c->forces_computed(forces_cover_all(c));
     return BH_OK;
 }
 
@@ -1424,22 +1412,13 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
 }
 
 // ---- diagnostics (bh_diag.hpp): potential walk and reductions
-// A tree of the current state is built for the potential walk and the force check without perturbing the run
-// (enqueue_quiet_build): the build runs as a step's build
-// would, except that it never re-orders the state, and afterwards everything a later build reads from an earlier one is put
-// back -- the build count (re-order cadence), samples_n (whether the next sort takes the bucket path), the bounds slot
-// records the last walk folded (copied aside on the device and back) and their flags.  What the build leaves otherwise --
-// the sorted copies and splitter samples of THIS state, the tree itself -- only changes the splitters of the next bucket
-// sort, whose result is the same permutation whatever the splitters (the keys carry the body index, so there are no ties).
+// A tree of the current state is built in a quiet scope (quietly) for the potential walk and the force check.
 // The walk writes phi and its own term counts only: force, body_counts, group_cost, partial, the event timings and
 // walk_launches are not touched.
 static int diag_check(bh_ctx *c, const char *what)
 {
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(what) + " before bh_upload");
-    if (c->let_mode || c->world > 1)
-        return fail(c, BH_ERR_STATE, std::string(what) + ": single GPU only -- in LET mode bh_let_potential / bh_let_energy give the potential "
+    return single_gpu_check(c, what, ": single GPU only -- in LET mode bh_let_potential / bh_let_energy give the potential "
                                      "and the energy sums; the replicated scheme (world > 1) and the other diagnostics have no distributed form");
-    return BH_OK;
 }
 
 static int diag_alloc(bh_ctx *c)
@@ -1455,41 +1434,10 @@ static int diag_alloc(bh_ctx *c)
     return rc;
 }
 
-// the walk counters of bh_stats (TreeCounters from `visits` on, which a build's keys_kernel clears): copied aside, or put back
-static int copy_walk_counters(bh_ctx *c, bool aside)
-{
-    if (!c->ctr_save) { if (int rc = dev_alloc(c, &c->ctr_save, 1)) return rc; }
-    constexpr size_t off = offsetof(TreeCounters, visits), bytes = sizeof(TreeCounters) - off;
-    char *from = (char *)(aside ? c->ctr : c->ctr_save) + off, *to = (char *)(aside ? c->ctr_save : c->ctr) + off;
-    BH_HIP(c, hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return BH_OK;
-}
-
-// the tree of the current state, no re-order, and everything a later build reads from an earlier one put back (above);
-// keep_walk_counters: also the walk counters of bh_stats, copied aside before the build and put back after it
-static int enqueue_quiet_build(bh_ctx *c, bool keep_walk_counters)
-{
-    if (keep_walk_counters) { if (int rc = copy_walk_counters(c, true)) return rc; }
-    if (!c->slots_save) { if (int rc = dev_alloc(c, &c->slots_save, (size_t)4 * kBoundSlots)) return rc; }
-    const int64_t builds = c->builds, samples_n = c->samples_n;
-    const int reorder_every = c->reorder_every;
-    const bool slots_valid = c->slots_valid, slots_dirty = c->slots_dirty;
-    const size_t slot_bytes = (size_t)4 * kBoundSlots * sizeof(double);
-    BH_HIP(c, hipMemcpyAsync(c->slots_save, c->bslots, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
-    c->reorder_every = 0;
-    int rc = enqueue_build(c);
-    c->reorder_every = reorder_every;
-    c->builds = builds; c->samples_n = samples_n;
-    c->slots_valid = slots_valid; c->slots_dirty = slots_dirty;
-    BH_HIP(c, hipMemcpyAsync(c->bslots, c->slots_save, slot_bytes, hipMemcpyDeviceToDevice, c->stream));
-    if (keep_walk_counters) { if (int rc2 = copy_walk_counters(c, false)) return rc2; }
-    return rc;
-}
-
 static int enqueue_potential(bh_ctx *c)
 {
     // (false: bh_stats after a potential on a BH_FLAG_WALK_STATS context reads zero walk counters -- as it always has)
-    if (int rc = enqueue_quiet_build(c, false)) return rc;
+    if (int rc = quietly(c, 0, [&] { return enqueue_build(c, false); })) return rc;
     if (c->n == 0) return BH_OK;
     const unsigned grid = blocks_for(c->n, kBlock);
     if (c->tree64()) {
@@ -1521,15 +1469,14 @@ int bh_compute_potential(bh_ctx *c)
     int rc = diag_alloc(c);
     if (!rc) rc = enqueue_potential(c);
     if (!rc) rc = check_overflow(c);
-    c->phi_current = rc == BH_OK;
+    c->potential_computed(rc == BH_OK);
     return rc;
 }
 
-int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
+// phi and, if asked for, its term counts in caller order; `stale`: the error text when phi is not the current state's
+static int download_potential(bh_ctx *c, double *phi, uint32_t *counts, const char *stale)
 {
-    if (!c || !phi) return fail(c, BH_ERR_ARG, "bh_get_potential: null array");
-    if (int rc = diag_check(c, "bh_get_potential")) return rc;
-    if (!c->phi_current) return fail(c, BH_ERR_STATE, "bh_get_potential: no potential of the current state (bh_compute_potential)");
+    if (!c->is.phi_current) return fail(c, BH_ERR_STATE, stale);
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     const int64_t n = c->n;
@@ -1538,6 +1485,13 @@ int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
     int rc = to_caller_order(c, phi, 1);
     if (rc || !counts) return rc;
     return counts_to_caller_order(c, c->phi_counts, counts);
+}
+
+int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
+{
+    if (!c || !phi) return fail(c, BH_ERR_ARG, "bh_get_potential: null array");
+    if (int rc = diag_check(c, "bh_get_potential")) return rc;
+    return download_potential(c, phi, counts, "bh_get_potential: no potential of the current state (bh_compute_potential)");
 }
 
 // the eight sums of bh_diag.hpp over the state and phi, in the two fixed-shape passes: q on the host when this returns
@@ -1561,7 +1515,7 @@ int bh_energy(bh_ctx *c, bh_energy_t *out)
 {
     if (!c || !out) return fail(c, BH_ERR_ARG, "bh_energy: null argument");
     if (int rc = diag_check(c, "bh_energy")) return rc;
-    if (!c->phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
+    if (!c->is.phi_current) { if (int rc = bh_compute_potential(c)) return rc; }
     BH_HIP(c, hipSetDevice(c->device));
     double q[kDiagQuantities];
     if (int rc = energy_sums(c, q)) return rc;
@@ -1580,7 +1534,7 @@ int bh_energy(bh_ctx *c, bh_energy_t *out)
 }
 
 // ---- direct sums and the Barnes-Hut force check (bh_direct.hpp)
-// The direct kernel reads the state only.  The check's tree forces come from a quiet build (enqueue_quiet_build) and the
+// The direct kernel reads the state only.  The check's tree forces come from a quiet build (quietly) and the
 // precision's own force walk (enqueue_walk, not integrating: n_threads applies as in a step) with the walk's outputs --
 // force, body_counts, group_cost -- swapped for scratch buffers, and walk_launches, group_cost_valid and the walk counters of
 // bh_stats put back: bh_get_forces, bh_get_interaction_counts, bh_stats and the ORB weights still describe the last real
@@ -1608,7 +1562,7 @@ static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targe
         if (rc) { dev_free(c, c->direct_targets); dev_free(c, c->direct_out); c->direct_targets = nullptr; c->direct_out = nullptr; return rc; }
     }
     const uint32_t *slot_of = nullptr;
-    if (!c->tree64() && !c->orig_identity) {            // (fp32 / mixed after a physical re-order: slots are not caller indices)
+    if (!c->tree64() && !c->is.orig_identity) {            // (fp32 / mixed after a physical re-order: slots are not caller indices)
         if (!c->slot_of) { if (int rc = dev_alloc(c, &c->slot_of, (size_t)chunk)) return rc; }
         hipLaunchKernelGGL(direct_slot_kernel, dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream, c->orig, c->n, c->slot_of);
         slot_of = c->slot_of;
@@ -1644,24 +1598,11 @@ static int check_walk(bh_ctx *c, double *out)
         if (rc) return rc;
     }
     if ((c->cfg.flags & BH_FLAG_WALK_STATS) && !c->check_counts) { if ((rc = dev_alloc(c, &c->check_counts, cap))) return rc; }
-    const int64_t launches = c->walk_launches;
-    const bool cost_valid = c->group_cost_valid;
-    // (the check's walk counts as well: its counters are kept around build and walk together, so the quiet build keeps none)
-    if ((rc = copy_walk_counters(c, true))) return rc;
-    rc = enqueue_quiet_build(c, false);
-    if (!rc) {
-        auto swap_outputs = [&] {
-            std::swap(c->force, c->check_force);
-            std::swap(c->body_counts, c->check_counts);
-            std::swap(c->group_cost, c->check_cost);
-        };
-        swap_outputs();
-        rc = enqueue_walk(c, false, false);
-        swap_outputs();
-    }
-    c->walk_launches = launches;
-    c->group_cost_valid = cost_valid;
-    if (int rc2 = copy_walk_counters(c, false)) return rc2;
+    // (the check's walk counts as well: its counters are kept around build and walk together)
+    rc = quietly(c, kQuietCounters | kQuietOutputs, [&] {
+        const int r = enqueue_build(c, false);
+        return r ? r : enqueue_walk(c, false, false);
+    });
     if (!rc) rc = check_overflow(c);
     return rc ? rc : forces_or_accels(c, c->check_force, out, true);
 }
@@ -1693,7 +1634,7 @@ int bh_force_check(bh_ctx *c, const int64_t *targets, int64_t n_targets, double 
 }
 
 // ---- the field at arbitrary points (bh_field.hpp)
-// The tree comes from a quiet build (enqueue_quiet_build), with the walk counters of bh_stats copied aside and put back as in
+// The tree comes from a quiet build (quietly), with the walk counters of bh_stats copied aside and put back as in
 // check_walk (keys_kernel clears them).  The kernels read the tree and the call's own buffers and write the call's own buffers
 // only: force, body_counts, group_cost, phi, the event timings and walk_launches are not touched.
 static int field_alloc(bh_ctx *c, int64_t want)
@@ -1768,7 +1709,7 @@ int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel
     }
     BH_HIP(c, hipSetDevice(c->device));
     if (int rc = field_alloc(c, std::min(n_points, kFieldChunk))) return rc;
-    int rc = enqueue_quiet_build(c, true);
+    int rc = quietly(c, kQuietCounters, [&] { return enqueue_build(c, false); });
     if (!rc) rc = check_overflow(c);
     if (rc) return rc;
     for (int64_t t0 = 0; t0 < n_points; t0 += kFieldChunk) {
@@ -1786,7 +1727,7 @@ int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel
 // ---- tree export: DFS pre-order, children in index order (TraverseTreeToFile, project.cu:504-534)
 static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vector<int32_t> &depth)
 {
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "no tree built yet");
+    if (!c->is.tree_valid) return fail(c, BH_ERR_STATE, "no tree built yet");
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     TreeCounters h{};
@@ -1801,7 +1742,7 @@ static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vect
     std::vector<NodeAux> aux;
     std::vector<uint32_t> perm(std::max<int64_t>(c->n, 1));
     if (c->n > 0) BH_HIP(c, hipMemcpy(perm.data(), c->perm, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (!c->tree64() && !c->orig_identity && c->n > 0) {          // slots -> the caller's body indices
+    if (!c->tree64() && !c->is.orig_identity && c->n > 0) {          // slots -> the caller's body indices
         std::vector<uint32_t> o(c->n);
         BH_HIP(c, hipMemcpy(o.data(), c->orig, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (auto &b : perm) b = o[b];
@@ -1812,8 +1753,9 @@ static int export_tree_host(bh_ctx *c, std::vector<bh_tree_node> &out, std::vect
         BH_HIP(c, hipMemcpy(ld.data(), c->ld, nn * sizeof(LinkD), hipMemcpyDeviceToHost));
     } else {
         const int64_t nq = (int64_t)h.n_internal + 1;      // quad 0 = root
-        if (!c->aux_full && c->n > 0) {                    // the step's node kernel writes bucket records only
+        if (!c->is.aux_full && c->n > 0) {                    // the step's node kernel writes bucket records only
             launch_nodes_fast(c, true, c->stream);
+            c->all_node_records_written();
             BH_HIP(c, hipGetLastError());
             BH_HIP(c, hipStreamSynchronize(c->stream));
         }
@@ -1922,13 +1864,13 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
     std::memset(out, 0, sizeof(*out));
     out->n_bodies = c->n;
     out->steps_done = c->steps_done;
-    out->walk_launches = (uint64_t)c->walk_launches;
+    out->walk_launches = (uint64_t)c->last.walk_launches;
     out->device_bytes = c->device_bytes;
     TreeCounters h{};
     BH_HIP(c, hipMemcpy(&h, c->ctr, sizeof(h), hipMemcpyDeviceToHost));
     out->sort_spill_buckets = h.sort_spills;
     out->sort_rerun_buckets = h.sort_reruns;
-    if (c->tree_valid) {
+    if (c->is.tree_valid) {
         out->n_internal = h.n_internal;
         out->n_nodes = 1 + 4 * (int64_t)h.n_internal;
         out->visits = h.visits;
@@ -1965,8 +1907,8 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
         // state is fp64); scans: counts in and out, cell starts, terms -> prefix sums; nodes: ~0.72 cells per body,
         // each reading its key window share, ranks and five prefix sums and writing an 80-byte quad
         const int passes = (2 * c->Dm + kSortBits - 1) / kSortBits;
-        const uint64_t keys_b = (c->state64() ? 24u : 16u) + (c->last_sort_packed ? 0u : 4u);
-        const uint64_t sort_b = c->last_sort_bucket ? 46u : (uint64_t)passes * (c->last_sort_packed ? 24u : 32u);
+        const uint64_t keys_b = (c->state64() ? 24u : 16u) + (c->last.last_sort_packed ? 0u : 4u);
+        const uint64_t sort_b = c->last.last_sort_bucket ? 46u : (uint64_t)passes * (c->last.last_sort_packed ? 24u : 32u);
         const uint64_t prep_b = c->state64() ? 76u : 40u, scan_b = c->state64() ? 59u : 47u, nodes_b = c->tree64() ? 140u : 117u;
         out->build_bytes = (uint64_t)c->n * (keys_b + sort_b + prep_b + scan_b + nodes_b);
         out->walk_bytes = out->wave_nodes ? (uint64_t)c->n * 44u + out->wave_nodes * 20u : 0u;
@@ -2048,7 +1990,7 @@ extern "C" {
 int bh_step_local(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_step_local before bh_upload");
+    if (int rc = need_upload(c, "bh_step_local before bh_upload")) return rc;
     if (c->state64()) return fail(c, BH_ERR_STATE, "bh_step_local: fp32 mode only");
     BH_HIP(c, hipSetDevice(c->device));
     int rc = enqueue_build(c);
@@ -2066,7 +2008,7 @@ int bh_scatter_sorted(bh_ctx *c)
                            c->perm, c->sstate, (float2 *)c->pos, (float2 *)c->vel, c->n);
         BH_HIP(c, hipGetLastError());
     }
-    c->slots_valid = false; c->phi_current = false; c->forces_current = false;
+    c->positions_moved_by_scatter();
     c->steps_done += 1;
     return BH_OK;
 }
@@ -2121,30 +2063,29 @@ int bh_let_configure(bh_ctx *c, int32_t rank, int32_t world, int64_t let_cap, in
     BH_HIP(c, hipMemset(c->let_tsum, 0, kMaxWorld * sizeof(uint32_t)));
     c->let_mode = true;
     c->external_box = true;
-    c->tree_valid = false;
+    c->let_configured();
     return BH_OK;
 }
 
-// quiet: the walk's records stay for the next bh_let_bounds (a step after the diagnostic describes itself by the same boxes)
+// quiet (the scope's struct pair alone: nothing to copy on the device): the walk's records stay for the next bh_let_bounds (a
+// step after the diagnostic describes itself by the same boxes)
 static int let_bounds(bh_ctx *c, bool quiet, const char *who)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, std::string(who) + ": call bh_let_configure first");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
+    if (int rc = let_check(c, who, kLetBodies)) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    const int from_walk = c->partial_count;
-    if (c->partial_count <= 0) {
-        const unsigned nbb = kLetBoxes * kLetBoxParts;
+    const RunState saved = *c;
+    int count = c->carry.partial_count;
+    if (count <= 0) {
+        count = kLetBoxes * kLetBoxParts;
         with_state(c, [&](auto r2) {
             using Real2 = decltype(r2);
-            hipLaunchKernelGGL((let_slice_bounds_kernel<Real2>), dim3(nbb), dim3(kBlock), 0, c->stream, (const Real2 *)c->pos, c->n,
+            hipLaunchKernelGGL((let_slice_bounds_kernel<Real2>), dim3((unsigned)count), dim3(kBlock), 0, c->stream, (const Real2 *)c->pos, c->n,
                                c->partial);
         });
-        c->partial_count = (int)nbb;
     }
-    hipLaunchKernelGGL(let_local_bounds_kernel, dim3(kLetBoxes), dim3(kWave), 0, c->stream, c->partial,
-                       c->partial_count, c->lbounds);
-    c->partial_count = (quiet && from_walk > 0) ? from_walk : 0;
-    c->slots_valid = false;
+    hipLaunchKernelGGL(let_local_bounds_kernel, dim3(kLetBoxes), dim3(kWave), 0, c->stream, c->partial, count, c->lbounds);
+    c->let_bounds_taken();
+    if (quiet) c->quiet_end(saved);
     BH_HIP(c, hipGetLastError());
     return BH_OK;
 }
@@ -2155,7 +2096,7 @@ int bh_let_bounds_quiet(bh_ctx *c) { return let_bounds(c, true, "bh_let_bounds_q
 int bh_let_pointers(bh_ctx *c, void **lbounds, void **all_bounds, void **send, void **recv, int64_t *block_bytes,
                     int32_t *boxes_per_rank)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_pointers: call bh_let_configure first");
+    if (int rc = let_check(c, "bh_let_pointers", kLetConfigured)) return rc;
     if (lbounds) *lbounds = c->lbounds;
     if (all_bounds) *all_bounds = c->all_bounds;
     if (send) *send = c->let_send;
@@ -2165,42 +2106,34 @@ int bh_let_pointers(bh_ctx *c, void **lbounds, void **all_bounds, void **send, v
     return BH_OK;
 }
 
-// quiet (the distributed diagnostics): the local tree by enqueue_quiet_build -- no re-order, build count and samples_n put
-// back --, the walk counters of bh_stats copied aside and back (let_box_kernel clears them), the bh_let_build timings left
-// alone, and the permutation the last force walk's group costs are indexed through kept for bh_orb_histogram.  The LET
-// size counters take this build's sizes like any other's.
+// quiet (the distributed diagnostics): the whole call in a quiet scope -- the local tree without a re-order, build count and
+// samples_n put back --, the walk counters of bh_stats copied aside and back (let_box_kernel clears them), the bh_let_build
+// timings left alone (they are recorded outside a scope only), and the permutation the last force walk's group costs are indexed
+// through kept for bh_orb_histogram.  The LET size counters take this build's sizes like any other's.
 static int let_build(bh_ctx *c, bool quiet, const char *who)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, std::string(who) + ": call bh_let_configure first");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
+    if (int rc = let_check(c, who, kLetBodies)) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const uint32_t *cost_perm = c->cost_perm;
-    if (quiet) {
-        if (int rc = copy_walk_counters(c, true)) return rc;
-        if (c->group_cost_valid && c->tree_valid && !cost_perm && c->n > 0) {
-            if (!c->perm_save) { if (int rc = dev_alloc(c, &c->perm_save, (size_t)std::max<int64_t>(c->cfg.capacity, 1))) return rc; }
-            BH_HIP(c, hipMemcpyAsync(c->perm_save, c->perm, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            cost_perm = c->perm_save;
-        }
-    } else {
-        (void)hipEventRecord(c->ev_let[0], st);
-    }
-    hipLaunchKernelGGL(let_box_kernel, dim3(1), dim3(64), 0, st, c->all_bounds, c->world * kLetBoxes, c->box, c->ctr,
-                       c->let_ctr, c->Dm);
-    int rc = quiet ? enqueue_quiet_build(c, false) : enqueue_build(c);
-    if (rc) return rc;
-    if (quiet) c->cost_perm = cost_perm;
-    else (void)hipEventRecord(c->ev_let[1], st);
-    const int64_t nq = c->quads_local;
-    hipLaunchKernelGGL(let_mark_alloc_kernel, dim3(blocks_for(4 * nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->all_bounds,
-                       c->world, c->rank, c->ctr, c->internal_cap, c->needmask, c->let_tsum, c->let_outidx, nq);
-    hipLaunchKernelGGL(let_pack_kernel, dim3(blocks_for(nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->needmask,
-                       c->let_outidx, nq, c->world, c->rank, c->ctr, c->internal_cap, c->let_send,
-                       (uint32_t)c->let_cap, c->forest_base + (int64_t)c->rank * c->let_cap, c->let_tsum, c->let_ctr);
-    if (quiet) { if (int rc2 = copy_walk_counters(c, false)) return rc2; }
-    else { (void)hipEventRecord(c->ev_let[2], st); c->let_timed = true; }
-    c->let_moved = false;
+    auto stamp = [&](int i) { if (!quiet) (void)hipEventRecord(c->ev_let[i], st); };
+    auto body = [&]() -> int {
+        stamp(0);
+        hipLaunchKernelGGL(let_box_kernel, dim3(1), dim3(64), 0, st, c->all_bounds, c->world * kLetBoxes, c->box, c->ctr,
+                           c->let_ctr, c->Dm);
+        if (int rc = enqueue_build(c, !quiet)) return rc;
+        stamp(1);
+        const int64_t nq = c->quads_local;
+        hipLaunchKernelGGL(let_mark_alloc_kernel, dim3(blocks_for(4 * nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->all_bounds,
+                           c->world, c->rank, c->ctr, c->internal_cap, c->needmask, c->let_tsum, c->let_outidx, nq);
+        hipLaunchKernelGGL(let_pack_kernel, dim3(blocks_for(nq, kBlock)), dim3(kBlock), 0, st, c->qf, c->needmask,
+                           c->let_outidx, nq, c->world, c->rank, c->ctr, c->internal_cap, c->let_send,
+                           (uint32_t)c->let_cap, c->forest_base + (int64_t)c->rank * c->let_cap, c->let_tsum, c->let_ctr);
+        stamp(2);
+        return BH_OK;
+    };
+    if (int rc = quiet ? quietly(c, kQuietCounters | kQuietCostPerm, body) : body()) return rc;
+    if (!quiet) c->let_timed = true;
+    c->let_built();
     BH_HIP(c, hipGetLastError());
     return BH_OK;
 }
@@ -2208,46 +2141,23 @@ static int let_build(bh_ctx *c, bool quiet, const char *who)
 int bh_let_build(bh_ctx *c) { return let_build(c, false, "bh_let_build"); }
 int bh_let_build_quiet(bh_ctx *c) { return let_build(c, true, "bh_let_build_quiet"); }
 
-int bh_let_walk(bh_ctx *c)
+// the walks of a built LET context; an integrating one is a step
+static int let_walk(bh_ctx *c, const char *who, bool integrate, int part)
 {
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_walk: call bh_let_configure first");
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_walk before bh_let_build");
+    if (int rc = let_check(c, who, kLetTree)) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    int rc = enqueue_walk(c, true, false);
-    if (rc) return rc;
-    c->steps_done += 1;
-    return BH_OK;
-}
-
-// The forest walk in two launches, so that the all_to_all of the LETs can run under the first:
-// bh_let_walk_local needs only bh_let_build's local tree; bh_let_walk_remote needs the received
-// blocks, adds their contribution and finishes the step (integrate != 0) or just the forces.
-int bh_let_walk_local(bh_ctx *c)
-{
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_walk_local: call bh_let_configure first");
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_walk_local before bh_let_build");
-    BH_HIP(c, hipSetDevice(c->device));
-    return enqueue_walk(c, false, false, 1);
-}
-
-int bh_let_walk_remote(bh_ctx *c, int32_t integrate)
-{
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_walk_remote: call bh_let_configure first");
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_walk_remote before bh_let_build");
-    BH_HIP(c, hipSetDevice(c->device));
-    int rc = enqueue_walk(c, integrate != 0, false, 2);
-    if (rc) return rc;
+    if (int rc = enqueue_walk(c, integrate, false, part)) return rc;
     if (integrate) c->steps_done += 1;
     return BH_OK;
 }
 
-int bh_let_forces(bh_ctx *c)
-{
-    if (!c || !c->let_mode) return fail(c, BH_ERR_STATE, "bh_let_forces: call bh_let_configure first");
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_forces before bh_let_build");
-    BH_HIP(c, hipSetDevice(c->device));
-    return enqueue_walk(c, false, false);
-}
+int bh_let_walk(bh_ctx *c) { return let_walk(c, "bh_let_walk", true, 0); }
+int bh_let_forces(bh_ctx *c) { return let_walk(c, "bh_let_forces", false, 0); }
+// The forest walk in two launches, so that the all_to_all of the LETs can run under the first:
+// bh_let_walk_local needs only bh_let_build's local tree; bh_let_walk_remote needs the received
+// blocks, adds their contribution and finishes the step (integrate != 0) or just the forces.
+int bh_let_walk_local(bh_ctx *c) { return let_walk(c, "bh_let_walk_local", false, 1); }
+int bh_let_walk_remote(bh_ctx *c, int32_t integrate) { return let_walk(c, "bh_let_walk_remote", integrate != 0, 2); }
 
 // ---- diagnostics of the distributed step (bh_diag.hpp: forest_potential_f32_kernel and the reductions) ----------------
 // The forest the last bh_let_build left and the caller completed with the peers' blocks, walked by the potential kernel: it
@@ -2255,18 +2165,16 @@ int bh_let_forces(bh_ctx *c)
 // force walk's.
 static int let_diag_check(bh_ctx *c, const char *what)
 {
-    if (!c->let_mode)
-        return fail(c, BH_ERR_STATE, std::string(what) + ": LET mode only (bh_let_configure; BH_PRECISION_F32 / MIXED) -- "
-                                     "a single context has bh_compute_potential / bh_energy");
-    return BH_OK;
+    return c->let_mode ? BH_OK : fail(c, BH_ERR_STATE, std::string(what) + ": LET mode only (bh_let_configure; BH_PRECISION_F32 / MIXED) -- "
+                                                       "a single context has bh_compute_potential / bh_energy");
 }
 
 int bh_let_potential(bh_ctx *c)
 {
     if (!c) return BH_ERR_ARG;
     if (int rc = let_diag_check(c, "bh_let_potential")) return rc;
-    if (!c->tree_valid) return fail(c, BH_ERR_STATE, "bh_let_potential before bh_let_build");
-    if (c->let_moved) return fail(c, BH_ERR_STATE, "bh_let_potential: the bodies have moved since the last bh_let_build");
+    if (!c->is.tree_valid) return fail(c, BH_ERR_STATE, "bh_let_potential before bh_let_build");
+    if (c->is.let_moved) return fail(c, BH_ERR_STATE, "bh_let_potential: the bodies have moved since the last bh_let_build");
     BH_HIP(c, hipSetDevice(c->device));
     int rc = diag_alloc(c);
     if (!rc && c->n > 0) {
@@ -2276,7 +2184,7 @@ int bh_let_potential(bh_ctx *c)
         BH_HIP(c, hipGetLastError());
     }
     if (!rc) rc = check_overflow(c);
-    c->phi_current = rc == BH_OK;
+    c->potential_computed(rc == BH_OK);
     return rc;
 }
 
@@ -2284,22 +2192,14 @@ int bh_let_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
 {
     if (!c || !phi) return fail(c, BH_ERR_ARG, "bh_let_get_potential: null array");
     if (int rc = let_diag_check(c, "bh_let_get_potential")) return rc;
-    if (!c->phi_current) return fail(c, BH_ERR_STATE, "bh_let_get_potential: no potential of the current state (bh_let_potential)");
-    BH_HIP(c, hipSetDevice(c->device));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    const int64_t n = c->n;
-    if (n == 0) return BH_OK;
-    BH_HIP(c, hipMemcpy(phi, c->phi, n * sizeof(double), hipMemcpyDeviceToHost));
-    int rc = to_caller_order(c, phi, 1);
-    if (rc || !counts) return rc;
-    return counts_to_caller_order(c, c->phi_counts, counts);
+    return download_potential(c, phi, counts, "bh_let_get_potential: no potential of the current state (bh_let_potential)");
 }
 
 int bh_let_energy(bh_ctx *c, double *sums)
 {
     if (!c || !sums) return fail(c, BH_ERR_ARG, "bh_let_energy: null argument");
     if (int rc = let_diag_check(c, "bh_let_energy")) return rc;
-    if (!c->phi_current) { if (int rc = bh_let_potential(c)) return rc; }
+    if (!c->is.phi_current) { if (int rc = bh_let_potential(c)) return rc; }
     BH_HIP(c, hipSetDevice(c->device));
     double q[kDiagQuantities];
     if (int rc = energy_sums(c, q)) return rc;
@@ -2312,7 +2212,7 @@ int bh_set_ids(bh_ctx *c, const int64_t *ids)
 {
     if (!c || !ids) return fail(c, BH_ERR_ARG, "bh_set_ids: null argument");
     if (!c->gid) return fail(c, BH_ERR_STATE, "bh_set_ids: fp32 and mixed precision only");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, "bh_set_ids before bh_upload");
+    if (int rc = need_upload(c, "bh_set_ids before bh_upload")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     BH_HIP(c, hipMemcpy(c->gid, ids, c->n * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -2333,7 +2233,7 @@ static int check_cuts(bh_ctx *c, const bh_orb_cuts *cuts, const char *who)
 {
     if (!c || !cuts) return fail(c, BH_ERR_ARG, std::string(who) + ": null argument");
     if (c->tree64()) return fail(c, BH_ERR_STATE, std::string(who) + ": fp32 and mixed precision only");
-    if (!c->uploaded) return fail(c, BH_ERR_STATE, std::string(who) + " before bh_upload");
+    if (int rc = need_upload(c, std::string(who) + " before bh_upload")) return rc;
     if (cuts->world < 1 || cuts->world > kMaxWorld || cuts->n_cuts != cuts->world - 1)
         return fail(c, BH_ERR_ARG, std::string(who) + ": world must be 1..64 and n_cuts = world - 1");
     return BH_OK;
@@ -2354,8 +2254,8 @@ int bh_orb_histogram(bh_ctx *c, const bh_orb_cuts *cuts, int32_t level, void **h
     if (c->n > 0) {
         // weights: the cost of the body's 64-body group in the last full walk; they are indexed by sorted
         // position, so the bodies are visited through the last build's permutation
-        const bool weighted = c->group_cost_valid && c->tree_valid;
-        const uint32_t *perm = weighted ? (c->cost_perm ? c->cost_perm : c->perm) : nullptr;   // (the last force walk's order)
+        const bool weighted = c->last.group_cost_valid && c->is.tree_valid;
+        const uint32_t *perm = weighted ? (c->last.cost_perm ? c->last.cost_perm : c->perm) : nullptr;   // (the last force walk's order)
         const uint32_t *cost = weighted ? c->group_cost : nullptr;
         const unsigned g = blocks_for(c->n, kBlock);
         with_state(c, [&](auto r2) {
@@ -2390,7 +2290,7 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
     const int64_t n = c->n;
     const int W = cuts->world;
     for (int r = 0; r < W; ++r) send_counts[r] = 0;
-    c->tree_valid = false;                                  // the sort buffers are reused from here on
+    c->migration_packed();                                  // the sort buffers are reused from here on
     if (n == 0) { BH_HIP(c, hipStreamSynchronize(c->stream)); return BH_OK; }
     hipStream_t st = c->stream;
     const unsigned g = blocks_for(n, kBlock);
@@ -2401,7 +2301,7 @@ int bh_migrate_pack(bh_ctx *c, const bh_orb_cuts *cuts, int64_t *send_counts)
     });
     // one stable radix pass on the destination rank (< 64 < 256): slots grouped by destination, slot order kept
     const int cur = enqueue_lsd_passes<kSortItems>(st, c->keys, c->vals, c->radix_counts, c->bsum_sort, n, kSortBits, false);
-    const uint32_t *orig = c->orig_identity ? nullptr : c->orig;
+    const uint32_t *orig = c->is.orig_identity ? nullptr : c->orig;
     with_state(c, [&](auto r2) {
         using Real2 = decltype(r2);
         using Real = decltype(r2.x);
@@ -2450,7 +2350,7 @@ int bh_migrate_unpack(bh_ctx *c, int64_t n_new)
         BH_HIP(c, hipGetLastError());
     }
     c->n = n_new;
-    forget_body_set(c);                                       // (arrival order is the caller order from here on)
+    c->bodies_replaced();                                     // (arrival order is the caller order from here on)
     return BH_OK;
 }
 

@@ -20,6 +20,7 @@ from gpu_nbody_simulation_amd import _lib, initial_conditions as IC, project  # 
 from gpu_nbody_simulation_amd.engine import FLAG_WALK_PORTABLE, FLAG_WALK_STATS  # noqa: E402
 import field_ref as FR  # noqa: E402
 import parity_classes as PC  # noqa: E402
+import quiet_case as QC  # noqa: E402
 
 P = G.Precision
 ALL = [P.F64_EXACT, P.F64, P.MIXED, P.F32]
@@ -240,6 +241,14 @@ def test_field_calls_do_not_perturb_the_run(prec, n_threads):
         assert (s1.last_step_ms, s1.walk_ms, s1.build_ms) == pytest.approx((s0.last_step_ms, s0.walk_ms, s0.build_ms), rel=1e-4)
         if flags:
             assert np.array_equal(c0, e.interaction_counts())
+
+
+@pytest.mark.parametrize("prec,n_threads", QC.CASES, ids=QC.IDS)
+def test_field_calls_do_not_perturb_the_stats_of_the_last_step(prec, n_threads):
+    """tests/quiet_case.py: a first build by the LSD passes, the field's quiet build by the bucket sort; the walk counters are
+    the force walk's (BH_FLAG_WALK_STATS)."""
+    pts = FR.points_around(QC.bodies()[1], 500, 2)
+    QC.check(prec, n_threads, lambda e: e.field(pts, with_counts=True), flags=0 if prec == P.F64_EXACT else FLAG_WALK_STATS)
 
 
 # ---- 6. edges ----------------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ from gpu_nbody_simulation_amd.engine import (FLAG_LDS_STACK, FLAG_WALK_NO_SPLIT,
 from direct_ref import same_bits  # noqa: E402
 import field_ref as FR  # noqa: E402
 import soft_ref as SR  # noqa: E402
+import quiet_case as QC  # noqa: E402
 from let_ranks import EmulatedRanks  # noqa: E402
 
 P = G.Precision
@@ -505,3 +506,16 @@ def test_softened_diagnostics_do_not_perturb_the_trajectory(prec):
                     e.force_check(np.arange(0, 4096, 64))
             runs.append(e.download() + (e.stats().walk_launches,))
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1]) and runs[0][2] == runs[1][2]
+
+
+# (BH_PRECISION_F64_EXACT takes no softening length: bh_set_softening refuses it, test_errors_and_state)
+@pytest.mark.parametrize("prec,n_threads", [c for c in QC.CASES if c[0] != P.F64_EXACT], ids=[i for i in QC.IDS if "EXACT" not in i])
+def test_softened_diagnostics_do_not_perturb_the_stats_of_the_last_step(prec, n_threads):
+    """tests/quiet_case.py: a first build by the LSD passes, the three quiet builds by the bucket sort."""
+    pts = FR.points_around(QC.bodies()[1], 256, 1)
+
+    def diagnostics(e):
+        e.energy()
+        e.field(pts)
+        e.force_check(np.arange(0, QC.N, 64))
+    QC.check(prec, n_threads, diagnostics, softening=EPS)
