@@ -118,6 +118,11 @@ SIGNATURES = {
     "bh_drift": (C.c_int, [_ctx, C.c_double]),
     "bh_timestep": (C.c_int, [_ctx, C.c_double, C.c_double, C.POINTER(bh_timestep_t)]),
     "bh_step_kdk": (C.c_int, [_ctx, C.c_int32]),
+    "bh_moment_map": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int64)]),
+    "bh_moment_map_max": (C.c_int, [_ctx, _dp]),
+    "bh_moment_map_deposit": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp),
+                                        C.POINTER(C.c_int64)]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

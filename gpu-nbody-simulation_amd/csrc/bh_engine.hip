@@ -24,6 +24,7 @@
 #include "bh_let.hpp"
 #include "bh_migrate.hpp"
 #include "bh_split.hpp"
+#include "bh_moments.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
 
@@ -132,6 +133,12 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     double *diag_part = nullptr, *diag_out = nullptr;
     // the split operators (bh_split.hpp; is.forces_current): the records of bh_timestep are allocated on first use
     TsRecord *ts_part = nullptr, *ts_out = nullptr;
+    // moment maps (bh_moments.hpp), allocated on first use: the first pass's record, the body counter, and the 4-plane int64
+    // grid, which grows to the largest map asked for (map_cells of them per plane)
+    MapMax *map_max = nullptr;
+    unsigned long long *map_count = nullptr;
+    long long *map_planes = nullptr;
+    int64_t map_cells = 0;
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -1369,6 +1376,165 @@ int bh_step_kdk(bh_ctx *c, int32_t nsteps)
     BH_HIP(c, hipEventRecord(c->ev_step[1], c->stream));
     steps_enqueued(c, nsteps, want);
     c->forces_computed(forces_cover_all(c));
+    return BH_OK;
+}
+
+// ---- moment maps (bh_moments.hpp).  They read pos / vel / mass as they lie in memory and write buffers of their own: no
+// tree, no record of bh_run_state.hpp, so a step before and after runs bit for bit as it would have.
+static int map_check(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme)
+{
+    const std::string w(who);
+    if (!box) return fail(c, BH_ERR_ARG, w + ": null box");
+    if (nx < 1 || ny < 1) return fail(c, BH_ERR_ARG, w + ": nx and ny must be at least 1");
+    if ((int64_t)nx * ny > kMapMaxCells)
+        return fail(c, BH_ERR_ARG, w + ": nx * ny exceeds BH_MAP_MAX_CELLS = " + std::to_string(kMapMaxCells));
+    if (scheme != BH_MAP_NGP && scheme != BH_MAP_CIC) return fail(c, BH_ERR_ARG, w + ": scheme must be BH_MAP_NGP or BH_MAP_CIC");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(box[k])) return fail(c, BH_ERR_ARG, w + ": the box is not finite");
+    if (!(box[0] < box[1]) || !(box[2] < box[3])) return fail(c, BH_ERR_ARG, w + ": the box is empty (needs xmin < xmax and ymin < ymax)");
+    if (!std::isfinite(box[1] - box[0]) || !std::isfinite(box[3] - box[2]) || !std::isfinite((double)nx / (box[1] - box[0])) ||
+        !std::isfinite((double)ny / (box[3] - box[2])))
+        return fail(c, BH_ERR_ARG, w + ": the box's extent or the cells per unit length overflow fp64");
+    return need_upload(c, w + " before bh_upload/bh_initialize");
+}
+
+static int map_alloc(bh_ctx *c, int64_t cells)
+{
+    if (!c->map_max) {
+        int rc = dev_alloc(c, &c->map_max, 1);
+        if (!rc) rc = dev_alloc(c, &c->map_count, 1);
+        if (rc) { dev_free(c, c->map_max); dev_free(c, c->map_count); c->map_max = nullptr; c->map_count = nullptr; return rc; }
+    }
+    if (cells > c->map_cells) {
+        dev_free(c, c->map_planes);
+        c->map_planes = nullptr;
+        c->map_cells = 0;
+        if (int rc = dev_alloc(c, &c->map_planes, (size_t)kMapPlanes * cells)) return rc;
+        c->map_cells = cells;
+    }
+    return BH_OK;
+}
+
+// pass 1: the four maxima on the host when this returns; BH_ERR_ARG when a body is not finite
+static int map_maxima(bh_ctx *c, const char *who, double (&maxabs)[kMapPlanes])
+{
+    for (double &v : maxabs) v = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = map_alloc(c, 0)) return rc;
+    BH_HIP(c, hipMemsetAsync(c->map_max, 0, sizeof(MapMax), c->stream));
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        using Real = decltype(r2.x);
+        hipLaunchKernelGGL((moment_max_kernel<Real2, Real>), dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream,
+                           static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass),
+                           c->n, c->map_max);
+    });
+    BH_HIP(c, hipGetLastError());
+    MapMax r{};
+    BH_HIP(c, hipMemcpyAsync(&r, c->map_max, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    if (r.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a moment m v, m |v|^2 that "
+                                   "overflows fp64)");
+    for (int p = 0; p < kMapPlanes; ++p) std::memcpy(&maxabs[p], &r.bits[p], sizeof(double));
+    return BH_OK;
+}
+
+// ceil(log2(max(n, 1)))
+static int map_log2_ceil(int64_t n)
+{
+    int L = 0;
+    while (((int64_t)1 << L) < n) ++L;
+    return L;
+}
+
+// pass 2 with the exponents e: the grid stays on the device (map_planes), *n_deposited on the host.  The exponents must
+// cover this context's own maxima and body count -- else a contribution or a sum could leave int64.
+static int map_deposit(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *e,
+                       const double (&maxabs)[kMapPlanes], int64_t *n_deposited)
+{
+    const int L = map_log2_ceil(c->n);
+    for (int p = 0; p < kMapPlanes; ++p) {
+        int E = 0;
+        if (maxabs[p] != 0.0) (void)std::frexp(maxabs[p], &E);
+        if (maxabs[p] != 0.0 && (int64_t)E + e[p] + L > 62)
+            return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
+                                       " is too large for this context's bodies (at most " + std::to_string(62 - E - L) + ")");
+    }
+    const int64_t cells = (int64_t)nx * ny;
+    if (int rc = map_alloc(c, cells)) return rc;
+    BH_HIP(c, hipMemsetAsync(c->map_planes, 0, (size_t)kMapPlanes * cells * sizeof(long long), c->stream));
+    BH_HIP(c, hipMemsetAsync(c->map_count, 0, sizeof(unsigned long long), c->stream));
+    if (c->n > 0) {
+        MapGrid g{};
+        g.xmin = box[0]; g.xmax = box[1]; g.ymin = box[2]; g.ymax = box[3];
+        g.sx = (double)nx / (box[1] - box[0]);
+        g.sy = (double)ny / (box[3] - box[2]);
+        g.nx = nx; g.ny = ny;
+        for (int p = 0; p < kMapPlanes; ++p) g.e[p] = e[p];
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            dispatch([&](auto cic) {
+                hipLaunchKernelGGL((moment_deposit_kernel<decltype(cic)::value, Real2, Real>), dim3(blocks_for(c->n, kBlock)), dim3(kBlock),
+                                   0, c->stream, static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
+                                   static_cast<const Real *>(c->mass), c->n, g, c->map_planes, c->map_count);
+            }, scheme == BH_MAP_CIC);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    unsigned long long cnt = 0;
+    BH_HIP(c, hipMemcpyAsync(&cnt, c->map_count, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    *n_deposited = (int64_t)cnt;
+    return BH_OK;
+}
+
+int bh_moment_map_max(bh_ctx *c, double *maxabs)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_moment_map_max: null output");
+    if (int rc = need_upload(c, "bh_moment_map_max before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kMapPlanes];
+    if (int rc = map_maxima(c, "bh_moment_map_max", m)) return rc;
+    std::copy(m, m + kMapPlanes, maxabs);
+    return BH_OK;
+}
+
+int bh_moment_map_deposit(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *exponents,
+                          void **planes_dev, int64_t *n_deposited)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!exponents || !planes_dev || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map_deposit: null argument");
+    if (int rc = map_check(c, "bh_moment_map_deposit", box, nx, ny, scheme)) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kMapPlanes];
+    if (int rc = map_maxima(c, "bh_moment_map_deposit", m)) return rc;
+    if (int rc = map_deposit(c, "bh_moment_map_deposit", box, nx, ny, scheme, exponents, m, n_deposited)) return rc;
+    *planes_dev = c->map_planes;
+    return BH_OK;
+}
+
+int bh_moment_map(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, int64_t *planes, int32_t *exponents,
+                  int64_t *n_deposited)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map: null argument");
+    if (int rc = map_check(c, "bh_moment_map", box, nx, ny, scheme)) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kMapPlanes];
+    if (int rc = map_maxima(c, "bh_moment_map", m)) return rc;
+    const int L = map_log2_ceil(c->n);
+    int32_t e[kMapPlanes];
+    for (int p = 0; p < kMapPlanes; ++p) {
+        int E = 0;
+        e[p] = 0;
+        if (m[p] != 0.0) { (void)std::frexp(m[p], &E); e[p] = 62 - E - L; }
+    }
+    if (int rc = map_deposit(c, "bh_moment_map", box, nx, ny, scheme, e, m, n_deposited)) return rc;
+    BH_HIP(c, hipMemcpy(planes, c->map_planes, (size_t)kMapPlanes * nx * ny * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kMapPlanes, exponents);
     return BH_OK;
 }
 

@@ -563,6 +563,50 @@ class LetStepper:
         self.check()
         return combine_energy_sums(rows.reshape(-1, 9).tolist())
 
+    def moment_map(self, box, nx: int, ny: int, scheme: str = "cic", raw: bool = False):
+        """BhMomentMap of the WHOLE system (engine.moment_map), the same bits on every rank and the same bits as one
+        engine's map of the same bodies.  all_reduce MAX of the ranks' four maxima and SUM of their body counts, from
+        which every rank derives the same exponents; each rank deposits its own bodies in fixed point; one
+        all_reduce(SUM) of the int64 grid -- integer sums are exact in any order.  No rank holds more than its own bodies
+        and one grid.  Collective: every rank must call it with the same box, grid and scheme (checked: ValueError on
+        every rank if not).  Reads the state only."""
+        import numpy as np
+        from .engine import MAP_SCHEMES, moment_exponents, moment_map_from_planes
+        b = np.ascontiguousarray(box, dtype=np.float64).reshape(-1)
+        if len(b) != 4 or scheme not in MAP_SCHEMES:
+            raise ValueError(f"box = (xmin, xmax, ymin, ymax), scheme one of {sorted(MAP_SCHEMES)}")
+        nx, ny = int(nx), int(ny)
+        on_dev = self.lbounds.is_cuda and not self._staged()      # RCCL takes device tensors, gloo host tensors
+        dev = self.lbounds.device if on_dev else "cpu"
+        many = dist.is_initialized() and self.world > 1
+        # a rank with a non-finite body reports it through the collective, so that all raise together
+        try:
+            mx, bad = self.eng.moment_map_max(), None
+        except Exception as err:                                  # noqa: BLE001 -- re-raised below, after the collective
+            mx, bad = np.zeros(4), err
+        # the same arguments everywhere: min and max of (box, nx, ny, scheme) agree exactly when all ranks passed the same
+        args = torch.tensor([*b, float(nx), float(ny), float(MAP_SCHEMES[scheme])], dtype=torch.float64, device=dev)
+        hi = torch.cat([args, -args, torch.tensor([*mx, 1.0 if bad else 0.0], dtype=torch.float64, device=dev)])
+        cnt = torch.tensor([int(self.eng.n)], dtype=torch.int64, device=dev)
+        if many:
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+        hi = hi.cpu()
+        k = args.numel()
+        if bad is not None or float(hi[-1]) != 0.0:
+            raise bad if bad is not None else ValueError("moment_map: another rank has a non-finite body")
+        if not (torch.equal(hi[:k], args.cpu()) and torch.equal(hi[k:2 * k], -args.cpu())):      # (a NaN fails too)
+            raise ValueError(f"moment_map: the ranks disagree on the box, the grid or the scheme (rank {self.rank} has "
+                             f"{b.tolist()}, {nx} x {ny}, {scheme})")
+        e = moment_exponents(hi[2 * k:2 * k + 4].numpy(), int(cnt.item()))
+        g, n_dep = self.eng.moment_map_deposit(b, nx, ny, scheme, e)
+        if not isinstance(g, torch.Tensor):                       # stand-in engines hand a tensor over directly
+            g = wrap_device(g, 4 * ny * nx, "<i8", self.device)
+        g = self._all_reduce_(g, dist.ReduceOp.SUM)
+        nd = self._all_reduce_(torch.tensor([int(n_dep)], dtype=torch.int64, device=dev), dist.ReduceOp.SUM)
+        planes = g.cpu().numpy().reshape(4, ny, nx).copy()
+        return moment_map_from_planes(planes, e, b, scheme, int(nd.item()), raw)
+
     @property
     def ids(self):
         """Global identifiers of this rank's bodies in the order download() returns them."""

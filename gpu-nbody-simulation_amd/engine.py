@@ -119,6 +119,57 @@ class BhForceError:
     rms: float                   # RMS |F_tree - F_dir| / RMS |F_dir|
 
 
+MAP_SCHEMES = {"ngp": 0, "cic": 1}      # BH_MAP_NGP, BH_MAP_CIC
+MAP_MAX_CELLS = 1 << 24                 # BH_MAP_MAX_CELLS
+
+
+@dataclass
+class BhMomentMap:
+    """Moment maps of the current state on nx x ny cells over box (moment_map): fp64 arrays (ny, nx), y the outer axis.
+    mass, px, py, k2 are the fixed-point sums times 2^-exponent (sums beyond 2^53 units round to fp64 there; the scaling
+    itself is exact); the others are derived from them, NaN in a cell without mass except sigma, which is 0 there."""
+    mass: np.ndarray             # sum m
+    px: np.ndarray               # sum m vx
+    py: np.ndarray               # sum m vy
+    k2: np.ndarray               # sum m (vx^2 + vy^2)
+    sigma: np.ndarray            # surface density: mass / cell area
+    vx: np.ndarray               # mass-weighted mean velocity: px / mass
+    vy: np.ndarray
+    dispersion: np.ndarray       # sqrt(max(k2 / mass - vx^2 - vy^2, 0))
+    box: tuple                   # (xmin, xmax, ymin, ymax)
+    scheme: str                  # "ngp" or "cic"
+    n_deposited: int             # bodies with at least one corner inside the grid
+    planes: np.ndarray | None = None      # raw=True: the int64 sums (4, ny, nx) ...
+    exponents: np.ndarray | None = None   # ... and their exponents: value = planes * 2^-exponent
+
+
+def moment_exponents(maxabs, n_total: int) -> np.ndarray:
+    """The four exponents 62 - E_p - L of a moment map from the maxima max |q_p| (bh_moment_map_max, combined over the
+    ranks with MAX) and the body count of the whole system: max < 2^E_p, L = ceil(log2(max(n, 1))); 0 where the maximum
+    is 0."""
+    m = np.asarray(maxabs, dtype=np.float64).reshape(4)
+    L = 0 if n_total <= 1 else (int(n_total) - 1).bit_length()
+    _, E = np.frexp(m)
+    return np.where(m == 0.0, 0, 62 - E - L).astype(np.int32)
+
+
+def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int, raw: bool = False) -> BhMomentMap:
+    """BhMomentMap of the int64 sums (4, ny, nx) and their exponents."""
+    planes = np.asarray(planes, dtype=np.int64)
+    _, ny, nx = planes.shape
+    box = tuple(float(b) for b in box)
+    mass, px, py, k2 = (np.ldexp(planes[p].astype(np.float64), -int(exponents[p])) for p in range(4))
+    area = ((box[1] - box[0]) / nx) * ((box[3] - box[2]) / ny)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vx, vy = px / mass, py / mass
+        disp = np.sqrt(np.maximum(k2 / mass - vx * vx - vy * vy, 0.0))
+    empty = mass == 0.0
+    for a in (vx, vy, disp):
+        a[empty] = np.nan
+    return BhMomentMap(mass, px, py, k2, mass / area, vx, vy, disp, box, scheme, int(n_deposited),
+                       planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+
+
 # (q as exact fractions: ceil(q n) in integers, so that no rounding of q * n moves an index)
 _QUANTILES = {"median": (1, 2), "p90": (9, 10), "p99": (99, 100), "p999": (999, 1000)}
 
@@ -396,6 +447,49 @@ class BarnesHutEngine:
         self._check(self._lib.bh_field_at(self._h, _dptr(p) if k else None, k, _dptr(acc), _dptr(phi),
                                           cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if with_counts else None))
         return (acc[:k], phi[:k], cnt[:k]) if with_counts else (acc[:k], phi[:k])
+
+    # -- moment maps ----------------------------------------------------------------------------
+    @staticmethod
+    def _map_args(box, scheme):
+        b = np.ascontiguousarray(box, dtype=np.float64).reshape(-1)
+        if len(b) != 4:
+            raise ValueError("box = (xmin, xmax, ymin, ymax)")
+        if scheme not in MAP_SCHEMES:
+            raise ValueError(f"scheme must be one of {sorted(MAP_SCHEMES)}")
+        return b, MAP_SCHEMES[scheme]
+
+    def moment_map(self, box, nx: int, ny: int, scheme: str = "cic", raw: bool = False) -> BhMomentMap:
+        """Surface density, mean velocity and velocity dispersion of the current state on nx x ny cells over
+        box = (xmin, xmax, ymin, ymax), deposited on the device ("ngp": nearest grid point, "cic": cloud in cell) in
+        fixed point: the same bodies give the same bits in any order.  Reads the state only; the run is not perturbed.
+        raw: also the int64 planes and their exponents."""
+        b, sch = self._map_args(box, scheme)
+        nx, ny = int(nx), int(ny)
+        ok = nx >= 1 and ny >= 1 and nx * ny <= MAP_MAX_CELLS          # (else the call refuses before it writes)
+        planes = np.zeros((4, ny, nx) if ok else (4, 1, 1), dtype=np.int64)
+        e = np.zeros(4, dtype=np.int32)
+        nd = C.c_int64()
+        self._check(self._lib.bh_moment_map(self._h, _dptr(b), nx, ny, sch, planes.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nd)))
+        return moment_map_from_planes(planes, e, b, scheme, nd.value, raw)
+
+    def moment_map_max(self) -> np.ndarray:
+        """max |m|, |m vx|, |m vy|, |m (vx^2 + vy^2)| over this context's bodies (zeros without bodies)."""
+        m = np.zeros(4)
+        self._check(self._lib.bh_moment_map_max(self._h, _dptr(m)))
+        return m
+
+    def moment_map_deposit(self, box, nx: int, ny: int, scheme: str, exponents):
+        """(device pointer of the int64 grid 4 x ny x nx, n_deposited): this context's bodies deposited with the caller's
+        exponents (moment_exponents); the grid stays valid until the next moment-map call."""
+        b, sch = self._map_args(box, scheme)
+        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+        if len(e) != 4:
+            raise ValueError("four exponents")
+        p, nd = C.c_void_p(), C.c_int64()
+        self._check(self._lib.bh_moment_map_deposit(self._h, _dptr(b), int(nx), int(ny), sch,
+                                                    e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p), C.byref(nd)))
+        return p.value, nd.value
 
     # -- tree output ------------------------------------------------------------------------
     def export_tree(self):

@@ -75,7 +75,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      positions_file: str | None = None, energy_file: str | None = None, energy_every: int = 0,
                      force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
                      field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0,
-                     integrator: str = "euler"):
+                     integrator: str = "euler", density_file: str | None = None, density_grid=None, density_box=None,
+                     density_scheme: str = "cic"):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -93,6 +94,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     cell-centred field_grid = (NX, NY) grid over field_box = (xmin, xmax, ymin, ymax) (None: the bounding box of the final
     positions): the line `# x,y,ax,ay,phi`, then one row per point (%.17g), y the outer axis.  Not part of
     gpu_parallel_duration_us.
+    density_file: after the last step, also write the moment maps of the final state (BarnesHutEngine.moment_map, scheme
+    density_scheme) on the density_grid = (NX, NY) cells over density_box (None: the bounding box of the final positions):
+    the line `# x,y,sigma,vx,vy,dispersion`, then one row per cell centre (%.17g; nan in a cell without mass), y the outer
+    axis -- the points of field_file for the same grid and box.  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -200,6 +205,14 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, field_file) if not os.path.isabs(field_file) else field_file, "w") as f:
                 f.write("# x,y,ax,ay,phi\n")
                 f.write("".join("%.17g,%.17g,%.17g,%.17g,%.17g\n" % (x, y, a[0], a[1], q) for (x, y), a, q in zip(pts, acc, phi)))
+        if density_file is not None:
+            pts = field_grid_points(density_grid, density_box, pos)
+            box = density_box if density_box is not None else (pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max())
+            mm = eng.moment_map(box, int(density_grid[0]), int(density_grid[1]), density_scheme)
+            cols = [a.reshape(-1) for a in (mm.sigma, mm.vx, mm.vy, mm.dispersion)]
+            with open(os.path.join(out_dir, density_file) if not os.path.isabs(density_file) else density_file, "w") as f:
+                f.write("# x,y,sigma,vx,vy,dispersion\n")
+                f.write("".join("%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n" % (x, y, *r) for (x, y), r in zip(pts, zip(*cols))))
         if traj is not None:
             traj.close()
         for f in (energy, ferr):
@@ -261,6 +274,15 @@ def _parse(argv):
                     help="cells of the cell-centred grid of --field-file (row-major rows, y the outer axis)")
     ap.add_argument("--field-box", type=float, nargs=4, default=None, metavar=("XMIN", "XMAX", "YMIN", "YMAX"),
                     help="what the grid covers (default: the bounding box of the final positions)")
+    ap.add_argument("--density-file", default=None, metavar="PATH",
+                    help="after the last step, also write x,y,sigma,vx,vy,dispersion (surface density, mean velocity, velocity "
+                         "dispersion) of the cells of the --density-grid")
+    ap.add_argument("--density-grid", type=int, nargs=2, default=None, metavar=("NX", "NY"),
+                    help="cells of --density-file (rows of cell centres, y the outer axis: the points of --field-grid)")
+    ap.add_argument("--density-box", type=float, nargs=4, default=None, metavar=("XMIN", "XMAX", "YMIN", "YMAX"),
+                    help="what the cells cover (default: the bounding box of the final positions, as --field-box)")
+    ap.add_argument("--density-scheme", choices=["ngp", "cic"], default="cic",
+                    help="ngp: a body goes to the cell it is in; cic: to the four nearest cell centres, bilinearly")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -280,6 +302,10 @@ def _parse(argv):
         ap.error("--field-file and --field-grid go together")
     if a.field_box is not None and a.field_file is None:
         ap.error("--field-box needs --field-file")
+    if (a.density_file is None) != (a.density_grid is None):
+        ap.error("--density-file and --density-grid go together")
+    if a.density_box is not None and a.density_file is None:
+        ap.error("--density-box needs --density-file")
     if a.softening is not None:
         if not (a.softening >= 0.0 and a.softening < float("inf")):
             ap.error("--softening: the length must be finite and >= 0")
@@ -341,7 +367,8 @@ def main(argv=None) -> int:
         reference_compat=not a.no_compat, positions_file=a.positions_file, energy_file=a.energy_file,
         energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
         force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box,
-        softening=a.softening or 0.0, integrator=a.integrator)
+        softening=a.softening or 0.0, integrator=a.integrator, density_file=a.density_file, density_grid=a.density_grid,
+        density_box=a.density_box, density_scheme=a.density_scheme)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -392,6 +392,47 @@ int bh_drift(bh_ctx *ctx, double h);
 int bh_timestep(bh_ctx *ctx, double eta, double length, bh_timestep_t *out);
 int bh_step_kdk(bh_ctx *ctx, int32_t nsteps);
 
+/* --- moment maps: where the mass is, how it streams, how hot it is ----------------------------------------------------
+ * The reference draws its pictures on the host from the downloaded state (plot_2d.py); these deposit on the device, so a
+ * distributed run can map a system no rank holds.  Four moments of every body, each formed in fp64 in the written order
+ * (an fp32 state is widened first, exactly), on nx x ny cells over box = {xmin, xmax, ymin, ymax}, half open:
+ *     plane 0: m      plane 1: m * vx      plane 2: m * vy      plane 3: m * (vx * vx + vy * vy)
+ * With sx = nx / (xmax - xmin) (one division), and likewise in y:
+ *   BH_MAP_NGP: tx = (x - xmin) * sx; the whole body goes to cell (floor(tx), floor(ty)) when 0 <= tx < nx and x < xmax
+ *     (and the same in y), else nowhere.  A body exactly at xmax is outside.
+ *   BH_MAP_CIC: tx = (x - xmin) * sx - 0.5, ix = floor(tx), fx = tx - ix; the corners (ix, 1 - fx) and (ix + 1, fx), the
+ *     same in y, a corner's weight wx * wy.  Corners outside the grid are dropped, the others kept: a body within half a
+ *     cell of the box is partly inside.
+ *   Inside and outside are decided on the fp64 tx: a body at 1e300 converts to no index.
+ * Fixed point.  A first pass takes max |q_p| of every plane over the bodies; E_p is its frexp exponent (max < 2^E_p),
+ * L = ceil(log2(max(n, 1))) for the n bodies of the WHOLE system, and the plane's exponent is 62 - E_p - L (0 when the
+ * maximum is 0).  A contribution is (int64) rint(ldexp(q_p * (wx * wy), exponent)) (NGP: q_p itself), added with integer
+ * atomics: the sums cannot leave int64 (n contributions of at most 2^(62 - L)), and, integer addition being associative,
+ * they do not depend on the order of the bodies, the launch or the number of contexts whose grids are added -- the same
+ * system gives the same bits.  Every contribution is rounded once: a cell is off by at most half a unit of 2^-exponent
+ * per contribution it received.  value = planes * 2^-exponent.
+ * bh_moment_map: both passes and the download.  planes: 4 * ny * nx, plane-major, y the outer axis of a plane.
+ *   *n_deposited: the bodies with at least one corner inside.
+ * bh_moment_map_max: the first pass alone, maxabs[p] = max |q_p| over this context's bodies (0 without bodies).
+ * bh_moment_map_deposit: the second pass alone with the caller's exponents -- for a distributed map: the MAX of the
+ *   ranks' maxima and the SUM of their body counts give every rank the same exponents -- and the grid left on the device:
+ *   *planes_dev points at 4 * ny * nx int64, valid until the next moment-map call or bh_destroy.  Exponents too large for
+ *   this context's own maxima and body count are refused.
+ * Valid any time after bh_upload / bh_initialize / bh_migrate_unpack, in every precision, in LET mode too (the context's own
+ * bodies); they read the state arrays bh_download reads, build no tree and change nothing a step reads: the steps around
+ * them run bit for bit as they would have.  They wait for the stream.
+ * Errors: BH_ERR_ARG for a null pointer, nx or ny < 1, nx * ny > BH_MAP_MAX_CELLS, an unknown scheme, a box that is empty or
+ *   not finite (or whose extent overflows), and -- with a message that says so -- a body whose position, velocity or mass is
+ *   not finite or whose moment overflows fp64.  BH_ERR_STATE before any upload. */
+#define BH_MAP_NGP 0
+#define BH_MAP_CIC 1
+#define BH_MAP_MAX_CELLS 16777216
+int bh_moment_map(bh_ctx *ctx, const double box[4], int32_t nx, int32_t ny, int32_t scheme,
+                  int64_t *planes, int32_t exponents[4], int64_t *n_deposited);
+int bh_moment_map_max(bh_ctx *ctx, double maxabs[4]);
+int bh_moment_map_deposit(bh_ctx *ctx, const double box[4], int32_t nx, int32_t ny, int32_t scheme,
+                          const int32_t exponents[4], void **planes_dev, int64_t *n_deposited);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
