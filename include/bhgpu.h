@@ -191,7 +191,13 @@ const char *bh_build_info(void);
  * Masses: BH_PRECISION_F64_EXACT reproduces the reference bit for bit for POSITIVE masses (however small).  A mass of
  * exactly 0.0 is accepted, but QuadInsert takes a leaf whose mass is 0.0 for empty (project.cu:395-397): a massless
  * body is overwritten by a later arrival and subdivides an earlier one, an insertion-order-dependent tree that
- * this build does not reproduce -- here a massless body occupies its leaf like any other (and pulls nobody). */
+ * this build does not reproduce -- here a massless body occupies its leaf like any other (and pulls nobody).
+ * BH_PRECISION_F32 / BH_PRECISION_MIXED: the mass and the moments of a tree cell of two or more bodies are differences
+ * of fp64 prefix sums over ALL sorted bodies, so they carry an ABSOLUTE error of the order of H * 2^-53 times the total
+ * mass and the total moments sum |m x|, sum |m y| of the system (H ~ 44 additions between a term and a prefix sum; above
+ * 2,048 scan tiles 36 + one per 256 tiles).  That is far below the fp32 rounding of an ordinary cell's record; a cell
+ * LIGHTER than that relative to the whole system is not resolved -- its mass is that noise, its centre arbitrary, and
+ * whether the 1e-15f cut-off (project.cu:617) drops it is decided by the noise.  One-body cells take the body's own values. */
 int bh_upload(bh_ctx *ctx, const double *pos, const double *vel, const double *mass, int64_t n);
 int bh_download(bh_ctx *ctx, double *pos, double *vel);
 

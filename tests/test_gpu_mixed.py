@@ -17,6 +17,7 @@ from oracle import bh_oracle as O  # noqa: E402
 import gpu_nbody_simulation_amd as G  # noqa: E402
 from gpu_nbody_simulation_amd import initial_conditions as IC  # noqa: E402
 from test_gpu_let import EmulatedRanks, rel  # noqa: E402
+from nodes_ref import Twin  # noqa: E402
 
 
 def engine(n, precision=G.Precision.MIXED, **kw):
@@ -56,14 +57,15 @@ def test_mixed_accelerations_and_tree(kind, n):
     np.testing.assert_allclose(root["mass"], m.sum(), rtol=1e-6)
 
 
-@pytest.mark.parametrize("precision", [G.Precision.MIXED, G.Precision.F64_EXACT, G.Precision.F64])
+@pytest.mark.parametrize("precision", [G.Precision.MIXED, G.Precision.F32, G.Precision.F64_EXACT, G.Precision.F64])
 def test_fast_keys_equal_the_bisection_keys(precision):
     """keys_kernel takes a body's cell from one multiply per axis when the body is provably clear of every
     grid line and falls back to the reference's bisection otherwise.  Bodies placed EXACTLY on the
     bisection's own (rounded) midpoints, one ulp below and one ulp above them, on both axes, at every depth,
     and on the box corners: the exported tree is the oracle's, cell by cell and occupant by occupant.
     (Round 4: the exact modes take the same look-up, with child-index digits instead of curve digits; there the
-    centres of mass and masses are the reference's bit for bit as well.)"""
+    centres of mass and masses are the reference's bit for bit as well.  Precision.F32 sees the same points rounded to
+    float32; there and in MIXED mass and centre of every node are held to the bound derived in tests/nodes_ref.py.)"""
     rng = np.random.default_rng(17)
     corners = np.array([[-1.0, -1.0], [1.0, 1.0], [-1.0, 1.0], [1.0, -1.0]])
     lo, hi = corners.min(0), corners.max(0)
@@ -96,16 +98,22 @@ def test_fast_keys_equal_the_bisection_keys(precision):
     n = len(p)
     m = rng.uniform(0.5, 1.0, n) * 1e-12
     v = np.zeros((n, 2))
+    if precision == G.Precision.F32:
+        p, m = (a.astype(np.float32).astype(np.float64) for a in (p, m))
     with engine(n, precision=precision) as e:
         e.upload(p, v, m)
         e.build_tree()
         nodes, depth = e.export_tree()
     rn, rd = O.canonical_tree(O.build_tree(p, m, 21))
     assert len(nodes) == len(rn) and np.array_equal(depth, rd)
-    exact = precision != G.Precision.MIXED
+    exact = precision not in (G.Precision.MIXED, G.Precision.F32)
     for f in ("xmin", "xmax", "ymin", "ymax", "particle") + (("comx", "comy", "mass") if exact else ()):
         assert np.array_equal(nodes[f], rn[f]), f
     assert np.array_equal(nodes["child"] == -1, rn["child"] == -1)
+    if not exact:
+        res = Twin(p, m, 21).check(nodes, depth, mixed=precision == G.Precision.MIXED)
+        print(res)
+        assert res["nodes"] == len(rn) and res["undecided"] == 0 and res["unresolved"] == 0
 
 
 def test_mixed_keeps_displacements_below_fp32_resolution():
