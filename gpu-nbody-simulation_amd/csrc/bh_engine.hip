@@ -25,6 +25,7 @@
 #include "bh_migrate.hpp"
 #include "bh_split.hpp"
 #include "bh_moments.hpp"
+#include "bh_neighbours.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
 
@@ -159,6 +160,21 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     uint64_t *field_keys[2] = {nullptr, nullptr};
     double *field_phi = nullptr;
     uint32_t *field_order = nullptr, *field_counts = nullptr, *field_radix = nullptr, *field_rows = nullptr;
+    // neighbour queries (bh_neighbours.hpp), allocated on first use and grown as the field's block: one block for the search
+    // structure of up to nb_cap bodies, one for a launch of up to nb_rows queries with nb_entries list entries in all
+    char *nb_block = nullptr, *nb_qblock = nullptr;
+    int64_t nb_cap = 0, nb_rows = 0, nb_entries = 0;
+    uint64_t nb_bytes = 0, nb_qbytes = 0;
+    uint64_t *nb_keys[2] = {nullptr, nullptr}, *nb_pkeys[2] = {nullptr, nullptr};
+    uint32_t *nb_slot = nullptr, *nb_sidx = nullptr, *nb_radix = nullptr, *nb_rowsum = nullptr, *nb_order = nullptr, *nb_evals = nullptr;
+    double2 *nb_spos = nullptr, *nb_points = nullptr;
+    NbBox *nb_boxes = nullptr;
+    NbBounds *nb_bounds = nullptr;
+    double *nb_box = nullptr, *nb_d2 = nullptr;
+    int32_t *nb_off = nullptr;
+    int64_t *nb_idx = nullptr;
+    hipEvent_t nb_ev[4] = {nullptr, nullptr, nullptr, nullptr};    // around the build and around a launch's sort and search
+    double nb_build_ms = 0.0, nb_query_ms = 0.0;                    // of the last call (bh_neighbours_times)
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -1010,7 +1026,7 @@ void bh_destroy(bh_ctx *c)
     c->exp.destroy(c->n);
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
-    destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let);
+    destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1887,6 +1903,217 @@ int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel
         if (counts) BH_HIP(c, hipMemcpyAsync(counts + t0, c->field_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         BH_HIP(c, hipStreamSynchronize(c->stream));
     }
+    return BH_OK;
+}
+
+// ---- neighbour queries (bh_neighbours.hpp).  They read pos (and orig) as they lie in memory and write buffers of their own: no
+// force tree, no record of bh_run_state.hpp, no counter and no timing of the run, so a step before and after runs bit for bit as
+// it would have.
+constexpr int64_t kNbChunk = kFieldChunk;       // queries per launch: a point's index travels in its key word
+
+// the structure's block for n bodies and the launch block for `rows` queries of `entries` list entries in all
+static int nb_alloc(bh_ctx *c, int64_t n, int64_t rows, int64_t entries)
+{
+    auto carve = [](char *&b, auto **out, size_t count) {
+        using T = typename std::remove_reference<decltype(**out)>::type;
+        *out = reinterpret_cast<T *>(b);
+        b += (count * sizeof(T) + 15) / 16 * 16;
+    };
+    for (auto &e : c->nb_ev)
+        if (!e) BH_HIP(c, hipEventCreate(&e));
+    if (n > c->nb_cap) {
+        int64_t cap = 1024;
+        while (cap < n) cap <<= 1;
+        if (c->nb_block) {                                     // (the previous call has waited for its stream)
+            dev_free(c, c->nb_block);
+            c->device_bytes -= c->nb_bytes;
+            c->nb_block = nullptr; c->nb_cap = 0; c->nb_bytes = 0;
+        }
+        int32_t off[kNbMaxLevels + 1];
+        nb_levels(cap, off);
+        const size_t nodes = (size_t)off[kNbMaxLevels] + kNbMaxLevels;            // (n <= cap has at most a node more per level)
+        const size_t nbl = blocks_for(std::max(cap, kNbChunk), kBlock * kFieldSortItems);
+        const size_t bytes = (size_t)cap * (sizeof(double2) + 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + nodes * sizeof(NbBox) +
+                             ((size_t)kRadix * nbl + kRadix) * sizeof(uint32_t) + sizeof(NbBounds) + 4 * sizeof(double) +
+                             (kNbMaxLevels + 1) * sizeof(int32_t) + 16 * 12;
+        char *b = nullptr;
+        if (int rc = dev_alloc(c, &b, bytes)) return rc;
+        c->nb_block = b; c->nb_cap = cap; c->nb_bytes = bytes;
+        carve(b, &c->nb_spos, (size_t)cap); carve(b, &c->nb_boxes, nodes);
+        carve(b, &c->nb_keys[0], (size_t)cap); carve(b, &c->nb_keys[1], (size_t)cap);
+        carve(b, &c->nb_bounds, 1); carve(b, &c->nb_box, 4);
+        carve(b, &c->nb_slot, (size_t)cap); carve(b, &c->nb_sidx, (size_t)cap);
+        carve(b, &c->nb_radix, (size_t)kRadix * nbl); carve(b, &c->nb_rowsum, (size_t)kRadix);
+        carve(b, &c->nb_off, (size_t)kNbMaxLevels + 1);
+    }
+    if (rows > c->nb_rows || entries > c->nb_entries) {
+        int64_t cap = std::max<int64_t>(c->nb_rows, 1024);
+        while (cap < rows) cap <<= 1;
+        const int64_t ent = std::max(entries, c->nb_entries);
+        if (c->nb_qblock) {
+            dev_free(c, c->nb_qblock);
+            c->device_bytes -= c->nb_qbytes;
+            c->nb_qblock = nullptr; c->nb_rows = 0; c->nb_entries = 0; c->nb_qbytes = 0;
+        }
+        const size_t bytes = (size_t)cap * (sizeof(double2) + 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) +
+                             (size_t)ent * (sizeof(int64_t) + sizeof(double)) + 16 * 8;
+        char *b = nullptr;
+        if (int rc = dev_alloc(c, &b, bytes)) return rc;
+        c->nb_qblock = b; c->nb_rows = cap; c->nb_entries = ent; c->nb_qbytes = bytes;
+        carve(b, &c->nb_points, (size_t)cap); carve(b, &c->nb_pkeys[0], (size_t)cap); carve(b, &c->nb_pkeys[1], (size_t)cap);
+        carve(b, &c->nb_idx, (size_t)ent); carve(b, &c->nb_d2, (size_t)ent);
+        carve(b, &c->nb_order, (size_t)cap); carve(b, &c->nb_evals, (size_t)cap);
+    }
+    return BH_OK;
+}
+
+// bounds, keys, sort, sorted copies and boxes of the current state (n > 0); BH_ERR_ARG when a position is not finite.  *levels:
+// the levels of the hierarchy.
+static int nb_build(bh_ctx *c, const char *who, int *levels)
+{
+    hipStream_t st = c->stream;
+    const int64_t n = c->n;
+    const unsigned grid = blocks_for(n, kBlock);
+    const NbBounds empty{~0ull, 0ull, ~0ull, 0ull, 0ull};
+    BH_HIP(c, hipEventRecord(c->nb_ev[0], st));
+    BH_HIP(c, hipMemcpyAsync(c->nb_bounds, &empty, sizeof(empty), hipMemcpyHostToDevice, st));
+    BH_HIP(c, hipStreamSynchronize(st));                        // (`empty` lives on this stack)
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        hipLaunchKernelGGL((nb_bounds_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos), n, c->nb_bounds);
+    });
+    BH_HIP(c, hipGetLastError());
+    NbBounds got{};
+    BH_HIP(c, hipMemcpyAsync(&got, c->nb_bounds, sizeof(got), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (got.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body of the state has a non-finite position (found by the bounds pass)");
+    hipLaunchKernelGGL(nb_setup_kernel, dim3(1), dim3(1), 0, st, c->nb_bounds, n, c->nb_box, c->nb_off);
+    const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
+    static_assert(kFieldKeyBits % kSortBits == 0 && ((kFieldKeyBits / kSortBits) & 1) == 0, "the sorted keys end in the first array");
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        const Real2 *pos = static_cast<const Real2 *>(c->pos);
+        hipLaunchKernelGGL((nb_keys_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, n, c->nb_box, c->nb_keys[0]);
+        uint32_t *const slot[2] = {c->nb_slot, c->nb_slot};    // (packed: written by the last pass only)
+        enqueue_lsd_passes<kFieldSortItems>(st, c->nb_keys, slot, c->nb_radix, c->nb_rowsum, n, kFieldKeyBits, true);
+        hipLaunchKernelGGL((nb_gather_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, c->nb_slot, orig, n, c->nb_spos, c->nb_sidx);
+    });
+    int32_t off[kNbMaxLevels + 1];
+    *levels = nb_levels(n, off);
+    hipLaunchKernelGGL(nb_leaf_kernel, dim3(blocks_for(off[1], kBlock)), dim3(kBlock), 0, st, c->nb_spos, n, off[1], c->nb_boxes);
+    for (int l = 1; l < *levels; ++l) {
+        const int32_t count = off[l + 1] - off[l], below = off[l] - off[l - 1];
+        hipLaunchKernelGGL(nb_level_kernel, dim3(blocks_for(count, kBlock)), dim3(kBlock), 0, st, c->nb_boxes + off[l - 1], below,
+                           c->nb_boxes + off[l], count);
+    }
+    BH_HIP(c, hipGetLastError());
+    BH_HIP(c, hipEventRecord(c->nb_ev[1], st));
+    return BH_OK;
+}
+
+// Both queries.  k > 0: bh_neighbours; k == 0: bh_count_within at r2.  Rows come back in the launch's sorted order and are put
+// at their caller places here.
+static int nb_query(bh_ctx *c, const char *who, const double *points, int64_t n_points, int32_t k, double r2, int64_t *idx,
+                    double *d2, uint32_t *evals)
+{
+    const std::string w(who);
+    if (int rc = diag_check(c, who)) return rc;
+    if (!points && n_points != c->n) return fail(c, BH_ERR_ARG, w + ": without points, n_points must be the number of bodies");
+    for (int64_t i = 0; points && i < 2 * n_points; ++i)
+        if (!std::isfinite(points[i])) return fail(c, BH_ERR_ARG, w + ": point " + std::to_string(i / 2) + " has a non-finite coordinate");
+    if (n_points == 0) return BH_OK;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, w + ": more than 2^24 bodies (their indices share a key word)");
+    const int64_t kk = std::max<int32_t>(k, 1);               // entries per row on the host side (counts: one)
+    if (n == 0) {                                              // no bodies: nobody is near
+        if (idx) std::fill(idx, idx + n_points * kk, (int64_t)-1);
+        if (d2) std::fill(d2, d2 + n_points * kk, (double)INFINITY);
+        if (evals) std::fill(evals, evals + n_points, 0u);
+        return BH_OK;
+    }
+    BH_HIP(c, hipSetDevice(c->device));
+    const int64_t rows_max = std::min(n_points, kNbChunk);
+    if (int rc = nb_alloc(c, n, rows_max, rows_max * k)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, who, &levels)) return rc;
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> dest((size_t)rows_max), hev((size_t)rows_max);
+    std::vector<int64_t> hidx(idx ? (size_t)(rows_max * k) : 0);
+    std::vector<double> hd2(d2 ? (size_t)(rows_max * k) : 0);
+    std::vector<uint32_t> sidx;
+    if (!points) {
+        sidx.resize((size_t)n);
+        BH_HIP(c, hipMemcpyAsync(sidx.data(), c->nb_sidx, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    c->nb_query_ms = 0.0;
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        BH_HIP(c, hipEventRecord(c->nb_ev[2], st));
+        if (points) {
+            BH_HIP(c, hipMemcpyAsync(c->nb_points, points + 2 * t0, (size_t)rows * sizeof(double2), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(field_keys_kernel, dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_points, rows, c->nb_box,
+                               c->nb_pkeys[0]);
+            uint32_t *const order[2] = {c->nb_order, c->nb_order};
+            enqueue_lsd_passes<kFieldSortItems>(st, c->nb_pkeys, order, c->nb_radix, c->nb_rowsum, rows, kFieldKeyBits, true);
+        }
+        auto launch = [&](auto pts) {
+            constexpr bool PTS = decltype(pts)::value;
+            if (k > 0)
+                hipLaunchKernelGGL((nb_knn_kernel<PTS>), dim3(blocks_for(rows, kWave)), dim3(kWave), (size_t)k * kWave * 12, st, c->nb_spos,
+                                   c->nb_sidx, c->nb_keys[0], c->nb_boxes, c->nb_off, levels, (int32_t)n, k, c->nb_points, c->nb_order,
+                                   c->nb_pkeys[0], t0, rows, c->nb_idx, c->nb_d2, c->nb_evals);
+            else
+                hipLaunchKernelGGL((nb_count_kernel<PTS>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_spos, c->nb_boxes,
+                                   c->nb_off, levels, (int32_t)n, c->nb_points, c->nb_order, t0, rows, r2, c->nb_evals);
+        };
+        dispatch(launch, points != nullptr);
+        BH_HIP(c, hipGetLastError());
+        BH_HIP(c, hipEventRecord(c->nb_ev[3], st));
+        if (points) BH_HIP(c, hipMemcpyAsync(dest.data(), c->nb_order, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (idx) BH_HIP(c, hipMemcpyAsync(hidx.data(), c->nb_idx, (size_t)(rows * k) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (d2) BH_HIP(c, hipMemcpyAsync(hd2.data(), c->nb_d2, (size_t)(rows * k) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (evals) BH_HIP(c, hipMemcpyAsync(hev.data(), c->nb_evals, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+        float ms = 0.f;
+        BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[2], c->nb_ev[3]));
+        c->nb_query_ms += (double)ms;
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t at = points ? t0 + (int64_t)dest[(size_t)r] : (int64_t)sidx[(size_t)(t0 + r)];
+            if (idx) std::copy(hidx.begin() + r * k, hidx.begin() + (r + 1) * k, idx + at * k);
+            if (d2) std::copy(hd2.begin() + r * k, hd2.begin() + (r + 1) * k, d2 + at * k);
+            if (evals) evals[at] = hev[(size_t)r];
+        }
+    }
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
+    c->nb_build_ms = (double)ms;
+    return BH_OK;
+}
+
+int bh_neighbours(bh_ctx *c, const double *points, int64_t n_points, int32_t k, int64_t *idx, double *d2, uint32_t *evals)
+{
+    if (!c) return BH_ERR_ARG;
+    if (k < 1 || k > kNbMaxK) return fail(c, BH_ERR_ARG, "bh_neighbours: k must be 1 .. BH_NEIGHBOURS_MAX_K = 32");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_neighbours: n_points < 0");
+    if (!idx && !d2) return fail(c, BH_ERR_ARG, "bh_neighbours: no output array (idx and d2 are both null)");
+    return nb_query(c, "bh_neighbours", points, n_points, k, 0.0, idx, d2, evals);
+}
+
+int bh_count_within(bh_ctx *c, const double *points, int64_t n_points, double radius, uint32_t *counts)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(c, BH_ERR_ARG, "bh_count_within: the radius must be finite and >= 0");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_count_within: n_points < 0");
+    if (!counts) return fail(c, BH_ERR_ARG, "bh_count_within: null counts");
+    return nb_query(c, "bh_count_within", points, n_points, 0, radius * radius, nullptr, nullptr, counts);
+}
+
+int bh_neighbours_times(bh_ctx *c, double *build_ms, double *query_ms)
+{
+    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_neighbours_times: null argument");
+    *build_ms = c->nb_build_ms;
+    *query_ms = c->nb_query_ms;
     return BH_OK;
 }
 

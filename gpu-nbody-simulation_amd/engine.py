@@ -170,6 +170,48 @@ def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int
                        planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
 
 
+NEIGHBOURS_MAX_K = 32                   # BH_NEIGHBOURS_MAX_K
+
+
+def _density_k(k) -> int:
+    k = int(k)
+    if not 2 <= k <= NEIGHBOURS_MAX_K:
+        raise ValueError(f"local density needs 2 <= k <= {NEIGHBOURS_MAX_K}")
+    return k
+
+
+def local_density_from(idx, d2, masses):
+    """(sigma, r_k) from the k nearest neighbours idx, d2 (n, k) of every body and the masses: Casertano and Hut's estimator
+    in two dimensions, sigma_i = (m of the 1st + ... + m of the (k-1)-th neighbour, added in that order) / (pi * d2 of the
+    k-th), r_k = sqrt(d2 of the k-th).  sigma is NaN (and r_k inf) where a body has fewer than k neighbours, inf where
+    d2 of the k-th is 0."""
+    idx = np.asarray(idx, dtype=np.int64)
+    d2 = np.asarray(d2, dtype=np.float64)
+    m = np.asarray(masses, dtype=np.float64).reshape(-1)
+    k = _density_k(idx.shape[1])
+    msum = np.zeros(len(idx))
+    for j in range(k - 1):
+        msum = msum + m[np.maximum(idx[:, j], 0)]
+    d2k = d2[:, k - 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sigma = msum / (np.pi * d2k)
+    sigma[d2k == 0.0] = np.inf
+    sigma[idx[:, k - 1] < 0] = np.nan
+    return sigma, np.sqrt(d2k)
+
+
+def density_centre_from(sigma, positions) -> np.ndarray:
+    """sum sigma_i x_i / sum sigma_i over the bodies with finite sigma, each sum with math.fsum (NaN without such a body)."""
+    import math
+    sigma = np.asarray(sigma, dtype=np.float64)
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+    ok = np.isfinite(sigma)
+    w = math.fsum(sigma[ok].tolist())
+    if w == 0.0:
+        return np.array([np.nan, np.nan])
+    return np.array([math.fsum((sigma[ok] * pos[ok, 0]).tolist()) / w, math.fsum((sigma[ok] * pos[ok, 1]).tolist()) / w])
+
+
 # (q as exact fractions: ceil(q n) in integers, so that no rounding of q * n moves an index)
 _QUANTILES = {"median": (1, 2), "p90": (9, 10), "p99": (99, 100), "p999": (999, 1000)}
 
@@ -490,6 +532,54 @@ class BarnesHutEngine:
         self._check(self._lib.bh_moment_map_deposit(self._h, _dptr(b), int(nx), int(ny), sch,
                                                     e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p), C.byref(nd)))
         return p.value, nd.value
+
+    # -- neighbours -----------------------------------------------------------------------------
+    def _query_points(self, points):
+        """(array or None, number of queries, pointer for the C-ABI) of a query list (None: every body)."""
+        if points is None:
+            return None, self.n, None
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        return p, len(p), _dptr(p) if len(p) else (C.c_double * 2)()
+
+    def neighbours(self, k: int, points=None, with_evals: bool = False):
+        """(idx (q, k) int64, d2 (q, k) float64[, evals (q,) uint32]): the k nearest bodies of every body (points None; the
+        body itself left out by index) or of the coordinates `points` (q, 2) (nobody left out), in the order (d2, caller
+        index) with d2 = dx * dx + dy * dy in fp64; idx = -1 and d2 = inf where there are fewer than k.  evals: the distances
+        the search computed per query.  Reads the state only; the run is not perturbed."""
+        p, q, pp = self._query_points(points)
+        k = int(k)
+        kk = k if 1 <= k <= NEIGHBOURS_MAX_K else 1             # (else the call refuses before it writes)
+        idx = np.full((max(q, 1), kk), -1, dtype=np.int64)
+        d2 = np.full((max(q, 1), kk), np.inf)
+        ev = np.zeros(max(q, 1), dtype=np.uint32) if with_evals else None
+        self._check(self._lib.bh_neighbours(self._h, pp, q, k, idx.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(d2),
+                                            ev.ctypes.data_as(C.POINTER(C.c_uint32)) if with_evals else None))
+        return (idx[:q], d2[:q], ev[:q]) if with_evals else (idx[:q], d2[:q])
+
+    def count_within(self, radius: float, points=None) -> np.ndarray:
+        """uint32 (q,): the bodies with d2 <= radius * radius of every body (points None; itself left out) or of `points`."""
+        p, q, pp = self._query_points(points)
+        cnt = np.zeros(max(q, 1), dtype=np.uint32)
+        self._check(self._lib.bh_count_within(self._h, pp, q, float(radius), cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return cnt[:q]
+
+    def neighbours_times(self):
+        """(build_ms, query_ms) of the last neighbours() / count_within(): HIP events around the structure's build and the
+        searches."""
+        b, q = C.c_double(), C.c_double()
+        self._check(self._lib.bh_neighbours_times(self._h, C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    def local_density(self, k: int = 6):
+        """(sigma (n,), r_k (n,)): Casertano and Hut's k-th-neighbour density estimate in two dimensions from one
+        neighbours(k) call and the masses -- see local_density_from."""
+        idx, d2 = self.neighbours(_density_k(k))
+        return local_density_from(idx, d2, self.masses())
+
+    def density_centre(self, k: int = 6) -> np.ndarray:
+        """(x, y): the density-weighted centre sum sigma_i x_i / sum sigma_i over the bodies with finite sigma (math.fsum)."""
+        sigma, _ = self.local_density(k)
+        return density_centre_from(sigma, self.download()[0])
 
     # -- tree output ------------------------------------------------------------------------
     def export_tree(self):

@@ -76,7 +76,7 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
                      field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0,
                      integrator: str = "euler", density_file: str | None = None, density_grid=None, density_box=None,
-                     density_scheme: str = "cic"):
+                     density_scheme: str = "cic", neighbours_file: str | None = None, neighbours_k: int = 6):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -98,6 +98,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     density_scheme) on the density_grid = (NX, NY) cells over density_box (None: the bounding box of the final positions):
     the line `# x,y,sigma,vx,vy,dispersion`, then one row per cell centre (%.17g; nan in a cell without mass), y the outer
     axis -- the points of field_file for the same grid and box.  Not part of gpu_parallel_duration_us.
+    neighbours_file: after the last step, also write the k-th-neighbour density of the final state
+    (BarnesHutEngine.local_density(neighbours_k)): the line `# i,x,y,r_k,sigma`, then one row per body in caller order (%.17g):
+    its index, its position, the distance of its k-th neighbour and Casertano and Hut's surface density.  Not part of
+    gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -213,6 +217,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, density_file) if not os.path.isabs(density_file) else density_file, "w") as f:
                 f.write("# x,y,sigma,vx,vy,dispersion\n")
                 f.write("".join("%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n" % (x, y, *r) for (x, y), r in zip(pts, zip(*cols))))
+        if neighbours_file is not None:
+            sigma, r_k = eng.local_density(neighbours_k)
+            with open(os.path.join(out_dir, neighbours_file) if not os.path.isabs(neighbours_file) else neighbours_file, "w") as f:
+                f.write("# i,x,y,r_k,sigma\n")
+                f.write("".join("%d,%.17g,%.17g,%.17g,%.17g\n" % (i, x, y, r, sg) for i, ((x, y), r, sg) in enumerate(zip(pos, r_k, sigma))))
         if traj is not None:
             traj.close()
         for f in (energy, ferr):
@@ -283,6 +292,10 @@ def _parse(argv):
                     help="what the cells cover (default: the bounding box of the final positions, as --field-box)")
     ap.add_argument("--density-scheme", choices=["ngp", "cic"], default="cic",
                     help="ngp: a body goes to the cell it is in; cic: to the four nearest cell centres, bilinearly")
+    ap.add_argument("--neighbours-file", default=None, metavar="PATH",
+                    help="after the last step, also write i,x,y,r_k,sigma of every body: the distance of its k-th neighbour and "
+                         "the k-th-neighbour surface density (Casertano and Hut)")
+    ap.add_argument("--neighbours-k", type=int, default=None, metavar="K", help="the k of --neighbours-file (default 6; 2 .. 32)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -306,6 +319,10 @@ def _parse(argv):
         ap.error("--density-file and --density-grid go together")
     if a.density_box is not None and a.density_file is None:
         ap.error("--density-box needs --density-file")
+    if a.neighbours_k is not None and a.neighbours_file is None:
+        ap.error("--neighbours-k needs --neighbours-file")
+    if a.neighbours_k is not None and not 2 <= a.neighbours_k <= 32:
+        ap.error("--neighbours-k: 2 .. 32")
     if a.softening is not None:
         if not (a.softening >= 0.0 and a.softening < float("inf")):
             ap.error("--softening: the length must be finite and >= 0")
@@ -368,7 +385,8 @@ def main(argv=None) -> int:
         energy_every=a.energy_every, force_error_file=a.force_error_file, force_error_every=a.force_error_every,
         force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box,
         softening=a.softening or 0.0, integrator=a.integrator, density_file=a.density_file, density_grid=a.density_grid,
-        density_box=a.density_box, density_scheme=a.density_scheme)
+        density_box=a.density_box, density_scheme=a.density_scheme, neighbours_file=a.neighbours_file,
+        neighbours_k=6 if a.neighbours_k is None else a.neighbours_k)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -439,6 +439,35 @@ int bh_moment_map_max(bh_ctx *ctx, double maxabs[4]);
 int bh_moment_map_deposit(bh_ctx *ctx, const double box[4], int32_t nx, int32_t ny, int32_t scheme,
                           const int32_t exponents[4], void **planes_dev, int64_t *n_deposited);
 
+/* --- neighbours: which bodies are next to a body or a point, and how far away ------------------------------------------
+ * Queries.  points == NULL: the queries are the n bodies in caller order and n_points must be n; body i is left out of its
+ *   own answer by index -- another body at the same place is not: it is a neighbour at d2 = 0.  Otherwise points[n_points][2]
+ *   are coordinates that are nobody's: a point exactly on a body has that body as a neighbour at d2 = 0.
+ * Distance.  For query q and body j of the CURRENT state: dx = x_j - q.x; dy = y_j - q.y; d2 = dx * dx + dy * dy, in fp64 with
+ *   nothing fused, in every precision (an fp32 state is widened first, exactly).
+ * bh_neighbours: the first k bodies in the total order (d2, caller index j), ascending: idx[n_points][k] their caller indices,
+ *   d2[n_points][k] the distances; with fewer than k candidates the remaining slots are idx = -1, d2 = +inf.  Either output
+ *   may be NULL, not both.  evals (may be NULL): the number of bodies whose d2 the search computed for the query, seeds
+ *   included -- deterministic for a given state and call, a measure of the work and no part of the answer.
+ * bh_count_within: counts[n_points] = the bodies with d2 <= radius * radius (the product formed once in fp64 on the host),
+ *   the same self-exclusion.
+ * A query's result does not depend on the other queries of the call, their order or their number.  The search (a bounding-box
+ * hierarchy over the Morton-sorted bodies, rebuilt on every call) prunes with bounds that rounding cannot invert, so the
+ * results are those of the brute-force definition above, bit for bit.
+ * bh_neighbours_times: HIP-event times of the last of these calls: the structure's build (bounds, sort, boxes) and the
+ *   queries (a point launch's own sort included), downloads excluded.
+ * They read the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.  They wait for the stream.
+ * Errors: BH_ERR_ARG for k < 1 or k > BH_NEIGHBOURS_MAX_K, n_points < 0, a null output, points == NULL with n_points != n, a
+ *   non-finite query coordinate (checked before anything is enqueued), a negative or non-finite radius, and -- found by the
+ *   bounds pass, with a message that says so -- a non-finite body position in the state.  BH_ERR_CAPACITY for more than 2^24
+ *   bodies (their indices share a key word).  BH_ERR_STATE before any upload, in LET mode and with world > 1 (a neighbour can
+ *   live on another rank).  n_points = 0 returns at once; without bodies every idx is -1, every d2 +inf, every count 0. */
+#define BH_NEIGHBOURS_MAX_K 32
+int bh_neighbours(bh_ctx *ctx, const double *points, int64_t n_points, int32_t k, int64_t *idx, double *d2, uint32_t *evals);
+int bh_count_within(bh_ctx *ctx, const double *points, int64_t n_points, double radius, uint32_t *counts);
+int bh_neighbours_times(bh_ctx *ctx, double *build_ms, double *query_ms);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
