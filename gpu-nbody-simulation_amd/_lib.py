@@ -126,6 +126,11 @@ SIGNATURES = {
     "bh_neighbours": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
     "bh_count_within": (C.c_int, [_ctx, _dp, C.c_int64, C.c_double, C.POINTER(C.c_uint32)]),
     "bh_neighbours_times": (C.c_int, [_ctx, _dp, _dp]),
+    "bh_groups": (C.c_int, [_ctx, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                            C.POINTER(C.c_uint64)]),
+    "bh_groups_catalogue": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "bh_groups_times": (C.c_int, [_ctx, _dp, _dp, _dp]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

@@ -26,6 +26,7 @@
 #include "bh_split.hpp"
 #include "bh_moments.hpp"
 #include "bh_neighbours.hpp"
+#include "bh_groups.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
 
@@ -175,6 +176,22 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     int64_t *nb_idx = nullptr;
     hipEvent_t nb_ev[4] = {nullptr, nullptr, nullptr, nullptr};    // around the build and around a launch's sort and search
     double nb_build_ms = 0.0, nb_query_ms = 0.0;                    // of the last call (bh_neighbours_times)
+    // friends-of-friends groups (bh_groups.hpp), allocated on first use: one block for up to fof_cap bodies beside the
+    // neighbour structure's, and the catalogue of the last bh_groups call on the host (no record of bh_run_state.hpp: it is
+    // that call's result, whatever the run does afterwards)
+    char *fof_block = nullptr;
+    int64_t fof_cap = 0;
+    uint64_t fof_bytes = 0;
+    uint32_t *fof_parent = nullptr, *fof_root = nullptr, *fof_minidx = nullptr, *fof_count = nullptr, *fof_rec_label = nullptr,
+             *fof_rec_count = nullptr;
+    long long *fof_label = nullptr;
+    unsigned long long *fof_sums = nullptr;
+    GrpCounters *fof_ctr = nullptr;
+    GrpMax *fof_max = nullptr;
+    hipEvent_t fof_ev[2] = {nullptr, nullptr};                      // after the labels, after the catalogue
+    double fof_build_ms = 0.0, fof_link_ms = 0.0, fof_cat_ms = 0.0; // of the last call (bh_groups_times)
+    std::vector<int64_t> fof_cat_labels, fof_cat_counts, fof_cat_sums;
+    int32_t fof_cat_exp[kGrpPlanes] = {0, 0, 0, 0, 0};
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -1027,6 +1044,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb_ev);
+    destroy(c->fof_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2114,6 +2132,182 @@ int bh_neighbours_times(bh_ctx *c, double *build_ms, double *query_ms)
     if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_neighbours_times: null argument");
     *build_ms = c->nb_build_ms;
     *query_ms = c->nb_query_ms;
+    return BH_OK;
+}
+
+// ---- friends-of-friends groups (bh_groups.hpp) on the structure of the neighbour queries.  They read pos, vel, mass and orig as
+// they lie in memory and write buffers of their own: a step before and after runs bit for bit as it would have.
+static int fof_alloc(bh_ctx *c, int64_t n)
+{
+    auto carve = [](char *&b, auto **out, size_t count) {
+        using T = typename std::remove_reference<decltype(**out)>::type;
+        *out = reinterpret_cast<T *>(b);
+        b += (count * sizeof(T) + 15) / 16 * 16;
+    };
+    for (auto &e : c->fof_ev)
+        if (!e) BH_HIP(c, hipEventCreate(&e));
+    if (n <= c->fof_cap) return BH_OK;
+    int64_t cap = 1024;
+    while (cap < n) cap <<= 1;
+    if (c->fof_block) {                                            // (the previous call has waited for its stream)
+        dev_free(c, c->fof_block);
+        c->device_bytes -= c->fof_bytes;
+        c->fof_block = nullptr; c->fof_cap = 0; c->fof_bytes = 0;
+    }
+    const size_t bytes = (size_t)cap * (6 * sizeof(uint32_t) + sizeof(long long) + kGrpPlanes * sizeof(unsigned long long)) +
+                         sizeof(GrpCounters) + sizeof(GrpMax) + 16 * 10;
+    char *b = nullptr;
+    if (int rc = dev_alloc(c, &b, bytes)) return rc;
+    c->fof_block = b; c->fof_cap = cap; c->fof_bytes = bytes;
+    carve(b, &c->fof_sums, (size_t)cap * kGrpPlanes); carve(b, &c->fof_label, (size_t)cap);
+    carve(b, &c->fof_ctr, 1); carve(b, &c->fof_max, 1);
+    carve(b, &c->fof_parent, (size_t)cap); carve(b, &c->fof_root, (size_t)cap); carve(b, &c->fof_minidx, (size_t)cap);
+    carve(b, &c->fof_count, (size_t)cap); carve(b, &c->fof_rec_label, (size_t)cap); carve(b, &c->fof_rec_count, (size_t)cap);
+    return BH_OK;
+}
+
+int bh_groups(bh_ctx *c, double linking_length, int64_t min_members, int64_t *label, int64_t *n_groups, int64_t *n_catalogue,
+              uint64_t *stats)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(linking_length >= 0.0) || !std::isfinite(linking_length))
+        return fail(c, BH_ERR_ARG, "bh_groups: the linking length must be finite and >= 0");
+    if (min_members < 1) return fail(c, BH_ERR_ARG, "bh_groups: min_members must be at least 1");
+    if (!n_groups) return fail(c, BH_ERR_ARG, "bh_groups: null n_groups");
+    if (int rc = diag_check(c, "bh_groups")) return rc;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_groups: more than 2^24 bodies (their indices share a key word)");
+    c->fof_cat_labels.clear(); c->fof_cat_counts.clear(); c->fof_cat_sums.clear();
+    std::fill(c->fof_cat_exp, c->fof_cat_exp + kGrpPlanes, 0);
+    c->fof_build_ms = c->fof_link_ms = c->fof_cat_ms = 0.0;
+    *n_groups = 0;
+    if (n_catalogue) *n_catalogue = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (n == 0) return BH_OK;
+    const double b2 = linking_length * linking_length;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, 0, 0)) return rc;
+    if (int rc = fof_alloc(c, n)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_groups", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(n, kBlock);
+    const int32_t n32 = (int32_t)n;
+    BH_HIP(c, hipMemsetAsync(c->fof_ctr, 0, sizeof(GrpCounters), st));
+    BH_HIP(c, hipMemsetAsync(c->fof_minidx, 0xff, (size_t)n * sizeof(uint32_t), st));
+    BH_HIP(c, hipMemsetAsync(c->fof_count, 0, (size_t)n * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(grp_init_kernel, dim3(grid), dim3(kBlock), 0, st, c->nb_boxes, c->nb_off, levels, n32, b2, c->fof_parent, c->fof_ctr);
+    hipLaunchKernelGGL(grp_link_kernel, dim3(grid), dim3(kBlock), 0, st, c->nb_spos, c->nb_boxes, c->nb_off, levels, n32, b2,
+                       c->fof_parent, c->fof_ctr);
+    hipLaunchKernelGGL(grp_flatten_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_parent, c->nb_sidx, n32, c->fof_root, c->fof_minidx,
+                       c->fof_count, c->fof_ctr);
+    hipLaunchKernelGGL(grp_label_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_root, c->fof_minidx, c->nb_sidx, n32, c->fof_label);
+    BH_HIP(c, hipGetLastError());
+    BH_HIP(c, hipEventRecord(c->fof_ev[0], st));
+    GrpExp ex{};
+    GrpCounters ctr{};
+    if (n_catalogue) {
+        BH_HIP(c, hipMemsetAsync(c->fof_max, 0, sizeof(GrpMax), st));
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((grp_max_kernel<Real2, Real>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos),
+                               static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass), n, c->fof_max);
+        });
+        // (gid: the parents are not read any more)
+        hipLaunchKernelGGL(grp_compact_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_root, c->fof_minidx, c->fof_count, n32,
+                           (uint32_t)std::min<int64_t>(min_members, (int64_t)UINT32_MAX), c->fof_parent, c->fof_rec_label,
+                           c->fof_rec_count, c->fof_ctr);
+        BH_HIP(c, hipGetLastError());
+        GrpMax mx{};
+        BH_HIP(c, hipMemcpyAsync(&mx, c->fof_max, sizeof(mx), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(&ctr, c->fof_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+        if (mx.bad)
+            return fail(c, BH_ERR_ARG, "bh_groups: a body has a non-finite velocity or mass (or a moment m x, m v that overflows fp64)");
+        const int L = map_log2_ceil(n);
+        for (int p = 0; p < kGrpPlanes; ++p) {
+            double m = 0.0;
+            std::memcpy(&m, &mx.bits[p], sizeof(double));
+            int E = 0;
+            if (m != 0.0) { (void)std::frexp(m, &E); ex.e[p] = 62 - E - L; }
+        }
+    }
+    if (!n_catalogue) {
+        BH_HIP(c, hipMemcpyAsync(&ctr, c->fof_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+    }
+    const int64_t kept = (int64_t)ctr.kept;
+    if (n_catalogue && kept > 0) {
+        BH_HIP(c, hipMemsetAsync(c->fof_sums, 0, (size_t)kept * kGrpPlanes * sizeof(unsigned long long), st));
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((grp_sum_kernel<Real2, Real>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos),
+                               static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass), c->nb_slot, c->fof_root,
+                               c->fof_count, c->fof_parent, n32, (uint32_t)std::min<int64_t>(min_members, (int64_t)UINT32_MAX), ex,
+                               c->fof_sums);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    BH_HIP(c, hipEventRecord(c->fof_ev[1], st));
+    std::vector<uint32_t> rl((size_t)kept), rc_((size_t)kept);
+    std::vector<int64_t> sums((size_t)kept * kGrpPlanes);
+    if (kept > 0) {
+        BH_HIP(c, hipMemcpyAsync(rl.data(), c->fof_rec_label, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(rc_.data(), c->fof_rec_count, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(sums.data(), c->fof_sums, sums.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (label) BH_HIP(c, hipMemcpyAsync(label, c->fof_label, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
+    c->fof_build_ms = (double)ms;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[1], c->fof_ev[0]));
+    c->fof_link_ms = (double)ms;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->fof_ev[0], c->fof_ev[1]));
+    c->fof_cat_ms = (double)ms;
+    // the records in the order (count descending, label ascending): the device numbered them as its atomics fell
+    std::vector<int64_t> order((size_t)kept);
+    for (int64_t g = 0; g < kept; ++g) order[(size_t)g] = g;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        return rc_[(size_t)a] != rc_[(size_t)b] ? rc_[(size_t)a] > rc_[(size_t)b] : rl[(size_t)a] < rl[(size_t)b];
+    });
+    c->fof_cat_labels.resize((size_t)kept); c->fof_cat_counts.resize((size_t)kept); c->fof_cat_sums.resize((size_t)kept * kGrpPlanes);
+    for (int64_t k = 0; k < kept; ++k) {
+        const size_t g = (size_t)order[(size_t)k];
+        c->fof_cat_labels[(size_t)k] = (int64_t)rl[g];
+        c->fof_cat_counts[(size_t)k] = (int64_t)rc_[g];
+        std::copy(sums.begin() + g * kGrpPlanes, sums.begin() + (g + 1) * kGrpPlanes, c->fof_cat_sums.begin() + (size_t)k * kGrpPlanes);
+    }
+    std::copy(ex.e, ex.e + kGrpPlanes, c->fof_cat_exp);
+    *n_groups = (int64_t)ctr.roots;
+    if (n_catalogue) *n_catalogue = kept;
+    if (stats) { stats[0] = ctr.evals; stats[1] = ctr.pairs; stats[2] = ctr.hooks; }
+    return BH_OK;
+}
+
+int bh_groups_catalogue(bh_ctx *c, int64_t max_records, int64_t *labels, int64_t *counts, int64_t *sums, int32_t *exponents,
+                        int64_t *n_out)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!n_out || max_records < 0) return fail(c, BH_ERR_ARG, "bh_groups_catalogue: null n_out or max_records < 0");
+    const int64_t g = (int64_t)c->fof_cat_labels.size();
+    *n_out = g;
+    if (exponents) std::copy(c->fof_cat_exp, c->fof_cat_exp + kGrpPlanes, exponents);
+    if (g > max_records) return fail(c, BH_ERR_CAPACITY, "bh_groups_catalogue: the catalogue has " + std::to_string(g) + " records");
+    if (labels) std::copy(c->fof_cat_labels.begin(), c->fof_cat_labels.end(), labels);
+    if (counts) std::copy(c->fof_cat_counts.begin(), c->fof_cat_counts.end(), counts);
+    if (sums) std::copy(c->fof_cat_sums.begin(), c->fof_cat_sums.end(), sums);
+    return BH_OK;
+}
+
+int bh_groups_times(bh_ctx *c, double *build_ms, double *link_ms, double *catalogue_ms)
+{
+    if (!c || !build_ms || !link_ms || !catalogue_ms) return fail(c, BH_ERR_ARG, "bh_groups_times: null argument");
+    *build_ms = c->fof_build_ms;
+    *link_ms = c->fof_link_ms;
+    *catalogue_ms = c->fof_cat_ms;
     return BH_OK;
 }
 

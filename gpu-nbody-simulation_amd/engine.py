@@ -170,6 +170,45 @@ def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int
                        planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
 
 
+@dataclass
+class BhGroups:
+    """Friends-of-friends groups of the current state (groups): the label of every body, and a catalogue of the groups with at
+    least min_members bodies in the order (count descending, id ascending).  mass, com and velocity are the fixed-point sums
+    times 2^-exponent and their quotients (sums beyond 2^53 units round to fp64 there); NaN where a group has no mass."""
+    label: np.ndarray            # (n,) int64: the smallest caller index in the body's group
+    n_groups: int                # all components, whatever min_members
+    linking_length: float
+    min_members: int
+    id: np.ndarray               # (g,) int64: the label of the group
+    count: np.ndarray            # (g,) int64
+    mass: np.ndarray             # (g,): sum m
+    com: np.ndarray              # (g, 2): sum m x / sum m
+    velocity: np.ndarray         # (g, 2): sum m v / sum m
+    sums: np.ndarray | None = None        # raw=True: the int64 sums (g, 5) of m, m x, m y, m vx, m vy ...
+    exponents: np.ndarray | None = None   # ... and their exponents: value = sums * 2^-exponent
+    stats: tuple | None = None            # with_stats=True: (distances computed, friend pairs found, unions that joined)
+
+    def members(self, g: int) -> np.ndarray:
+        """the caller indices of the bodies of catalogue entry g, ascending"""
+        return np.nonzero(self.label == self.id[g])[0]
+
+
+def groups_from_sums(label, n_groups: int, linking_length: float, min_members: int, ids, counts, sums, exponents,
+                     raw: bool = False, stats=None) -> BhGroups:
+    """BhGroups of the labels and the catalogue's int64 sums (g, 5) and their exponents."""
+    sums = np.asarray(sums, dtype=np.int64).reshape(-1, 5)
+    exponents = np.asarray(exponents, dtype=np.int32).reshape(5)
+    val = [np.ldexp(sums[:, p].astype(np.float64), -int(exponents[p])) for p in range(5)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        com = np.stack([val[1] / val[0], val[2] / val[0]], axis=1)
+        vel = np.stack([val[3] / val[0], val[4] / val[0]], axis=1)
+    com[val[0] == 0.0] = np.nan
+    vel[val[0] == 0.0] = np.nan
+    return BhGroups(np.asarray(label, dtype=np.int64), int(n_groups), float(linking_length), int(min_members),
+                    np.asarray(ids, dtype=np.int64), np.asarray(counts, dtype=np.int64), val[0], com, vel,
+                    sums if raw else None, exponents.copy() if raw else None, stats)
+
+
 NEIGHBOURS_MAX_K = 32                   # BH_NEIGHBOURS_MAX_K
 
 
@@ -569,6 +608,35 @@ class BarnesHutEngine:
         b, q = C.c_double(), C.c_double()
         self._check(self._lib.bh_neighbours_times(self._h, C.byref(b), C.byref(q)))
         return b.value, q.value
+
+    # -- groups ---------------------------------------------------------------------------------
+    def groups(self, linking_length: float, min_members: int = 2, raw: bool = False, with_stats: bool = False) -> BhGroups:
+        """Friends-of-friends groups of the current state: bodies i, j are friends when d2 = dx * dx + dy * dy <= linking_length^2
+        (fp64, nothing fused), a group is a connected component, its label the smallest caller index in it -- the brute-force
+        definition bit for bit.  The catalogue holds the groups with at least min_members bodies.  raw: also the int64 sums and
+        their exponents; with_stats: the work counters.  Reads the state only; the run is not perturbed."""
+        n = self.n
+        label = np.zeros(max(n, 1), dtype=np.int64)
+        ng, nc = C.c_int64(), C.c_int64()
+        st = (C.c_uint64 * 3)()
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.bh_groups(self._h, float(linking_length), int(min_members), label.ctypes.data_as(i64), C.byref(ng),
+                                        C.byref(nc), st))
+        g = nc.value
+        ids, counts = np.zeros(max(g, 1), dtype=np.int64), np.zeros(max(g, 1), dtype=np.int64)
+        sums, e = np.zeros((max(g, 1), 5), dtype=np.int64), np.zeros(5, dtype=np.int32)
+        got = C.c_int64()
+        self._check(self._lib.bh_groups_catalogue(self._h, g, ids.ctypes.data_as(i64), counts.ctypes.data_as(i64),
+                                                  sums.ctypes.data_as(i64), e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got)))
+        return groups_from_sums(label[:n], ng.value, linking_length, min_members, ids[:g], counts[:g], sums[:g], e, raw,
+                                tuple(int(v) for v in st) if with_stats else None)
+
+    def groups_times(self):
+        """(build_ms, link_ms, catalogue_ms) of the last groups(): HIP events around the index's build, the linking and
+        labelling, and the catalogue."""
+        b, l, k = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.bh_groups_times(self._h, C.byref(b), C.byref(l), C.byref(k)))
+        return b.value, l.value, k.value
 
     def local_density(self, k: int = 6):
         """(sigma (n,), r_k (n,)): Casertano and Hut's k-th-neighbour density estimate in two dimensions from one

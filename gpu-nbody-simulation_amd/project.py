@@ -76,7 +76,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      force_error_file: str | None = None, force_error_every: int = 0, force_error_sample: int = 65536,
                      field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0,
                      integrator: str = "euler", density_file: str | None = None, density_grid=None, density_box=None,
-                     density_scheme: str = "cic", neighbours_file: str | None = None, neighbours_k: int = 6):
+                     density_scheme: str = "cic", neighbours_file: str | None = None, neighbours_k: int = 6,
+                     groups_file: str | None = None, linking_length: float | None = None, groups_min: int = 2):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -102,11 +103,17 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     (BarnesHutEngine.local_density(neighbours_k)): the line `# i,x,y,r_k,sigma`, then one row per body in caller order (%.17g):
     its index, its position, the distance of its k-th neighbour and Casertano and Hut's surface density.  Not part of
     gpu_parallel_duration_us.
+    groups_file: after the last step, also write the friends-of-friends catalogue of the final state
+    (BarnesHutEngine.groups(linking_length, groups_min)): the line `# id,count,mass,x,y,vx,vy`, then one row per group with at
+    least groups_min bodies (%.17g), the largest first: its label (the smallest body index in it), its member count, its mass,
+    its centre of mass and its bulk velocity.  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
     outputs as one BarnesHutEngine.step_kdk, so every line of the energy, force-error and positions files, and the state
     returned, has velocities and positions at the same time."""
+    if groups_file is not None and linking_length is None:
+        raise ValueError("groups_file needs a linking_length")
     if integrator not in ("euler", "kdk"):
         raise ValueError("integrator must be 'euler' or 'kdk'")
     n = len(masses)
@@ -222,6 +229,12 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, neighbours_file) if not os.path.isabs(neighbours_file) else neighbours_file, "w") as f:
                 f.write("# i,x,y,r_k,sigma\n")
                 f.write("".join("%d,%.17g,%.17g,%.17g,%.17g\n" % (i, x, y, r, sg) for i, ((x, y), r, sg) in enumerate(zip(pos, r_k, sigma))))
+        if groups_file is not None:
+            g = eng.groups(linking_length, groups_min)
+            with open(os.path.join(out_dir, groups_file) if not os.path.isabs(groups_file) else groups_file, "w") as f:
+                f.write("# id,count,mass,x,y,vx,vy\n")
+                f.write("".join("%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % (i, k, m, x, y, vx, vy)
+                                for i, k, m, (x, y), (vx, vy) in zip(g.id, g.count, g.mass, g.com, g.velocity)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr):
@@ -296,6 +309,12 @@ def _parse(argv):
                     help="after the last step, also write i,x,y,r_k,sigma of every body: the distance of its k-th neighbour and "
                          "the k-th-neighbour surface density (Casertano and Hut)")
     ap.add_argument("--neighbours-k", type=int, default=None, metavar="K", help="the k of --neighbours-file (default 6; 2 .. 32)")
+    ap.add_argument("--groups-file", default=None, metavar="PATH",
+                    help="after the last step, also write id,count,mass,x,y,vx,vy of every friends-of-friends group of the final "
+                         "state (needs --linking-length)")
+    ap.add_argument("--linking-length", type=float, default=None, metavar="B",
+                    help="bodies at most B apart are friends; a group is a connected component of that relation")
+    ap.add_argument("--groups-min", type=int, default=None, metavar="M", help="smallest group of --groups-file (default 2)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -323,6 +342,14 @@ def _parse(argv):
         ap.error("--neighbours-k needs --neighbours-file")
     if a.neighbours_k is not None and not 2 <= a.neighbours_k <= 32:
         ap.error("--neighbours-k: 2 .. 32")
+    if (a.groups_file is None) != (a.linking_length is None):
+        ap.error("--groups-file and --linking-length go together")
+    if a.groups_min is not None and a.groups_file is None:
+        ap.error("--groups-min needs --groups-file")
+    if a.groups_min is not None and a.groups_min < 1:
+        ap.error("--groups-min: at least 1")
+    if a.linking_length is not None and not (a.linking_length >= 0.0 and a.linking_length < float("inf")):
+        ap.error("--linking-length: the length must be finite and >= 0")
     if a.softening is not None:
         if not (a.softening >= 0.0 and a.softening < float("inf")):
             ap.error("--softening: the length must be finite and >= 0")
@@ -386,7 +413,8 @@ def main(argv=None) -> int:
         force_error_sample=a.force_error_sample, field_file=a.field_file, field_grid=a.field_grid, field_box=a.field_box,
         softening=a.softening or 0.0, integrator=a.integrator, density_file=a.density_file, density_grid=a.density_grid,
         density_box=a.density_box, density_scheme=a.density_scheme, neighbours_file=a.neighbours_file,
-        neighbours_k=6 if a.neighbours_k is None else a.neighbours_k)
+        neighbours_k=6 if a.neighbours_k is None else a.neighbours_k, groups_file=a.groups_file,
+        linking_length=a.linking_length, groups_min=2 if a.groups_min is None else a.groups_min)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -468,6 +468,42 @@ int bh_neighbours(bh_ctx *ctx, const double *points, int64_t n_points, int32_t k
 int bh_count_within(bh_ctx *ctx, const double *points, int64_t n_points, double radius, uint32_t *counts);
 int bh_neighbours_times(bh_ctx *ctx, double *build_ms, double *query_ms);
 
+/* --- groups: which bodies belong together (friends of friends), and a catalogue of the groups ---------------------------------
+ * Distance.  For bodies i != j of the CURRENT state: dx = x_j - x_i; dy = y_j - y_i; d2 = dx * dx + dy * dy, in fp64 with nothing
+ *   fused, in every precision (an fp32 state is widened first, exactly): the d2 of bh_count_within.  It is symmetric in (i, j).
+ * Friends.  i and j are friends when d2 <= b2, b2 = linking_length * linking_length (the product formed once in fp64 on the host).
+ * Groups.  A group is a connected component of the friendship graph over all n bodies; a body without friends is a group of one.
+ * Label.  label[i] (n of them, caller order; may be NULL) is the smallest caller index in the group of body i.  The labels are a
+ *   pure function of the state and the linking length: no launch shape, traversal order or race decides any of them.
+ * Catalogue.  Every group with at least min_members (>= 1) bodies has a record: its label, its member count and the five sums
+ *     plane 0: m      plane 1: m * x      plane 2: m * y      plane 3: m * vx      plane 4: m * vy
+ *   over its members, each moment one fp64 product, summed in the fixed point of the moment maps: a first pass takes max |q_p|
+ *   of every plane over ALL bodies, E_p is its frexp exponent, L = ceil(log2(max(n, 1))), the plane's exponent is 62 - E_p - L
+ *   (0 when the maximum is 0), a contribution is (int64) rint(ldexp(q_p, exponent)), added with 64-bit integer atomics: no
+ *   overflow, the same bits in any order, every contribution rounded once by at most half a unit.  value = sum * 2^-exponent.
+ *   The records are ordered by (count descending, label ascending).
+ * bh_groups: builds the index of the neighbour queries, links, labels and reduces; waits for the stream.  *n_groups: all
+ *   components, whatever min_members.  n_catalogue may be NULL: then no catalogue is made (and masses and velocities are not
+ *   read); else *n_catalogue is the number of records.  stats (may be NULL) = {distances computed, friend pairs found, unions
+ *   that joined two trees}: deterministic for a given state and call; the third is n - *n_groups; a measure of the work and no
+ *   part of the answer.
+ * bh_groups_catalogue: copies out the catalogue of the last bh_groups call -- that call's result, valid until the next bh_groups
+ *   or bh_destroy whatever the run does in between.  labels[g], counts[g], sums[g][5], exponents[5]; any of them may be NULL.
+ *   *n_out receives the number of records even when max_records is too small (then BH_ERR_CAPACITY and nothing else is copied
+ *   but the exponents).
+ * bh_groups_times: HIP-event times of the last bh_groups: the index's build; init, link, flatten and label; the catalogue.
+ * They read the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.
+ * Errors: BH_ERR_ARG for a negative or non-finite linking length, min_members < 1, a null n_groups, and -- found by the bounds
+ *   pass, with a message that says so -- a non-finite body position; with a catalogue also for a non-finite mass or velocity (or
+ *   a moment that overflows fp64).  BH_ERR_CAPACITY for more than 2^24 bodies.  BH_ERR_STATE before any upload, in LET mode and
+ *   with world > 1 (a group can span ranks).  Without bodies *n_groups = 0 and the catalogue is empty. */
+int bh_groups(bh_ctx *ctx, double linking_length, int64_t min_members, int64_t *label, int64_t *n_groups, int64_t *n_catalogue,
+              uint64_t stats[3]);
+int bh_groups_catalogue(bh_ctx *ctx, int64_t max_records, int64_t *labels, int64_t *counts, int64_t *sums, int32_t exponents[5],
+                        int64_t *n_out);
+int bh_groups_times(bh_ctx *ctx, double *build_ms, double *link_ms, double *catalogue_ms);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
