@@ -79,6 +79,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     uint16_t *sort_dig = nullptr;  // bucket of every key (written by the histogram, read by the scatter)
     int build_items = 0;           // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
     bool hilbert = false;                // fp32 mode: Hilbert-ordered keys (BH_HILBERT=0 disables, A/B)
+    bool chain_collapse = true;          // fp32 step build: slots link past single-child cell chains (BH_CHAIN_COLLAPSE=0 disables, A/B)
     double *bslots = nullptr;      // kBoundSlots running bounds records (bh_bounds.hpp)
 
     // state (double2/double or float2/float).  Exact mode: caller order.  fp32 / mixed: DEVICE order --
@@ -322,14 +323,20 @@ __global__ __launch_bounds__(kBlock) void reorder_state_kernel(uint32_t *__restr
 
 // fp32 node kernel.  full_aux: also the {first body, count} record of every node (the host export needs them;
 // a step only needs those of bucket leaves).  Inputs are what the build left on the device, so it can be run
-// again after the build (export_tree_host).
+// again after the build (export_tree_host).  The step build of a single-GPU context links past single-child cell chains
+// (nodes_fast_kernel, COLLAPSE); the export keeps the reference's tree -- every link -- and so does a LET context that has
+// peers, whose extraction marks and packs quads by index (bh_let.hpp: a quad's need mask is written through the link to it).
+// A LET context of world 1 has nobody to extract for -- every need mask it writes is zero, and the masks start out zero
+// (bh_let_configure) -- so it takes the single context's links and stays that context's walk bit for bit.
 static void launch_nodes_fast(bh_ctx *c, bool full_aux, hipStream_t st)
 {
-    dispatch([&](auto compat, auto full) {
-        hipLaunchKernelGGL((nodes_fast_kernel<decltype(compat)::value, decltype(full)::value>), dim3(blocks_for(cell_span(c), kBlock)),
+    dispatch([&](auto compat, auto full, auto chains) {
+        constexpr bool kCollapse = decltype(chains)::value && !decltype(full)::value;
+        hipLaunchKernelGGL((nodes_fast_kernel<decltype(compat)::value, decltype(full)::value, kCollapse>),
+                           dim3(blocks_for(cell_span(c), kBlock)),
                            dim3(kBlock), 0, st, c->keys_sorted, c->coarse, c->cnt, c->cell_first, c->spos, c->smass, c->box,
                            c->terms, c->n, c->Dm, c->cfg.theta, c->internal_cap, c->qf, c->aux, c->ctr);
-    }, c->compat, full_aux);
+    }, c->compat, full_aux, c->chain_collapse && !(c->let_mode && c->world > 1));
 }
 
 // before the bounds are folded into the slot records (bh_bounds.hpp): every record +-inf
@@ -953,6 +960,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     if (const char *e = std::getenv("BH_REORDER_EVERY")) c->reorder_every = std::max(0, std::atoi(e));
     c->hilbert = !c->tree64();
     if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
+    if (const char *e = std::getenv("BH_CHAIN_COLLAPSE")) c->chain_collapse = std::atoi(e) != 0;
     auto bail = [&](int rc) { g_create_error = c->err; bh_destroy(c); return rc; };
 
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(BH_ERR_DEVICE); }
@@ -2648,6 +2656,7 @@ int bh_let_configure(bh_ctx *c, int32_t rank, int32_t world, int64_t let_cap, in
     if (rc) return rc;
     BH_HIP(c, hipMemset(c->let_ctr, 0, sizeof(LetCounters)));
     BH_HIP(c, hipMemset(c->let_tsum, 0, kMaxWorld * sizeof(uint32_t)));
+    BH_HIP(c, hipMemset(c->needmask, 0, (size_t)std::max<int64_t>(c->quads_local, 1) * sizeof(uint64_t)));
     c->let_mode = true;
     c->external_box = true;
     c->let_configured();

@@ -867,7 +867,16 @@ constexpr int kKeyWin = kBlock + 1 + kKeyHalo;
 // this kernel); the step itself only needs those of bucket leaves -- 32 of the 112 bytes a cell writes, and
 // 8 of the 28 KB of LDS staging.  (Asking for 7 resident workgroups instead of 5 made it SLOWER, 55 -> 58 us at N = 1M:
 // the 72-register budget costs more than the extra residency returns.)
-template <bool COMPAT, bool FULL_AUX = false>
+// COLLAPSE (the step build only, never with FULL_AUX; BH_CHAIN_COLLAPSE=0 turns it off): the slot of a subdivided
+// child C links past the chain of cells below C that hold exactly C's bodies.  Those cells Z_1 = C, Z_2, ... Z_k
+// (each one the only non-empty child of the one before) have the same body range, so the same prefix-sum difference:
+// mass and centre are the same bits, only the threshold shrinks by 4 per level.  A lane accepts the chain at SOME
+// level iff d2 > thr(Z_k), with the same term whichever level that is, and otherwise opens all of them: the slot
+// carries thr(Z_k) and the quad of Z_k, and no walk visits Z_1 .. Z_(k-1)'s quads.  The chain's
+// cells share their first body and sit at consecutive depths, so their ranks are consecutive: rank(Z_k) = rank(C) +
+// k - 1, and k - 1 = min(shared levels of C's first and last key, Dm - 1) - depth(C).  Nothing deeper than an
+// existing subdivided cell is linked, and a depth-cap cell is still reached through its parent's quad.
+template <bool COMPAT, bool FULL_AUX = false, bool COLLAPSE = false>
 __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
     const uint64_t *__restrict__ keys, const uint64_t *__restrict__ coarse,
     const uint32_t *__restrict__ off, const uint32_t *__restrict__ cell_first,
@@ -876,6 +885,7 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
     int64_t n64, int Dm, double theta, int64_t internal_cap, QuadF *__restrict__ qf,
     NodeAux *__restrict__ aux, TreeCounters *ctr)
 {
+    static_assert(!(FULL_AUX && COLLAPSE), "the exported tree keeps every link");
     // ONE THREAD PER SUBDIVIDED CELL (rank r): its first body comes from cell_first[r], its depth
     // from its position in that body's chain.  32-bit indices throughout (bh_create caps n < 2^31).
     // LDS is used twice: first as the key window of the searches, then -- after a barrier -- as the
@@ -1111,7 +1121,10 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
     if (d == 0) {                                                // root record in quad 0
         for (int k = 1; k < 4; ++k) { put(0, k, 0.f, 0.f, 0.f, -1.f, -1); aux[k] = NodeAux{0, 0}; }
         const d3 t = psum[n];
-        if (t.a > 1e-15) put(0, 0, (float)(t.b / t.a), (float)(t.c / t.a), (float)t.a, (float)thr0, quad);
+        // (COLLAPSE: the root record links past the root's own chain like any other slot; n >= 2 here)
+        int dz0 = 0;
+        if (COLLAPSE) { const int s0 = shared_levels(key, K(n - 1), Dm); dz0 = (s0 < Dm - 1) ? s0 : Dm - 1; }
+        if (t.a > 1e-15) put(0, 0, (float)(t.b / t.a), (float)(t.c / t.a), (float)t.a, (float)ldexp(thr0, -2 * dz0), quad + dz0);
         else put(0, 0, 0.f, 0.f, 0.f, -1.f, -1);
         aux[0] = NodeAux{0, n};
     }
@@ -1151,7 +1164,7 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
     }
     d3 ps[5];
     uint32_t offc[4];
-    uint64_t kprev[4], kcur[4];
+    uint64_t kprev[4], kcur[4], klast[4];
     float2 p1[4];
     float m1[4];
     // (only what the child's kind needs: most cells sit at the bottom of the tree, their children are single
@@ -1170,9 +1183,11 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
         if (cells_in_window) {
             kcur[c] = sub ? KF(bc) : 0ull;
             kprev[c] = (sub && bc > 0) ? KF(bc - 1) : 0ull;
+            klast[c] = (COLLAPSE && sub) ? KF(bnd[c + 1] - 1) : 0ull;
         } else {
             kcur[c] = sub ? K(bc) : 0ull;
             kprev[c] = (sub && bc > 0) ? K(bc - 1) : 0ull;
+            klast[c] = (COLLAPSE && sub) ? K(bnd[c + 1] - 1) : 0ull;
         }
         p1[c] = (ncc == 1) ? spos[bc] : float2{0.f, 0.f};
         m1[c] = (ncc == 1) ? smass[bc] : 0.f;
@@ -1201,6 +1216,14 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
                 const int Lpc = (bc == 0) ? -1 : shared_levels(kprev[c], kcur[c], Dm);
                 child = (int32_t)(offc[c] + (uint32_t)((d + 1) - (Lpc + 1))) + 1;
                 thr = thr_child;
+                if (COLLAPSE) {
+                    // m, cx, cy above come from the prefix-sum difference of [bc, bn) alone: the same for every cell
+                    // of the chain.  All of the child's keys share at least d + 1 levels and d + 1 <= Dm - 1, so dz >= d + 1.
+                    const int sl = shared_levels(kcur[c], klast[c], Dm);
+                    const int dz = (sl < Dm - 1) ? sl : Dm - 1;
+                    child += dz - (d + 1);
+                    thr = (float)ldexp(thr0, -2 * dz);
+                }
             }
         }
         if (!(m > 1e-15f)) { cx = 0.f; cy = 0.f; m = 0.f; thr = 0.f; child = -1; }   // project.cu:617
