@@ -123,7 +123,14 @@ SIGNATURES = {
     "bh_moment_map_max": (C.c_int, [_ctx, _dp]),
     "bh_moment_map_deposit": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp),
                                         C.POINTER(C.c_int64)]),
-    "bh_neighbours": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
+    "bh_radial_profile": (C.c_int, [_ctx, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "bh_radial_max": (C.c_int, [_ctx, _dp, _dp, _dp]),
+    "bh_radial_deposit": (C.c_int, [_ctx, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp)]),
+    "bh_lagrangian_radii": (C.c_int, [_ctx, _dp, _dp, C.c_int32, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int32)]),
+    "bh_radial_select": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(_vp)]),
+    "bh_radial_times": (C.c_int, [_ctx, _dp, _dp, _dp]),
+    "bh_neighbours": (C.c_int,[_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
     "bh_count_within": (C.c_int, [_ctx, _dp, C.c_int64, C.c_double, C.POINTER(C.c_uint32)]),
     "bh_neighbours_times": (C.c_int, [_ctx, _dp, _dp]),
     "bh_groups": (C.c_int, [_ctx, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),

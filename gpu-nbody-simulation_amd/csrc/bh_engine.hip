@@ -25,6 +25,7 @@
 #include "bh_migrate.hpp"
 #include "bh_split.hpp"
 #include "bh_moments.hpp"
+#include "bh_radial.hpp"
 #include "bh_neighbours.hpp"
 #include "bh_groups.hpp"
 #include "bh_walk_fast.h"
@@ -142,6 +143,15 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     unsigned long long *map_count = nullptr;
     long long *map_planes = nullptr;
     int64_t map_cells = 0;
+    // radial profiles and Lagrangian radii (bh_radial.hpp), allocated on first use: the first pass's record, the select's flags,
+    // the squared edges, the 6-plane int64 profile of up to BH_RADIAL_MAX_BINS + 2 slots, a round's histograms
+    RadMax *rad_max = nullptr;
+    unsigned long long *rad_flags = nullptr;
+    double *rad_e2 = nullptr;
+    long long *rad_planes = nullptr, *rad_hist = nullptr;
+    int rad_blocks = 512;              // BH_RADIAL_BLOCKS: most persistent workgroups of the radial kernels
+    hipEvent_t rad_ev[4 + 2 * kRadRounds] = {};                     // around the first pass, the deposit, and every select round
+    double rad_max_ms = 0.0, rad_main_ms = 0.0, rad_round_ms[kRadRounds] = {};     // of the last call (bh_radial_times)
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -961,6 +971,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     c->hilbert = !c->tree64();
     if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_CHAIN_COLLAPSE")) c->chain_collapse = std::atoi(e) != 0;
+    if (const char *e = std::getenv("BH_RADIAL_BLOCKS")) { const int b = std::atoi(e); if (b >= 1 && b <= 65536) c->rad_blocks = b; }
     auto bail = [&](int rc) { g_create_error = c->err; bh_destroy(c); return rc; };
 
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(BH_ERR_DEVICE); }
@@ -1052,7 +1063,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb_ev);
-    destroy(c->fof_ev);
+    destroy(c->fof_ev); destroy(c->rad_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1577,6 +1588,338 @@ int bh_moment_map(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t 
     if (int rc = map_deposit(c, "bh_moment_map", box, nx, ny, scheme, e, m, n_deposited)) return rc;
     BH_HIP(c, hipMemcpy(planes, c->map_planes, (size_t)kMapPlanes * nx * ny * sizeof(int64_t), hipMemcpyDeviceToHost));
     std::copy(e, e + kMapPlanes, exponents);
+    return BH_OK;
+}
+
+// ---- radial profiles and Lagrangian radii (bh_radial.hpp).  As the moment maps: they read pos / vel / mass as they lie in
+// memory and write buffers of their own -- no tree, no build, so there is nothing for a quiet scope (bh_run_state.hpp) to put
+// back: no record of it is touched, and a step before and after runs bit for bit as it would have.
+static int rad_alloc(bh_ctx *c)
+{
+    for (auto &e : c->rad_ev)
+        if (!e) BH_HIP(c, hipEventCreate(&e));
+    if (c->rad_max) return BH_OK;
+    int rc = dev_alloc(c, &c->rad_max, 1);
+    if (!rc) rc = dev_alloc(c, &c->rad_flags, 1);
+    if (!rc) rc = dev_alloc(c, &c->rad_e2, (size_t)kRadMaxBins + 1);
+    if (!rc) rc = dev_alloc(c, &c->rad_planes, (size_t)(kRadPlanes + 1) * (kRadMaxBins + 2));
+    if (!rc) rc = dev_alloc(c, &c->rad_hist, (size_t)kRadMaxFractions * kRadDigits * 2);
+    if (rc) {
+        for (void *p : {(void *)c->rad_max, (void *)c->rad_flags, (void *)c->rad_e2, (void *)c->rad_planes, (void *)c->rad_hist}) dev_free(c, p);
+        c->rad_max = nullptr; c->rad_flags = nullptr; c->rad_e2 = nullptr; c->rad_planes = nullptr; c->rad_hist = nullptr;
+    }
+    return rc;
+}
+
+static int rad_centre(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, RadCentre *out)
+{
+    if (!centre) return fail(c, BH_ERR_ARG, std::string(who) + ": null centre");
+    *out = RadCentre{centre[0], centre[1], centre_vel ? centre_vel[0] : 0.0, centre_vel ? centre_vel[1] : 0.0};
+    if (!(std::isfinite(out->cx) && std::isfinite(out->cy) && std::isfinite(out->ux) && std::isfinite(out->uy)))
+        return fail(c, BH_ERR_ARG, std::string(who) + ": the centre or its velocity is not finite");
+    return BH_OK;
+}
+
+// the squared edges on the host; BH_ERR_ARG unless the edges and their squares are finite, >= 0 and strictly ascending
+static int rad_edges(bh_ctx *c, const char *who, const double *edges, int32_t nb, std::vector<double> &e2)
+{
+    const std::string w(who);
+    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
+    if (nb < 1 || nb > kRadMaxBins) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_RADIAL_MAX_BINS = " + std::to_string(kRadMaxBins));
+    e2.resize((size_t)nb + 1);
+    for (int k = 0; k <= nb; ++k) {
+        e2[(size_t)k] = edges[k] * edges[k];
+        if (!std::isfinite(edges[k]) || !std::isfinite(e2[(size_t)k])) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
+        if (edges[k] < 0.0) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
+        if (k > 0 && !(edges[k - 1] < edges[k] && e2[(size_t)k - 1] < e2[(size_t)k]))
+            return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
+    }
+    return BH_OK;
+}
+
+// persistent workgroups: at most rad_blocks of them, and none without a body
+static unsigned rad_grid(const bh_ctx *c) { return std::min<unsigned>((unsigned)c->rad_blocks, blocks_for(c->n, kBlock)); }
+
+// pass 1: the five maxima on the host when this returns (with_vel = false: the mass alone, the velocities are not read);
+// BH_ERR_ARG when a body is not finite, or -- no_negative -- when a mass is negative
+static int rad_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, bool with_vel, bool no_negative, double (&maxabs)[kRadPlanes])
+{
+    for (double &v : maxabs) v = 0.0;
+    c->rad_max_ms = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = rad_alloc(c)) return rc;
+    BH_HIP(c, hipEventRecord(c->rad_ev[0], c->stream));
+    BH_HIP(c, hipMemsetAsync(c->rad_max, 0, sizeof(RadMax), c->stream));
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        using Real = decltype(r2.x);
+        dispatch([&](auto vel) {
+            hipLaunchKernelGGL((radial_max_kernel<decltype(vel)::value, Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), 0,
+                               c->stream, static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
+                               static_cast<const Real *>(c->mass), c->n, ctr, c->rad_max);
+        }, with_vel);
+    });
+    BH_HIP(c, hipGetLastError());
+    BH_HIP(c, hipEventRecord(c->rad_ev[1], c->stream));
+    RadMax r{};
+    BH_HIP(c, hipMemcpyAsync(&r, c->rad_max, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[0], c->rad_ev[1]));
+    c->rad_max_ms = (double)ms;
+    if (r.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a squared radius or a "
+                                   "moment m vr, m vt, m vr^2, m vt^2 that overflows fp64)");
+    if (no_negative && r.negative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
+    for (int p = 0; p < kRadPlanes; ++p) std::memcpy(&maxabs[p], &r.bits[p], sizeof(double));
+    return BH_OK;
+}
+
+static int32_t rad_exponent(double maxabs, int L)
+{
+    int E = 0;
+    if (maxabs == 0.0) return 0;
+    (void)std::frexp(maxabs, &E);
+    return 62 - E - L;
+}
+
+// pass 2 with the exponents e: the planes stay on the device (rad_planes, 6 x (nb + 2))
+static int rad_deposit(bh_ctx *c, const char *who, const RadCentre &ctr, const std::vector<double> &e2, int32_t nb, const int32_t *e,
+                       const double (&maxabs)[kRadPlanes])
+{
+    const int L = map_log2_ceil(c->n);
+    for (int p = 0; p < kRadPlanes; ++p) {
+        int E = 0;
+        if (maxabs[p] != 0.0) (void)std::frexp(maxabs[p], &E);
+        if (maxabs[p] != 0.0 && (int64_t)E + e[p] + L > 62)
+            return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
+                                       " is too large for this context's bodies (at most " + std::to_string(62 - E - L) + ")");
+    }
+    if (int rc = rad_alloc(c)) return rc;
+    const int S = nb + 2;
+    c->rad_main_ms = 0.0;
+    for (double &v : c->rad_round_ms) v = 0.0;
+    BH_HIP(c, hipEventRecord(c->rad_ev[2], c->stream));
+    BH_HIP(c, hipMemsetAsync(c->rad_planes, 0, (size_t)(kRadPlanes + 1) * S * sizeof(long long), c->stream));
+    if (c->n > 0) {
+        BH_HIP(c, hipMemcpyAsync(c->rad_e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        RadExp ex{};
+        for (int p = 0; p < kRadPlanes; ++p) ex.e[p] = e[p];
+        const bool priv = S <= kRadLdsSlots;
+        const size_t lds = priv ? ((size_t)(kRadPlanes + 1) * S + (size_t)nb + 1) * 8 : (size_t)(kRadPlanes + 1) * kRadLdsSlots * 8;
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            dispatch([&](auto p) {
+                hipLaunchKernelGGL((radial_deposit_kernel<decltype(p)::value, Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), lds, c->stream,
+                                   static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
+                                   static_cast<const Real *>(c->mass), c->n, ctr, c->rad_e2, (int)nb, ex, c->rad_planes);
+            }, priv);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    BH_HIP(c, hipEventRecord(c->rad_ev[3], c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 is the caller's until the copy has run)
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[2], c->rad_ev[3]));
+    c->rad_main_ms = (double)ms;
+    return BH_OK;
+}
+
+int bh_radial_max(bh_ctx *c, const double *centre, const double *centre_vel, double *maxabs)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_radial_max: null output");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_radial_max", centre, centre_vel, &ctr)) return rc;
+    if (int rc = need_upload(c, "bh_radial_max before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_radial_max", ctr, true, false, m)) return rc;
+    std::copy(m, m + kRadPlanes, maxabs);
+    return BH_OK;
+}
+
+int bh_radial_deposit(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb,
+                      const int32_t *exponents, void **planes_dev)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!exponents || !planes_dev) return fail(c, BH_ERR_ARG, "bh_radial_deposit: null argument");
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = rad_centre(c, "bh_radial_deposit", centre, centre_vel, &ctr)) return rc;
+    if (int rc = rad_edges(c, "bh_radial_deposit", edges, nb, e2)) return rc;
+    if (int rc = need_upload(c, "bh_radial_deposit before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_radial_deposit", ctr, true, false, m)) return rc;
+    if (int rc = rad_deposit(c, "bh_radial_deposit", ctr, e2, nb, exponents, m)) return rc;
+    *planes_dev = c->rad_planes;
+    return BH_OK;
+}
+
+int bh_radial_profile(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int64_t *planes,
+                      int32_t *exponents)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_radial_profile: null argument");
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = rad_centre(c, "bh_radial_profile", centre, centre_vel, &ctr)) return rc;
+    if (int rc = rad_edges(c, "bh_radial_profile", edges, nb, e2)) return rc;
+    if (int rc = need_upload(c, "bh_radial_profile before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_radial_profile", ctr, true, false, m)) return rc;
+    const int L = map_log2_ceil(c->n);
+    int32_t e[kRadPlanes];
+    for (int p = 0; p < kRadPlanes; ++p) e[p] = rad_exponent(m[p], L);
+    if (int rc = rad_deposit(c, "bh_radial_profile", ctr, e2, nb, e, m)) return rc;
+    BH_HIP(c, hipMemcpy(planes, c->rad_planes, (size_t)(kRadPlanes + 1) * (nb + 2) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kRadPlanes, exponents);
+    return BH_OK;
+}
+
+// one round: rad_hist[np][256][2] on the device and complete when this returns; timed between rad_ev[4 + 2 round] and the next
+static int rad_select_round(bh_ctx *c, const char *who, const RadCentre &ctr, int32_t e0, int32_t round, const uint64_t *prefixes,
+                            int32_t np)
+{
+    if (int rc = rad_alloc(c)) return rc;
+    const int L = map_log2_ceil(c->n);
+    BH_HIP(c, hipEventRecord(c->rad_ev[4 + 2 * round], c->stream));
+    BH_HIP(c, hipMemsetAsync(c->rad_hist, 0, (size_t)np * kRadDigits * 2 * sizeof(long long), c->stream));
+    BH_HIP(c, hipMemsetAsync(c->rad_flags, 0, sizeof(unsigned long long), c->stream));
+    for (int32_t p0 = 0; p0 < np && c->n > 0; p0 += kRadSelChunk) {
+        RadSelect s{};
+        s.cx = ctr.cx; s.cy = ctr.cy;
+        s.m_limit = std::ldexp(1.0, 62 - L - e0);
+        s.e0 = e0;
+        s.hi_shift = 64 - kRadDigitBits * round;
+        s.lo_shift = 64 - kRadDigitBits * (round + 1);
+        s.np = std::min<int32_t>(kRadSelChunk, np - p0);
+        for (int k = 0; k < s.np; ++k) s.prefix[k] = prefixes[p0 + k];
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((radial_select_kernel<Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), 0, c->stream,
+                               static_cast<const Real2 *>(c->pos), static_cast<const Real *>(c->mass), c->n, s,
+                               c->rad_hist + (size_t)p0 * kRadDigits * 2, c->rad_flags);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    BH_HIP(c, hipEventRecord(c->rad_ev[5 + 2 * round], c->stream));
+    unsigned long long flags = 0;
+    BH_HIP(c, hipMemcpyAsync(&flags, c->rad_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[4 + 2 * round], c->rad_ev[5 + 2 * round]));
+    c->rad_round_ms[round] = (double)ms;
+    if (flags & kRadFlagBad) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position or mass (or a squared radius that overflows fp64)");
+    if (flags & kRadFlagNegative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
+    if (flags & kRadFlagLarge)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e0) + " is too large for this context's masses and body count");
+    return BH_OK;
+}
+
+static int rad_select_args(bh_ctx *c, const char *who, int32_t round, const uint64_t *prefixes, int32_t np)
+{
+    const std::string w(who);
+    if (round < 0 || round >= kRadRounds) return fail(c, BH_ERR_ARG, w + ": round must be 0 .. 7");
+    if (!prefixes) return fail(c, BH_ERR_ARG, w + ": null prefixes");
+    if (np < 1 || np > kRadMaxFractions) return fail(c, BH_ERR_ARG, w + ": np must be 1 .. BH_RADIAL_MAX_FRACTIONS");
+    if (round == 0 && (np != 1 || prefixes[0] != 0)) return fail(c, BH_ERR_ARG, w + ": round 0 has the one prefix 0");
+    for (int32_t a = 0; a < np; ++a) {
+        if (round > 0 && (prefixes[a] >> (kRadDigitBits * round)) != 0) return fail(c, BH_ERR_ARG, w + ": a prefix has more digits than the round");
+        for (int32_t b = 0; b < a; ++b)
+            if (prefixes[a] == prefixes[b]) return fail(c, BH_ERR_ARG, w + ": the prefixes must be distinct");
+    }
+    return BH_OK;
+}
+
+int bh_radial_select(bh_ctx *c, const double *centre, int32_t exponent, int32_t round, const uint64_t *prefixes, int32_t np,
+                     void **hist_dev)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!hist_dev) return fail(c, BH_ERR_ARG, "bh_radial_select: null output");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_radial_select", centre, nullptr, &ctr)) return rc;
+    if (int rc = rad_select_args(c, "bh_radial_select", round, prefixes, np)) return rc;
+    if (int rc = need_upload(c, "bh_radial_select before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    c->rad_max_ms = 0.0; c->rad_main_ms = 0.0;
+    for (double &v : c->rad_round_ms) v = 0.0;
+    if (int rc = rad_select_round(c, "bh_radial_select", ctr, exponent, round, prefixes, np)) return rc;
+    c->rad_main_ms = c->rad_round_ms[round];
+    *hist_dev = c->rad_hist;
+    return BH_OK;
+}
+
+int bh_lagrangian_radii(bh_ctx *c, const double *centre, const double *fractions, int32_t nf, double *r2, int64_t *count, int64_t *mass,
+                        int32_t *exponent)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!fractions || !r2 || !count || !mass || !exponent) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: null argument");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_lagrangian_radii", centre, nullptr, &ctr)) return rc;
+    if (nf < 1 || nf > kRadMaxFractions) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: nf must be 1 .. BH_RADIAL_MAX_FRACTIONS = 32");
+    for (int32_t f = 0; f < nf; ++f)
+        if (!(std::isfinite(fractions[f]) && fractions[f] > 0.0 && fractions[f] <= 1.0))
+            return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: a fraction must be finite, > 0 and <= 1");
+    if (int rc = need_upload(c, "bh_lagrangian_radii before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_lagrangian_radii", ctr, false, true, m)) return rc;
+    const int32_t e0 = rad_exponent(m[0], map_log2_ceil(c->n));
+    *exponent = e0;
+    c->rad_main_ms = 0.0;
+    for (double &v : c->rad_round_ms) v = 0.0;
+    // the decisions between the rounds are made here, on the host, from the downloaded histograms
+    uint64_t prefix[kRadMaxFractions] = {0};                     // the digits decided so far, per fraction
+    int64_t below_w[kRadMaxFractions] = {0}, below_n[kRadMaxFractions] = {0}, target[kRadMaxFractions] = {0};
+    std::vector<int64_t> hist((size_t)kRadMaxFractions * kRadDigits * 2);
+    for (int32_t round = 0; round < kRadRounds; ++round) {
+        uint64_t distinct[kRadMaxFractions];
+        int32_t which[kRadMaxFractions], np = 0;
+        for (int32_t f = 0; f < nf; ++f) {
+            int32_t k = 0;
+            while (k < np && distinct[k] != prefix[f]) ++k;
+            if (k == np) distinct[np++] = prefix[f];
+            which[f] = k;
+        }
+        if (int rc = rad_select_round(c, "bh_lagrangian_radii", ctr, e0, round, distinct, np)) return rc;
+        c->rad_main_ms += c->rad_round_ms[round];
+        BH_HIP(c, hipMemcpy(hist.data(), c->rad_hist, (size_t)np * kRadDigits * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (round == 0) {
+            int64_t W = 0;
+            for (int d = 0; d < kRadDigits; ++d) W += hist[(size_t)d * 2];
+            if (W == 0) {
+                for (int32_t f = 0; f < nf; ++f) { r2[f] = std::nan(""); count[f] = 0; mass[f] = 0; }
+                return BH_OK;
+            }
+            for (int32_t f = 0; f < nf; ++f)
+                target[f] = std::min<int64_t>(W, std::max<int64_t>(1, (int64_t)std::ceil(fractions[f] * (double)W)));
+        }
+        for (int32_t f = 0; f < nf; ++f) {
+            const int64_t *h = hist.data() + (size_t)which[f] * kRadDigits * 2;
+            int d = 0;
+            while (d < kRadDigits - 1 && below_w[f] + h[2 * d] < target[f]) { below_w[f] += h[2 * d]; below_n[f] += h[2 * d + 1]; ++d; }
+            prefix[f] = (prefix[f] << kRadDigitBits) | (uint64_t)d;
+            if (round == kRadRounds - 1) {
+                std::memcpy(&r2[f], &prefix[f], sizeof(double));
+                count[f] = below_n[f] + h[2 * d + 1];
+                mass[f] = below_w[f] + h[2 * d];
+            }
+        }
+    }
+    return BH_OK;
+}
+
+int bh_radial_times(bh_ctx *c, double *max_ms, double *main_ms, double *rounds_ms)
+{
+    if (!c || !max_ms || !main_ms) return fail(c, BH_ERR_ARG, "bh_radial_times: null argument");
+    *max_ms = c->rad_max_ms;
+    *main_ms = c->rad_main_ms;
+    if (rounds_ms) std::copy(c->rad_round_ms, c->rad_round_ms + kRadRounds, rounds_ms);
     return BH_OK;
 }
 

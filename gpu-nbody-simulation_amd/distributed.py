@@ -607,6 +607,96 @@ class LetStepper:
         planes = g.cpu().numpy().reshape(4, ny, nx).copy()
         return moment_map_from_planes(planes, e, b, scheme, int(nd.item()), raw)
 
+    def _radial_centre(self, centre, what: str):
+        """(cx, cy) of "com" (energy().com, the same bits on every rank) or a pair; "density" is a single-GPU search."""
+        import numpy as np
+        if isinstance(centre, str):
+            if centre == "com":
+                return np.array(self.energy().com, dtype=np.float64)
+            if centre == "density":
+                raise ValueError(f"{what}: centre='density' needs the neighbour search, which is single-GPU; use 'com' or a pair")
+            raise ValueError(f"{what}: centre must be 'com' or a pair (x, y)")
+        c = np.ascontiguousarray(centre, dtype=np.float64).reshape(-1)
+        if len(c) != 2:
+            raise ValueError(f"{what}: centre must be 'com' or a pair (x, y)")
+        return c
+
+    def _radial_agree(self, what: str, args, maxima, bad):
+        """The first collectives of a radial call: MAX of (args, -args, maxima, error flag) and SUM of the body counts.
+        Raises on every rank when one rank's first pass failed or the arguments differ.  -> (maxima of the whole system, n)."""
+        on_dev = self.lbounds.is_cuda and not self._staged()      # RCCL takes device tensors, gloo host tensors
+        dev = self.lbounds.device if on_dev else "cpu"
+        a = torch.tensor([float(x) for x in args], dtype=torch.float64, device=dev)
+        hi = torch.cat([a, -a, torch.tensor([*maxima, 1.0 if bad is not None else 0.0], dtype=torch.float64, device=dev)])
+        cnt = torch.tensor([int(self.eng.n)], dtype=torch.int64, device=dev)
+        if dist.is_initialized() and self.world > 1:
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+        hi, a = hi.cpu(), a.cpu()
+        k = a.numel()
+        if bad is not None or float(hi[-1]) != 0.0:
+            raise bad if bad is not None else ValueError(f"{what}: another rank has a body it cannot take (non-finite, or a negative mass)")
+        if not (torch.equal(hi[:k], a) and torch.equal(hi[k:2 * k], -a)):      # (a NaN fails too)
+            raise ValueError(f"{what}: the ranks disagree on the arguments (rank {self.rank} has {a.tolist()})")
+        return hi[2 * k:-1].numpy(), int(cnt.item())
+
+    def radial_profile(self, edges, centre="com", centre_velocity=None, raw: bool = False):
+        """BhRadialProfile of the WHOLE system (engine.radial_profile), the same bits on every rank and the same bits as one
+        engine's profile of the same bodies.  all_reduce MAX of the ranks' five maxima and SUM of their body counts, from which
+        every rank derives the same exponents; each rank bins its own bodies in fixed point; one all_reduce(SUM) of the int64
+        planes.  centre: "com" or a pair.  Collective: every rank must call it with the same arguments (checked: ValueError on
+        every rank if not).  Reads the state only."""
+        import numpy as np
+        from .engine import radial_exponents, radial_profile_from_planes
+        c = self._radial_centre(centre, "radial_profile")
+        u = np.zeros(2) if centre_velocity is None else np.ascontiguousarray(centre_velocity, dtype=np.float64).reshape(2)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(ed) - 1
+        try:
+            mx, bad = self.eng.radial_max(c, u), None
+        except Exception as err:                                  # noqa: BLE001 -- re-raised below, after the collective
+            mx, bad = np.zeros(5), err
+        hi, n_total = self._radial_agree("radial_profile", [*c, *u, float(nb), *ed], mx, bad)
+        e = radial_exponents(hi, n_total)
+        g = self.eng.radial_deposit(ed, c, u, e)
+        if not isinstance(g, torch.Tensor):                       # stand-in engines hand a tensor over directly
+            g = wrap_device(g, 6 * (nb + 2), "<i8", self.device)
+        g = self._all_reduce_(g, dist.ReduceOp.SUM)
+        return radial_profile_from_planes(g.cpu().numpy().reshape(6, nb + 2).copy(), e, ed, c, u, raw)
+
+    def lagrangian_radii(self, fractions=(0.01, 0.1, 0.5, 0.9), centre="com"):
+        """BhLagrangian of the WHOLE system (engine.lagrangian_radii), the same bits on every rank and the same bits as one
+        engine's radii of the same bodies.  all_reduce MAX of the ranks' largest masses and SUM of their body counts give the
+        exponent; then eight rounds: each rank histograms its own bodies (engine.radial_select), one all_reduce(SUM) of the
+        round's int64 histograms, and every rank makes the same decision from the same integers (engine.LagrangianSelect).
+        centre: "com" or a pair.  Collective: the same arguments on every rank (checked).  Reads the state only."""
+        import numpy as np
+        from .engine import LagrangianSelect, lagrangian_from, radial_exponents
+        c = self._radial_centre(centre, "lagrangian_radii")
+        sel = LagrangianSelect(fractions)
+        try:
+            mx, bad = self.eng.radial_max(c)[:1], None            # (the largest mass; the velocities must be finite too)
+        except Exception as err:                                  # noqa: BLE001 -- re-raised below, after the collective
+            mx, bad = np.zeros(1), err
+        hi, n_total = self._radial_agree("lagrangian_radii", [*c, float(len(sel.fractions)), *sel.fractions], mx, bad)
+        e0 = int(radial_exponents(hi, n_total)[0])
+        while not sel.done:
+            pre = sel.prefixes()
+            words = len(pre) * 512
+            t = torch.zeros(words + 1, dtype=torch.int64, device=self.device)      # (the last word: a rank's select failed)
+            try:
+                h, bad = self.eng.radial_select(c, e0, sel.round, pre), None
+                t[:words] = h if isinstance(h, torch.Tensor) else wrap_device(h, words, "<i8", self.device)
+            except Exception as err:                              # noqa: BLE001 -- re-raised below, after the collective
+                bad = err
+                t[words] = 1
+            t = self._all_reduce_(t, dist.ReduceOp.SUM).cpu()
+            if bad is not None or int(t[words]) != 0:
+                raise bad if bad is not None else ValueError("lagrangian_radii: another rank has a body it cannot take "
+                                                             "(non-finite, or a negative mass)")
+            sel.advance(t[:words].numpy().reshape(len(pre), 256, 2))
+        return lagrangian_from(sel.fractions, *sel.result(), e0, c)
+
     @property
     def ids(self):
         """Global identifiers of this rank's bodies in the order download() returns them."""

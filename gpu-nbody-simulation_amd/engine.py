@@ -170,6 +170,174 @@ def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int
                        planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
 
 
+RADIAL_MAX_BINS = 4096                  # BH_RADIAL_MAX_BINS
+RADIAL_MAX_FRACTIONS = 32               # BH_RADIAL_MAX_FRACTIONS
+RADIAL_DIGIT_BITS = 8                   # BH_RADIAL_DIGIT_BITS
+
+
+@dataclass
+class BhRadialProfile:
+    """Radial profile of the current state about a centre on the nb bins between edges (radial_profile): fp64 arrays (nb,)
+    unless said otherwise.  mass and the enclosed masses are the fixed-point sums times 2^-exponent; the others are derived
+    from them, NaN in a bin without mass except sigma, which is 0 there."""
+    edges: np.ndarray            # (nb + 1,)
+    r_mid: np.ndarray            # (edges[k] + edges[k + 1]) / 2
+    count: np.ndarray            # bodies per bin, int64
+    mass: np.ndarray             # sum m
+    sigma: np.ndarray            # surface density: mass / (pi (e2[k + 1] - e2[k])), e2 the squared edges
+    vr: np.ndarray               # mass-weighted mean radial velocity
+    vt: np.ndarray               # mass-weighted mean tangential velocity: the rotation curve
+    sigma_r: np.ndarray          # sqrt(max(sum m vr^2 / mass - vr^2, 0))
+    sigma_t: np.ndarray          # sqrt(max(sum m vt^2 / mass - vt^2, 0))
+    anisotropy: np.ndarray       # 1 - (tangential variance) / (radial variance), both clipped at 0
+    mass_inside: float           # inside edges[0] ...
+    mass_outside: float          # ... and at or beyond edges[nb]
+    count_inside: int
+    count_outside: int
+    enclosed: np.ndarray         # (nb + 1,): the mass inside every edge, summed in integers
+    centre: tuple
+    centre_velocity: tuple
+    planes: np.ndarray | None = None      # raw=True: the int64 sums (6, nb + 2), plane 5 the counts ...
+    exponents: np.ndarray | None = None   # ... and the five exponents: value = planes * 2^-exponent
+
+
+@dataclass
+class BhLagrangian:
+    """Lagrangian radii of the current state about a centre (lagrangian_radii): per fraction, in the caller's order."""
+    fractions: np.ndarray
+    r: np.ndarray                # sqrt(r2), taken on the host
+    r2: np.ndarray               # the squared radius of a body: the smallest that encloses the fraction (NaN without mass)
+    count: np.ndarray            # bodies with r2_i <= r2, int64
+    mass: np.ndarray             # their mass: mass_units * 2^-exponent
+    mass_units: np.ndarray       # int64: sum of rint(ldexp(m_i, exponent))
+    exponent: int
+    centre: tuple
+
+
+def radial_edges(r_min: float, r_max: float, nb: int, spacing: str = "log") -> np.ndarray:
+    """nb + 1 edges from r_min to r_max: "linear" (r_min >= 0) or "log" (r_min > 0) spacing; the end points are exact."""
+    nb = int(nb)
+    r_min, r_max = float(r_min), float(r_max)
+    if nb < 1 or not (np.isfinite(r_min) and np.isfinite(r_max) and 0.0 <= r_min < r_max):
+        raise ValueError("edges need nb >= 1 and finite 0 <= r_min < r_max")
+    if spacing == "linear":
+        e = r_min + (r_max - r_min) * (np.arange(nb + 1) / nb)
+    elif spacing == "log":
+        if r_min <= 0.0:
+            raise ValueError("log spacing needs r_min > 0")
+        e = r_min * (r_max / r_min) ** (np.arange(nb + 1) / nb)
+    else:
+        raise ValueError("spacing must be 'log' or 'linear'")
+    e[0], e[-1] = r_min, r_max
+    return e
+
+
+def radial_exponents(maxabs, n_total: int) -> np.ndarray:
+    """The exponents 62 - E_p - L of the fixed-point planes from the maxima max |q_p| (bh_radial_max, combined over the ranks
+    with MAX) and the body count of the whole system; 0 where the maximum is 0."""
+    m = np.asarray(maxabs, dtype=np.float64).reshape(-1)
+    L = 0 if n_total <= 1 else (int(n_total) - 1).bit_length()
+    _, E = np.frexp(m)
+    return np.where(m == 0.0, 0, 62 - E - L).astype(np.int32)
+
+
+def radial_profile_from_planes(planes, exponents, edges, centre, centre_velocity=(0.0, 0.0), raw: bool = False) -> BhRadialProfile:
+    """BhRadialProfile of the int64 sums (6, nb + 2) and their five exponents."""
+    planes = np.asarray(planes, dtype=np.int64)
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1).copy()
+    nb = len(edges) - 1
+    if planes.shape != (6, nb + 2):
+        raise ValueError("planes must be (6, nb + 2)")
+    e = [int(x) for x in exponents]
+    val = [np.ldexp(planes[p].astype(np.float64), -e[p]) for p in range(5)]
+    mass, pr, pt, kr, kt = (v[1:-1] for v in val)
+    e2 = edges * edges
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vr, vt = pr / mass, pt / mass
+        var_r, var_t = np.maximum(kr / mass - vr * vr, 0.0), np.maximum(kt / mass - vt * vt, 0.0)
+        beta = 1.0 - var_t / var_r
+    sig_r, sig_t = np.sqrt(var_r), np.sqrt(var_t)
+    empty = mass == 0.0
+    for a in (vr, vt, sig_r, sig_t, beta):
+        a[empty] = np.nan
+    enclosed = np.ldexp(np.cumsum(planes[0, :-1]).astype(np.float64), -e[0])       # (integer sums: |total| <= 2^62)
+    return BhRadialProfile(edges, 0.5 * (edges[:-1] + edges[1:]), planes[5, 1:-1].copy(), mass, mass / (np.pi * (e2[1:] - e2[:-1])),
+                           vr, vt, sig_r, sig_t, beta, float(val[0][0]), float(val[0][-1]), int(planes[5, 0]), int(planes[5, -1]),
+                           enclosed, tuple(float(x) for x in centre), tuple(float(x) for x in centre_velocity),
+                           planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+
+
+class LagrangianSelect:
+    """The decisions of the radix select of the Lagrangian radii, in Python integers: which prefixes the next round needs
+    (prefixes()), and which digit every fraction takes from that round's histograms (advance()).  The histograms may come
+    from one context (bh_radial_select) or be the sum of many: the decisions are the same wherever they are made."""
+    ROUNDS = 64 // RADIAL_DIGIT_BITS
+
+    def __init__(self, fractions):
+        import math
+        self.fractions = [float(f) for f in np.asarray(fractions, dtype=np.float64).reshape(-1)]
+        if not 1 <= len(self.fractions) <= RADIAL_MAX_FRACTIONS:
+            raise ValueError(f"1 .. {RADIAL_MAX_FRACTIONS} fractions")
+        if not all(math.isfinite(f) and 0.0 < f <= 1.0 for f in self.fractions):
+            raise ValueError("a fraction must be finite, > 0 and <= 1")
+        nf = len(self.fractions)
+        self.round, self.total = 0, None
+        self.prefix, self.below_w, self.below_n, self.target = [0] * nf, [0] * nf, [0] * nf, [0] * nf
+        self.last_w, self.last_n = [0] * nf, [0] * nf
+
+    @property
+    def done(self) -> bool:
+        return self.round >= self.ROUNDS or self.total == 0
+
+    def prefixes(self) -> list:
+        """The distinct prefixes of the fractions, in the order of their first appearance."""
+        out = []
+        for p in self.prefix:
+            if p not in out:
+                out.append(p)
+        return out
+
+    def advance(self, hist) -> None:
+        """hist (np, 256, 2) int64: {sum w, count} per digit, for prefixes() in that order."""
+        import math
+        pre = self.prefixes()
+        h = np.asarray(hist, dtype=np.int64).reshape(len(pre), 1 << RADIAL_DIGIT_BITS, 2).tolist()
+        if self.round == 0:
+            self.total = W = sum(d[0] for d in h[0])
+            if W == 0:
+                return
+            self.target = [min(W, max(1, int(math.ceil(f * float(W))))) for f in self.fractions]
+        for f in range(len(self.fractions)):
+            row = h[pre.index(self.prefix[f])]
+            d = 0
+            while d < (1 << RADIAL_DIGIT_BITS) - 1 and self.below_w[f] + row[d][0] < self.target[f]:
+                self.below_w[f] += row[d][0]
+                self.below_n[f] += row[d][1]
+                d += 1
+            self.prefix[f] = (self.prefix[f] << RADIAL_DIGIT_BITS) | d
+            self.last_w[f], self.last_n[f] = row[d][0], row[d][1]
+        self.round += 1
+
+    def result(self):
+        """(r2 float64, count int64, mass_units int64) per fraction; NaN, 0, 0 for a system without mass."""
+        nf = len(self.fractions)
+        if self.total == 0:
+            return np.full(nf, np.nan), np.zeros(nf, dtype=np.int64), np.zeros(nf, dtype=np.int64)
+        if self.round != self.ROUNDS:
+            raise ValueError("the selection has not run its eight rounds")
+        r2 = np.array(self.prefix, dtype=np.uint64).view(np.float64)
+        return (r2, np.array([a + b for a, b in zip(self.below_n, self.last_n)], dtype=np.int64),
+                np.array([a + b for a, b in zip(self.below_w, self.last_w)], dtype=np.int64))
+
+
+def lagrangian_from(fractions, r2, count, mass_units, exponent: int, centre) -> BhLagrangian:
+    """BhLagrangian of the selection's results."""
+    r2 = np.asarray(r2, dtype=np.float64).copy()
+    units = np.asarray(mass_units, dtype=np.int64).copy()
+    return BhLagrangian(np.asarray(fractions, dtype=np.float64).copy(), np.sqrt(r2), r2, np.asarray(count, dtype=np.int64).copy(),
+                        np.ldexp(units.astype(np.float64), -int(exponent)), units, int(exponent), tuple(float(x) for x in centre))
+
+
 @dataclass
 class BhGroups:
     """Friends-of-friends groups of the current state (groups): the label of every body, and a catalogue of the groups with at
@@ -571,6 +739,93 @@ class BarnesHutEngine:
         self._check(self._lib.bh_moment_map_deposit(self._h, _dptr(b), int(nx), int(ny), sch,
                                                     e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p), C.byref(nd)))
         return p.value, nd.value
+
+    # -- radial profiles and Lagrangian radii -----------------------------------------------------
+    def centre_of(self, centre) -> np.ndarray:
+        """(cx, cy) of "density" (density_centre(6)), "com" (energy().com) or a pair."""
+        if isinstance(centre, str):
+            if centre == "density":
+                return np.ascontiguousarray(self.density_centre(6), dtype=np.float64)
+            if centre == "com":
+                return np.array(self.energy().com, dtype=np.float64)
+            raise ValueError("centre must be 'density', 'com' or a pair (x, y)")
+        c = np.ascontiguousarray(centre, dtype=np.float64).reshape(-1)
+        if len(c) != 2:
+            raise ValueError("centre must be 'density', 'com' or a pair (x, y)")
+        return c
+
+    @staticmethod
+    def _pair_or_zero(v) -> np.ndarray:
+        u = np.zeros(2) if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if len(u) != 2:
+            raise ValueError("centre_velocity must be a pair (ux, uy)")
+        return u
+
+    def radial_profile(self, edges, centre="density", centre_velocity=None, raw: bool = False) -> BhRadialProfile:
+        """Surface density, rotation curve, radial and tangential dispersion and anisotropy of the current state in the bins
+        between `edges` (nb + 1 ascending radii, see radial_edges) about `centre` ("density", "com" or a pair), velocities
+        relative to centre_velocity (default 0); binned on the device in fixed point: the same bodies give the same bits in any
+        order.  Reads the state only; the run is not perturbed.  raw: also the int64 planes and their exponents."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(ed) - 1
+        ok = 1 <= nb <= RADIAL_MAX_BINS                            # (else the call refuses before it writes)
+        planes = np.zeros((6, nb + 2) if ok else (6, 3), dtype=np.int64)
+        e = np.zeros(5, dtype=np.int32)
+        self._check(self._lib.bh_radial_profile(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, nb,
+                                                planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        return radial_profile_from_planes(planes, e, ed, c, u, raw)
+
+    def radial_max(self, centre, centre_velocity=None) -> np.ndarray:
+        """max |m|, |m vr|, |m vt|, |m vr^2|, |m vt^2| over this context's bodies about the pair `centre` (zeros without bodies)."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        m = np.zeros(5)
+        self._check(self._lib.bh_radial_max(self._h, _dptr(c), _dptr(u), _dptr(m)))
+        return m
+
+    def radial_deposit(self, edges, centre, centre_velocity, exponents) -> int:
+        """Device pointer of the int64 planes 6 x (nb + 2): this context's bodies binned with the caller's exponents
+        (radial_exponents); valid until the next radial call."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+        if len(e) != 5:
+            raise ValueError("five exponents")
+        p = C.c_void_p()
+        self._check(self._lib.bh_radial_deposit(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, len(ed) - 1,
+                                                e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p)))
+        return p.value
+
+    def lagrangian_radii(self, fractions=(0.01, 0.1, 0.5, 0.9), centre="density") -> BhLagrangian:
+        """The radii about `centre` ("density", "com" or a pair) that enclose the mass fractions: for each the smallest body
+        radius inside which (ties included) at least that fraction of the fixed-point mass lies, selected on the device in
+        eight histogram passes -- no sort, no download of the state.  Reads the state only; the run is not perturbed."""
+        c = self.centre_of(centre)
+        f = np.ascontiguousarray(fractions, dtype=np.float64).reshape(-1)
+        nf = len(f)
+        k = max(nf, 1)
+        r2, cnt, mass, e = np.zeros(k), np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64), C.c_int32()
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.bh_lagrangian_radii(self._h, _dptr(c), _dptr(f) if nf else None, nf, _dptr(r2), cnt.ctypes.data_as(i64),
+                                                  mass.ctypes.data_as(i64), C.byref(e)))
+        return lagrangian_from(f, r2[:nf], cnt[:nf], mass[:nf], e.value, c)
+
+    def radial_select(self, centre, exponent: int, round: int, prefixes) -> int:
+        """Device pointer of one select round's histograms, len(prefixes) x 256 x {sum w, count} int64, over this context's
+        bodies (LagrangianSelect makes the decisions); valid until the next radial call."""
+        c = self.centre_of(centre)
+        pre = np.array([int(p) for p in prefixes], dtype=np.uint64)
+        p = C.c_void_p()
+        self._check(self._lib.bh_radial_select(self._h, _dptr(c), int(exponent), int(round),
+                                               pre.ctypes.data_as(C.POINTER(C.c_uint64)) if len(pre) else None, len(pre), C.byref(p)))
+        return p.value
+
+    def radial_times(self):
+        """(max_ms, main_ms, rounds_ms (8,)) of the last radial call: HIP events around the first pass, around the deposit or
+        the select rounds together, and around every select round."""
+        a, b, r = C.c_double(), C.c_double(), np.zeros(8)
+        self._check(self._lib.bh_radial_times(self._h, C.byref(a), C.byref(b), _dptr(r)))
+        return a.value, b.value, r
 
     # -- neighbours -----------------------------------------------------------------------------
     def _query_points(self, points):

@@ -23,7 +23,7 @@ import time
 
 import numpy as np
 
-from .engine import BarnesHutEngine, BhConfig, Precision, sample_targets
+from .engine import BarnesHutEngine, BhConfig, Precision, radial_edges, sample_targets
 from .textio import loadSimulationDataFromText
 
 # project.cu:27-35, 60-61
@@ -77,7 +77,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      field_file: str | None = None, field_grid=None, field_box=None, softening: float = 0.0,
                      integrator: str = "euler", density_file: str | None = None, density_grid=None, density_box=None,
                      density_scheme: str = "cic", neighbours_file: str | None = None, neighbours_k: int = 6,
-                     groups_file: str | None = None, linking_length: float | None = None, groups_min: int = 2):
+                     groups_file: str | None = None, linking_length: float | None = None, groups_min: int = 2,
+                     profile_file: str | None = None, profile_bins: int | None = None, profile_range=None,
+                     profile_spacing: str = "log", profile_centre="density", lagrange_file: str | None = None,
+                     lagrange_fractions=(0.01, 0.1, 0.5, 0.9), lagrange_every: int = 0, lagrange_centre="density"):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -107,6 +110,14 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     (BarnesHutEngine.groups(linking_length, groups_min)): the line `# id,count,mass,x,y,vx,vy`, then one row per group with at
     least groups_min bodies (%.17g), the largest first: its label (the smallest body index in it), its member count, its mass,
     its centre of mass and its bulk velocity.  Not part of gpu_parallel_duration_us.
+    profile_file: after the last step, also write the radial profile of the final state (BarnesHutEngine.radial_profile) in
+    profile_bins bins, profile_spacing "log" or "linear", over profile_range = (rmin, rmax) about profile_centre ("density",
+    "com" or a pair); range None: out to just beyond the farthest body, from 0 (linear) or a thousandth of that (log): the line
+    `# r_lo,r_hi,count,sigma,vr,vt,sigma_r,sigma_t`, then one row per bin (%.17g; nan in a bin without mass).  Not part of
+    gpu_parallel_duration_us.
+    lagrange_file: also write the Lagrangian radii of the state (BarnesHutEngine.lagrangian_radii(lagrange_fractions,
+    lagrange_centre)) with the cadence rules of energy_file (lagrange_every), one line each: `step,t,cx,cy,r_f1,...` (%.17g).
+    Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -116,6 +127,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("groups_file needs a linking_length")
     if integrator not in ("euler", "kdk"):
         raise ValueError("integrator must be 'euler' or 'kdk'")
+    if (profile_file is None) != (profile_bins is None):
+        raise ValueError("profile_file and profile_bins go together")
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -140,6 +153,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         if force_error_file is not None:
             ferr = open(os.path.join(out_dir, force_error_file) if not os.path.isabs(force_error_file) else force_error_file, "w")
             ferr_targets = sample_targets(n, force_error_sample)
+        lagrange = None
+        if lagrange_file is not None:
+            lagrange = open(os.path.join(out_dir, lagrange_file) if not os.path.isabs(lagrange_file) else lagrange_file, "w")
         done = 0
         # (file, steps between its lines, what writes a line)
         samplers = []
@@ -154,10 +170,16 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             ferr.write(",".join([str(done), "%.17g" % (done * delta_t), str(r.n)]
                                 + ["%.17g" % v for v in (r.median, r.p90, r.p99, r.p999, r.max)] + [str(r.worst)]) + "\n")
 
+        def sample_lagrange():
+            lr = eng.lagrangian_radii(lagrange_fractions, lagrange_centre)
+            lagrange.write(",".join([str(done)] + ["%.17g" % v for v in (done * delta_t, *lr.centre, *lr.r)]) + "\n")
+
         if energy is not None:
             samplers.append((energy_every, sample_energy))
         if ferr is not None:
             samplers.append((force_error_every, sample_force_error))
+        if lagrange is not None:
+            samplers.append((lagrange_every, sample_lagrange))
 
         advance_engine = eng.step if integrator == "euler" else eng.step_kdk
 
@@ -235,9 +257,16 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 f.write("# id,count,mass,x,y,vx,vy\n")
                 f.write("".join("%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % (i, k, m, x, y, vx, vy)
                                 for i, k, m, (x, y), (vx, vy) in zip(g.id, g.count, g.mass, g.com, g.velocity)))
+        if profile_file is not None:
+            centre = eng.centre_of(profile_centre)
+            prof = eng.radial_profile(profile_edges(profile_bins, profile_range, profile_spacing, pos, centre), centre)
+            cols = (prof.edges[:-1], prof.edges[1:], prof.count, prof.sigma, prof.vr, prof.vt, prof.sigma_r, prof.sigma_t)
+            with open(os.path.join(out_dir, profile_file) if not os.path.isabs(profile_file) else profile_file, "w") as f:
+                f.write("# r_lo,r_hi,count,sigma,vr,vt,sigma_r,sigma_t\n")
+                f.write("".join("%.17g,%.17g,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(*cols)))
         if traj is not None:
             traj.close()
-        for f in (energy, ferr):
+        for f in (energy, ferr, lagrange):
             if f is not None:
                 f.close()
     return pos, vel, gpu_parallel_us
@@ -258,6 +287,32 @@ def field_grid_points(grid, box, positions) -> np.ndarray:
     xs = x0 + (np.arange(nx) + 0.5) * ((x1 - x0) / nx)
     ys = y0 + (np.arange(ny) + 0.5) * ((y1 - y0) / ny)
     return np.stack([np.tile(xs, ny), np.repeat(ys, nx)], axis=1)
+
+
+def profile_edges(bins: int, rng, spacing: str, positions, centre) -> np.ndarray:
+    """The bins + 1 edges of --profile-file over rng = (rmin, rmax); None: out to just beyond the farthest body from `centre`,
+    from 0 ("linear") or a thousandth of that ("log")."""
+    if rng is None:
+        p = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+        if len(p) == 0:
+            raise ValueError("no bodies: give the profile range")
+        r_max = float(np.nextafter(np.sqrt(((p - np.asarray(centre, dtype=np.float64)) ** 2).sum(axis=1).max()), np.inf))
+        rng = (0.0 if spacing == "linear" else 1e-3 * r_max, r_max)
+    return radial_edges(float(rng[0]), float(rng[1]), int(bins), spacing)
+
+
+def _centre_arg(ap, flag: str, words):
+    """"density", "com" or two numbers."""
+    if words is None:
+        return "density"
+    if len(words) == 1 and words[0] in ("density", "com"):
+        return words[0]
+    try:
+        if len(words) == 2:
+            return (float(words[0]), float(words[1]))
+    except ValueError:
+        pass
+    ap.error(f"{flag}: density, com, or X Y")
 
 
 def _write_frame(f, t: float, pos) -> None:
@@ -315,6 +370,23 @@ def _parse(argv):
     ap.add_argument("--linking-length", type=float, default=None, metavar="B",
                     help="bodies at most B apart are friends; a group is a connected component of that relation")
     ap.add_argument("--groups-min", type=int, default=None, metavar="M", help="smallest group of --groups-file (default 2)")
+    ap.add_argument("--profile-file", default=None, metavar="PATH",
+                    help="after the last step, also write r_lo,r_hi,count,sigma,vr,vt,sigma_r,sigma_t (surface density, mean radial "
+                         "and tangential velocity and their dispersions) of the --profile-bins radial bins about --profile-centre")
+    ap.add_argument("--profile-bins", type=int, default=None, metavar="NB", help="bins of --profile-file (1 .. 4096)")
+    ap.add_argument("--profile-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
+                    help="what the bins cover (default: out to the farthest body, from 0 (linear) or a thousandth of that (log))")
+    ap.add_argument("--profile-spacing", choices=["log", "linear"], default="log", help="spacing of the bin edges")
+    ap.add_argument("--profile-centre", nargs="+", default=None, metavar="C",
+                    help="density (the density centre, default), com (the centre of mass) or X Y")
+    ap.add_argument("--lagrange-file", default=None, metavar="PATH",
+                    help="also write step,t,cx,cy,r_f1,... (the centre and the radii that enclose the --lagrange-fractions of the "
+                         "mass) before the first step, every --lagrange-every steps and after the last")
+    ap.add_argument("--lagrange-fractions", type=float, nargs="+", default=None, metavar="F",
+                    help="mass fractions in (0, 1] (default 0.01 0.1 0.5 0.9; at most 32)")
+    ap.add_argument("--lagrange-every", type=int, default=0, metavar="K",
+                    help="steps between two lines of --lagrange-file (0: first and last state only)")
+    ap.add_argument("--lagrange-centre", nargs="+", default=None, metavar="C", help="density (default), com or X Y")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -346,6 +418,22 @@ def _parse(argv):
         ap.error("--groups-file and --linking-length go together")
     if a.groups_min is not None and a.groups_file is None:
         ap.error("--groups-min needs --groups-file")
+    if (a.profile_file is None) != (a.profile_bins is None):
+        ap.error("--profile-file and --profile-bins go together")
+    if a.profile_file is None and (a.profile_range is not None or a.profile_centre is not None):
+        ap.error("--profile-range and --profile-centre need --profile-file")
+    if a.profile_bins is not None and not 1 <= a.profile_bins <= 4096:
+        ap.error("--profile-bins: 1 .. 4096")
+    if a.profile_range is not None and not (0.0 <= a.profile_range[0] < a.profile_range[1] < float("inf")):
+        ap.error("--profile-range: 0 <= RMIN < RMAX, finite")
+    if a.profile_range is not None and a.profile_spacing == "log" and a.profile_range[0] <= 0.0:
+        ap.error("--profile-range: log spacing needs RMIN > 0")
+    if a.lagrange_file is None and (a.lagrange_fractions is not None or a.lagrange_centre is not None or a.lagrange_every):
+        ap.error("--lagrange-fractions, --lagrange-every and --lagrange-centre need --lagrange-file")
+    if a.lagrange_fractions is not None and (len(a.lagrange_fractions) > 32 or not all(0.0 < f <= 1.0 for f in a.lagrange_fractions)):
+        ap.error("--lagrange-fractions: at most 32, each in (0, 1]")
+    a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
+    a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     if a.groups_min is not None and a.groups_min < 1:
         ap.error("--groups-min: at least 1")
     if a.linking_length is not None and not (a.linking_length >= 0.0 and a.linking_length < float("inf")):
@@ -414,7 +502,11 @@ def main(argv=None) -> int:
         softening=a.softening or 0.0, integrator=a.integrator, density_file=a.density_file, density_grid=a.density_grid,
         density_box=a.density_box, density_scheme=a.density_scheme, neighbours_file=a.neighbours_file,
         neighbours_k=6 if a.neighbours_k is None else a.neighbours_k, groups_file=a.groups_file,
-        linking_length=a.linking_length, groups_min=2 if a.groups_min is None else a.groups_min)
+        linking_length=a.linking_length, groups_min=2 if a.groups_min is None else a.groups_min,
+        profile_file=a.profile_file, profile_bins=a.profile_bins, profile_range=a.profile_range,
+        profile_spacing=a.profile_spacing, profile_centre=a.profile_centre, lagrange_file=a.lagrange_file,
+        lagrange_fractions=(0.01, 0.1, 0.5, 0.9) if a.lagrange_fractions is None else tuple(a.lagrange_fractions),
+        lagrange_every=a.lagrange_every, lagrange_centre=a.lagrange_centre)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

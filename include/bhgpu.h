@@ -439,6 +439,67 @@ int bh_moment_map_max(bh_ctx *ctx, double maxabs[4]);
 int bh_moment_map_deposit(bh_ctx *ctx, const double box[4], int32_t nx, int32_t ny, int32_t scheme,
                           const int32_t exponents[4], void **planes_dev, int64_t *n_deposited);
 
+/* --- radial profiles and Lagrangian radii: how the mass is arranged about a centre -----------------------------------------
+ * The radial counterpart of the moment maps, on the device, so that a distributed run can profile a system no rank holds.
+ * centre = {cx, cy}; centre_vel = {ucx, ucy} (NULL: 0).  Per body of the CURRENT state, in fp64 in the written order with
+ * nothing fused (an fp32 state is widened first, exactly):
+ *     dx = x - cx;  dy = y - cy;  r2 = dx * dx + dy * dy
+ *     ux = vx - ucx;  uy = vy - ucy;  a = dx * ux + dy * uy;  b = dx * uy - dy * ux
+ *     r2 >= 2^-1022:  r = sqrt(r2);  vr = a / r;  vt = b / r        r2 < 2^-1022 (zero or subnormal): vr = vt = 0
+ *     q0 = m   q1 = m * vr   q2 = m * vt   q3 = m * (vr * vr)   q4 = m * (vt * vt)
+ * Bins.  edges[nb + 1], 1 <= nb <= BH_RADIAL_MAX_BINS, finite, edges[0] >= 0, strictly ascending, and so are their squares
+ *   e2[k] = edges[k] * edges[k] (formed once in fp64 on the host).  nb + 2 slots, decided on r2 alone: slot 0: r2 < e2[0];
+ *   slot k + 1: e2[k] <= r2 < e2[k + 1]; slot nb + 1: r2 >= e2[nb].  A body exactly on an edge belongs to the bin above it.
+ * Planes.  planes[6][nb + 2], plane-major.  Planes 0-4 are the sums of q0-q4 in the fixed point of the moment maps: a first
+ *   pass takes max |q_p| over the bodies, E_p is its frexp exponent, L = ceil(log2(max(n, 1))) for the n bodies of the WHOLE
+ *   system, the plane's exponent is 62 - E_p - L (0 when the maximum is 0), a contribution is (int64) rint(ldexp(q_p,
+ *   exponent)), added with 64-bit integer atomics.  Plane 5 is the body count.  value = planes * 2^-exponent.  The planes are
+ *   a pure function of the set of bodies -- no order, launch shape or number of contexts enters -- and plane 0 summed over the
+ *   slots is the sum of w_i = rint(ldexp(m_i, exponent 0)) exactly.
+ * bh_radial_profile: both passes and the download.
+ * bh_radial_max: the first pass alone, maxabs[p] = max |q_p| over this context's bodies (0 without bodies).
+ * bh_radial_deposit: the second pass alone with the caller's exponents (a distributed profile: the MAX of the ranks' maxima
+ *   and the SUM of their body counts give every rank the same exponents), the planes left on the device: *planes_dev points
+ *   at 6 * (nb + 2) int64, valid until the next radial call or bh_destroy.  Exponents too large for this context's own
+ *   maxima and body count are refused.
+ * Lagrangian radii.  w_i = rint(ldexp(m_i, e0)), e0 the exponent of plane 0, W = sum w_i; every mass must be >= 0.  For a
+ *   fraction f, finite, 0 < f <= 1:  T_f = min(W, max(1, (int64) ceil(f * (double) W)));  R2_f = the smallest r2_i such that
+ *   the sum of w_j over r2_j <= r2_i is at least T_f.  r2[f] = R2_f, count[f] = the bodies with r2_i <= R2_f, mass[f] = the
+ *   sum of their w_i (bodies tied in r2 are all inside: no index order enters).  Up to BH_RADIAL_MAX_FRACTIONS fractions, in
+ *   any order, repeats allowed, results in the caller's order.  W = 0: r2 = NaN, count = mass = 0.  The velocities are not read.
+ * bh_lagrangian_radii: the first pass, then a radix select over the bit pattern of r2: 8 rounds of BH_RADIAL_DIGIT_BITS = 8
+ *   bits from the top, one pass over the bodies each; between two rounds every fraction picks, on the host, the digit at
+ *   which its running sum first reaches T_f.  *exponent = e0.
+ * bh_radial_select: one round alone with the caller's e0: the primitive of a distributed selection.  round 0 .. 7; prefixes[np],
+ *   1 <= np <= BH_RADIAL_MAX_FRACTIONS, distinct: the 8 * round bits already decided above this round's digit (round 0: the
+ *   one prefix 0).  *hist_dev points at np * 256 * 2 int64, hist[k][digit] = {sum w, count} over this context's bodies whose
+ *   higher bits equal prefixes[k], valid until the next radial call or bh_destroy.  Summed over the ranks the histograms are
+ *   those of the whole system.  An exponent too large for this context's masses and body count is refused.
+ * bh_radial_times: HIP-event times of the last of these calls: the first pass; the deposit, or the select rounds together;
+ *   rounds_ms[8] (may be NULL): every round of the last bh_lagrangian_radii / bh_radial_select (0 for a round not run).
+ * Valid any time after bh_upload / bh_initialize / bh_migrate_unpack, in every precision, in LET mode too (the context's own
+ * bodies); they read the state arrays bh_download reads, build no tree and change nothing a step reads: the steps around
+ * them run bit for bit as they would have.  They wait for the stream.
+ * Errors: BH_ERR_ARG for a null pointer (centre_vel and rounds_ms excepted), a centre or centre velocity that is not finite,
+ *   nb < 1 or > BH_RADIAL_MAX_BINS, edges that are not finite, negative or not strictly ascending (they or their squares), nf or
+ *   np < 1 or > BH_RADIAL_MAX_FRACTIONS, a fraction that is not finite or outside (0, 1], a round outside 0 .. 7, prefixes that
+ *   repeat or have more digits than the round, and -- with a message that says so -- a body whose position, velocity (not the
+ *   radii) or mass is not finite or whose r2 or moment overflows fp64, and for the radii a negative mass.  BH_ERR_STATE before
+ *   any upload. */
+#define BH_RADIAL_MAX_BINS 4096
+#define BH_RADIAL_MAX_FRACTIONS 32
+#define BH_RADIAL_DIGIT_BITS 8
+int bh_radial_profile(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *edges, int32_t nb,
+                      int64_t *planes, int32_t exponents[5]);
+int bh_radial_max(bh_ctx *ctx, const double centre[2], const double centre_vel[2], double maxabs[5]);
+int bh_radial_deposit(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *edges, int32_t nb,
+                      const int32_t exponents[5], void **planes_dev);
+int bh_lagrangian_radii(bh_ctx *ctx, const double centre[2], const double *fractions, int32_t nf, double *r2, int64_t *count,
+                        int64_t *mass, int32_t *exponent);
+int bh_radial_select(bh_ctx *ctx, const double centre[2], int32_t exponent, int32_t round, const uint64_t *prefixes, int32_t np,
+                     void **hist_dev);
+int bh_radial_times(bh_ctx *ctx, double *max_ms, double *main_ms, double rounds_ms[8]);
+
 /* --- neighbours: which bodies are next to a body or a point, and how far away ------------------------------------------
  * Queries.  points == NULL: the queries are the n bodies in caller order and n_points must be n; body i is left out of its
  *   own answer by index -- another body at the same place is not: it is a neighbour at d2 = 0.  Otherwise points[n_points][2]
