@@ -133,6 +133,8 @@ SIGNATURES = {
     "bh_neighbours": (C.c_int,[_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
     "bh_count_within": (C.c_int, [_ctx, _dp, C.c_int64, C.c_double, C.POINTER(C.c_uint32)]),
     "bh_neighbours_times": (C.c_int, [_ctx, _dp, _dp]),
+    "bh_pair_counts": (C.c_int, [_ctx, _dp, C.c_int64, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "bh_pair_counts_times": (C.c_int, [_ctx, _dp, _dp]),
     "bh_groups": (C.c_int, [_ctx, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                             C.POINTER(C.c_uint64)]),
     "bh_groups_catalogue": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),

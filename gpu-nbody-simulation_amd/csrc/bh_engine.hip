@@ -27,6 +27,7 @@
 #include "bh_moments.hpp"
 #include "bh_radial.hpp"
 #include "bh_neighbours.hpp"
+#include "bh_pairs.hpp"
 #include "bh_groups.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
@@ -187,6 +188,10 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     int64_t *nb_idx = nullptr;
     hipEvent_t nb_ev[4] = {nullptr, nullptr, nullptr, nullptr};    // around the build and around a launch's sort and search
     double nb_build_ms = 0.0, nb_query_ms = 0.0;                    // of the last call (bh_neighbours_times)
+    // pair counts (bh_pairs.hpp), allocated on first use: the squared edges, then the int64 histogram and the evals word
+    double *pair_e2 = nullptr;
+    unsigned long long *pair_hist = nullptr;
+    double pair_build_ms = 0.0, pair_query_ms = 0.0;                // of the last call (bh_pair_counts_times)
     // friends-of-friends groups (bh_groups.hpp), allocated on first use: one block for up to fof_cap bodies beside the
     // neighbour structure's, and the catalogue of the last bh_groups call on the host (no record of bh_run_state.hpp: it is
     // that call's result, whatever the run does afterwards)
@@ -2483,6 +2488,88 @@ int bh_neighbours_times(bh_ctx *c, double *build_ms, double *query_ms)
     if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_neighbours_times: null argument");
     *build_ms = c->nb_build_ms;
     *query_ms = c->nb_query_ms;
+    return BH_OK;
+}
+
+// ---- pair counts (bh_pairs.hpp) on the structure of the neighbour queries.  They read pos as it lies in memory and write buffers
+// of their own: a step before and after runs bit for bit as it would have.  Allowed in LET mode and with world > 1: the
+// bodies are this context's own.
+int bh_pair_counts(bh_ctx *c, const double *points, int64_t n_points, const double *edges, int32_t nb, int64_t *counts, int64_t *evals)
+{
+    if (!c) return BH_ERR_ARG;
+    if (nb < 1 || nb > kPairMaxBins) return fail(c, BH_ERR_ARG, "bh_pair_counts: 1 .. BH_PAIR_MAX_BINS = 1024 bins");
+    if (!edges || !counts) return fail(c, BH_ERR_ARG, "bh_pair_counts: null edges or counts");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_pair_counts: n_points < 0");
+    std::vector<double> e2((size_t)nb + 1);
+    for (int32_t k = 0; k <= nb; ++k) {
+        e2[(size_t)k] = edges[k] * edges[k];
+        if (!std::isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1])))
+            return fail(c, BH_ERR_ARG, "bh_pair_counts: the edges must be finite, >= 0 and strictly ascending");
+        if (!std::isfinite(e2[(size_t)k]) || (k > 0 && !(e2[(size_t)k] > e2[(size_t)k - 1])))
+            return fail(c, BH_ERR_ARG, "bh_pair_counts: the squared edges must be finite and strictly ascending");
+    }
+    if (int rc = need_upload(c, "bh_pair_counts before bh_upload/bh_initialize")) return rc;
+    const int64_t n = c->n;
+    if (!points && n_points != n) return fail(c, BH_ERR_ARG, "bh_pair_counts: without points, n_points must be the number of bodies");
+    for (int64_t i = 0; points && i < 2 * n_points; ++i)
+        if (!std::isfinite(points[i]))
+            return fail(c, BH_ERR_ARG, "bh_pair_counts: point " + std::to_string(i / 2) + " has a non-finite coordinate");
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_pair_counts: more than 2^24 bodies (their indices share a key word)");
+    std::fill(counts, counts + nb + 2, (int64_t)0);
+    if (evals) *evals = 0;
+    c->pair_build_ms = c->pair_query_ms = 0.0;
+    if (n == 0 || n_points == 0) return BH_OK;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, points ? std::min(n_points, kNbChunk) : 0, 0)) return rc;
+    if (!c->pair_e2) {
+        if (int rc = dev_alloc(c, &c->pair_e2, (size_t)kPairMaxBins + 1)) return rc;
+        if (int rc = dev_alloc(c, &c->pair_hist, (size_t)kPairMaxBins + 3)) return rc;
+    }
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_pair_counts", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const size_t words = (size_t)nb + 3;                       // the bins, then the evals word
+    BH_HIP(c, hipMemcpyAsync(c->pair_e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    BH_HIP(c, hipMemsetAsync(c->pair_hist, 0, words * sizeof(unsigned long long), st));
+    const size_t lds = (2 * (size_t)nb + 4) * sizeof(unsigned long long);
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        BH_HIP(c, hipEventRecord(c->nb_ev[2], st));
+        if (points) {
+            BH_HIP(c, hipMemcpyAsync(c->nb_points, points + 2 * t0, (size_t)rows * sizeof(double2), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(field_keys_kernel, dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_points, rows, c->nb_box,
+                               c->nb_pkeys[0]);
+            uint32_t *const order[2] = {c->nb_order, c->nb_order};
+            enqueue_lsd_passes<kFieldSortItems>(st, c->nb_pkeys, order, c->nb_radix, c->nb_rowsum, rows, kFieldKeyBits, true);
+        }
+        dispatch([&](auto pts) {
+            hipLaunchKernelGGL((pair_count_kernel<decltype(pts)::value>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), lds, st,
+                               c->nb_spos, c->nb_boxes, c->nb_off, levels, (int32_t)n, c->nb_points, c->nb_order, t0, rows, c->pair_e2, nb,
+                               c->pair_hist, c->pair_hist + nb + 2);
+        }, points != nullptr);
+        BH_HIP(c, hipGetLastError());
+        BH_HIP(c, hipEventRecord(c->nb_ev[3], st));
+        BH_HIP(c, hipStreamSynchronize(st));                    // (the next chunk overwrites the points; the events are read here)
+        float ms = 0.f;
+        BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[2], c->nb_ev[3]));
+        c->pair_query_ms += (double)ms;
+    }
+    std::vector<unsigned long long> got(words);
+    BH_HIP(c, hipMemcpyAsync(got.data(), c->pair_hist, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    for (int32_t k = 0; k < nb + 2; ++k) counts[k] = (int64_t)got[(size_t)k];
+    if (evals) *evals = (int64_t)got[(size_t)nb + 2];
+    float ms = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
+    c->pair_build_ms = (double)ms;
+    return BH_OK;
+}
+
+int bh_pair_counts_times(bh_ctx *c, double *build_ms, double *query_ms)
+{
+    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_pair_counts_times: null argument");
+    *build_ms = c->pair_build_ms;
+    *query_ms = c->pair_query_ms;
     return BH_OK;
 }
 

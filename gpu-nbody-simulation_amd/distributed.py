@@ -287,6 +287,18 @@ def combine_energy_sums(rows):
     return BhEnergy(kinetic, potential, kinetic + potential, (q[3], q[4]), q[5], com, q[0], n)
 
 
+def pair_ring_schedule(world: int):
+    """The rounds of LetStepper.pair_counts: rounds k = 1 .. world // 2, each a list over the ranks r of
+    (send_to, receive_from, counts) = ((r + k) % world, (r - k) % world, whether r adds the cross counts of what it receives
+    against its own bodies).  Everybody counts, except in the last round of an even world, where rank r and rank r + world / 2
+    receive each other's bodies and only r < world / 2 counts: every unordered pair of ranks is counted exactly once."""
+    world = int(world)
+    if world < 1:
+        raise ValueError("world must be at least 1")
+    return [[((r + k) % world, (r - k) % world, not (2 * k == world and r >= world // 2)) for r in range(world)]
+            for k in range(1, world // 2 + 1)]
+
+
 def init_process_group_from_env(backend: str | None = None):
     """RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run exports them."""
     rank = int(os.environ.get("RANK", "0"))
@@ -696,6 +708,74 @@ class LetStepper:
                                                              "(non-finite, or a negative mass)")
             sel.advance(t[:words].numpy().reshape(len(pre), 256, 2))
         return lagrangian_from(sel.fractions, *sel.result(), e0, c)
+
+    def pair_counts(self, edges):
+        """BhPairCounts of the WHOLE system (engine.pair_counts in auto mode), the same bits on every rank and the same bits
+        as one engine's counts of the same bodies.  Each rank counts the pairs among its own bodies; in round k of
+        pair_ring_schedule rank r sends its fp64 positions to rank (r + k) mod W, receives those of rank (r - k) mod W and
+        adds their cross counts against its own bodies (lengths first, then ONE all_to_all_single with a single non-empty
+        split), so that no rank holds more than its own bodies and one other rank's positions; one all_reduce(SUM) of the
+        int64 counts ends it.  Collective: the same edges on every rank (checked: ValueError on every rank if not)."""
+        import numpy as np
+        from .engine import PAIR_MAX_BINS, pair_counts_from
+        W, r = self.world, self.rank
+        many = dist.is_initialized() and W > 1
+        on_dev = many and dist.get_backend() != "gloo"            # RCCL takes device tensors, gloo host tensors
+        dev = self.device if on_dev else "cpu"
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(ed) - 1
+
+        def agree(values) -> bool:
+            a = torch.tensor([float(v) for v in values], dtype=torch.float64, device=dev)
+            hi = torch.cat([a, -a])
+            if many:
+                dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            return bool(torch.equal(hi[:a.numel()].cpu(), a.cpu()) and torch.equal(hi[a.numel():].cpu(), -a.cpu()))   # (a NaN fails too)
+
+        same = agree([nb])
+        same = torch.tensor([0 if same and agree(ed) else 1], dtype=torch.int64, device=dev)
+        if many:
+            dist.all_reduce(same, op=dist.ReduceOp.MAX)
+        if int(same.item()):
+            raise ValueError(f"pair_counts: the ranks disagree on the edges (rank {r} has {ed.tolist()})")
+        ok = 1 <= nb <= PAIR_MAX_BINS
+        total = np.zeros((nb + 2 if ok else 3) + 2, dtype=np.int64)      # the counts, the body count, a rank's error flag
+        bad = None
+        mine = None
+
+        def add(points=None):
+            nonlocal bad
+            if bad is None:
+                try:
+                    total[:-2] += self.eng.pair_counts_raw(ed, points)[0]
+                except Exception as err:                          # noqa: BLE001 -- re-raised below, after the collectives
+                    bad = err
+
+        add()
+        for rnd in pair_ring_schedule(W):
+            to, frm, counts = rnd[r]
+            if mine is None:
+                mine = torch.from_numpy(np.ascontiguousarray(self.eng.download()[0], dtype=np.float64).reshape(-1)).to(dev)
+            lens = torch.zeros(W, dtype=torch.int64, device=dev)
+            lens[to] = mine.numel()
+            got = torch.empty(W, dtype=torch.int64, device=dev)
+            dist.all_to_all_single(got, lens)
+            ins, outs = [0] * W, [0] * W
+            ins[to], outs[frm] = mine.numel(), int(got[frm].item())
+            theirs = torch.empty(outs[frm], dtype=torch.float64, device=dev)
+            dist.all_to_all_single(theirs, mine, outs, ins)
+            if counts and theirs.numel():
+                add(theirs.cpu().numpy().reshape(-1, 2))
+            del theirs
+        total[-2] = int(self.eng.n)
+        total[-1] = 0 if bad is None else 1
+        t = torch.from_numpy(total).to(dev)
+        if many:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        total = t.cpu().numpy()
+        if bad is not None or int(total[-1]) != 0:
+            raise bad if bad is not None else ValueError("pair_counts: another rank's count failed")
+        return pair_counts_from(total[:-2], ed, int(total[-2]))
 
     @property
     def ids(self):

@@ -377,6 +377,50 @@ def groups_from_sums(label, n_groups: int, linking_length: float, min_members: i
                     sums if raw else None, exponents.copy() if raw else None, stats)
 
 
+PAIR_MAX_BINS = 1024                    # BH_PAIR_MAX_BINS
+
+
+@dataclass
+class BhPairCounts:
+    """Pair-separation counts of the current state on the nb bins between edges (pair_counts): auto mode counts every
+    unordered pair of bodies once, cross mode every (point, body) combination.  A pair belongs to bin k when
+    edges[k]^2 < d2 <= edges[k + 1]^2 (the upper edge inclusive), d2 = dx * dx + dy * dy in fp64."""
+    edges: np.ndarray            # (nb + 1,)
+    counts: np.ndarray           # (nb,) int64
+    below: int                   # d2 <= edges[0]^2
+    beyond: int                  # d2 > edges[nb]^2
+    total: int                   # below + counts.sum() + beyond: n (n - 1) / 2, or n_points * n
+    n_bodies: int
+    n_points: int | None         # None in auto mode
+    evals: int | None            # the distances the call computed (with_evals), a measure of the work
+    cumulative: np.ndarray       # (nb + 1,) int64: the pairs with d2 <= edges[k]^2 at every edge
+
+
+def pair_counts_from(raw, edges, n_bodies: int, n_points=None, evals=None) -> BhPairCounts:
+    """BhPairCounts from the int64[nb + 2] of bh_pair_counts (of one context, or the sum of many)."""
+    raw = np.asarray(raw, dtype=np.int64).reshape(-1)
+    ed = np.asarray(edges, dtype=np.float64).reshape(-1).copy()
+    if len(raw) != len(ed) + 1:
+        raise ValueError("nb + 2 counts for nb + 1 edges")
+    return BhPairCounts(ed, raw[1:-1].copy(), int(raw[0]), int(raw[-1]), int(raw.sum()), int(n_bodies),
+                        None if n_points is None else int(n_points), None if evals is None else int(evals), np.cumsum(raw[:-1]))
+
+
+def correlation_from(dd, dr, n: int, n_r: int) -> np.ndarray:
+    """The Davis-Peebles estimate xi_k = (n_r / (n - 1)) * (2 * dd_k / dr_k) - 1 of the two-point correlation from the
+    unordered auto counts dd of n bodies and the cross counts dr of n_r random points against them; NaN where dr_k = 0."""
+    dd = np.asarray(dd, dtype=np.float64)
+    dr = np.asarray(dr, dtype=np.float64)
+    if dd.shape != dr.shape:
+        raise ValueError("dd and dr must have the same shape")
+    if n < 2 or n_r < 1:
+        raise ValueError("the estimator needs n >= 2 bodies and n_r >= 1 random points")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        xi = (n_r / (n - 1)) * (2.0 * dd / dr) - 1.0
+    xi[dr == 0.0] = np.nan
+    return xi
+
+
 NEIGHBOURS_MAX_K = 32                   # BH_NEIGHBOURS_MAX_K
 
 
@@ -863,6 +907,39 @@ class BarnesHutEngine:
         b, q = C.c_double(), C.c_double()
         self._check(self._lib.bh_neighbours_times(self._h, C.byref(b), C.byref(q)))
         return b.value, q.value
+
+    # -- pair counts ----------------------------------------------------------------------------
+    def pair_counts_raw(self, edges, points=None):
+        """(int64[nb + 2] = below, the nb bins, beyond; evals) of bh_pair_counts over this context's bodies."""
+        p, q, pp = self._query_points(points)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(ed) - 1
+        raw = np.zeros(nb + 2 if 1 <= nb <= PAIR_MAX_BINS else 3, dtype=np.int64)  # (else the call refuses before it writes)
+        ev = C.c_int64()
+        self._check(self._lib.bh_pair_counts(self._h, pp, q, _dptr(ed) if len(ed) else None, nb,
+                                             raw.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ev)))
+        return raw, ev.value
+
+    def pair_counts(self, edges, points=None, with_evals: bool = False) -> BhPairCounts:
+        """The pairs of bodies (points None: every unordered pair once) or of `points` (q, 2) and bodies (every combination)
+        per separation bin between `edges` (nb + 1 ascending radii, see radial_edges), counted on the device in one
+        traversal: the brute-force histogram bit for bit.  Reads the state only; the run is not perturbed."""
+        raw, ev = self.pair_counts_raw(edges, points)
+        return pair_counts_from(raw, edges, self.n, None if points is None else len(np.asarray(points).reshape(-1, 2)),
+                                ev if with_evals else None)
+
+    def pair_counts_times(self):
+        """(build_ms, query_ms) of the last pair_counts(): HIP events around the structure's build and the traversals."""
+        b, q = C.c_double(), C.c_double()
+        self._check(self._lib.bh_pair_counts_times(self._h, C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    def correlation(self, edges, randoms):
+        """(xi, dd, dr): the Davis-Peebles two-point correlation of the current state in the bins between `edges` from the
+        auto counts dd and the cross counts dr of the random points `randoms` (n_r, 2) -- see correlation_from."""
+        dd = self.pair_counts(edges)
+        dr = self.pair_counts(edges, randoms)
+        return correlation_from(dd.counts, dr.counts, self.n, dr.n_points), dd, dr
 
     # -- groups ---------------------------------------------------------------------------------
     def groups(self, linking_length: float, min_members: int = 2, raw: bool = False, with_stats: bool = False) -> BhGroups:

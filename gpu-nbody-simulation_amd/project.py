@@ -80,7 +80,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      groups_file: str | None = None, linking_length: float | None = None, groups_min: int = 2,
                      profile_file: str | None = None, profile_bins: int | None = None, profile_range=None,
                      profile_spacing: str = "log", profile_centre="density", lagrange_file: str | None = None,
-                     lagrange_fractions=(0.01, 0.1, 0.5, 0.9), lagrange_every: int = 0, lagrange_centre="density"):
+                     lagrange_fractions=(0.01, 0.1, 0.5, 0.9), lagrange_every: int = 0, lagrange_centre="density",
+                     pairs_file: str | None = None, pairs_bins: int | None = None, pairs_range=None, pairs_spacing: str = "log",
+                     pairs_randoms: int | None = None, pairs_seed: int = 0):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -118,6 +120,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     lagrange_file: also write the Lagrangian radii of the state (BarnesHutEngine.lagrangian_radii(lagrange_fractions,
     lagrange_centre)) with the cadence rules of energy_file (lagrange_every), one line each: `step,t,cx,cy,r_f1,...` (%.17g).
     Not part of gpu_parallel_duration_us.
+    pairs_file: after the last step, also write the pair-separation counts of the final state (BarnesHutEngine.pair_counts) in
+    pairs_bins bins, pairs_spacing "log" or "linear", over pairs_range = (rmin, rmax): the line `# r_lo,r_hi,dd`, then one row
+    per bin.  With pairs_randoms = NR points drawn uniformly in the bounding box of the final positions from
+    np.random.default_rng(pairs_seed), also their cross counts and the Davis-Peebles correlation
+    (BarnesHutEngine.correlation): `# r_lo,r_hi,dd,dr,xi` (%.17g; nan where dr = 0).  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -129,6 +136,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("integrator must be 'euler' or 'kdk'")
     if (profile_file is None) != (profile_bins is None):
         raise ValueError("profile_file and profile_bins go together")
+    if pairs_file is not None and (pairs_bins is None or pairs_range is None):
+        raise ValueError("pairs_file needs pairs_bins and pairs_range")
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -264,6 +273,17 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, profile_file) if not os.path.isabs(profile_file) else profile_file, "w") as f:
                 f.write("# r_lo,r_hi,count,sigma,vr,vt,sigma_r,sigma_t\n")
                 f.write("".join("%.17g,%.17g,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(*cols)))
+        if pairs_file is not None:
+            edges = radial_edges(float(pairs_range[0]), float(pairs_range[1]), int(pairs_bins), pairs_spacing)
+            with open(os.path.join(out_dir, pairs_file) if not os.path.isabs(pairs_file) else pairs_file, "w") as f:
+                if pairs_randoms is None:
+                    dd = eng.pair_counts(edges)
+                    f.write("# r_lo,r_hi,dd\n")
+                    f.write("".join("%.17g,%.17g,%d\n" % r for r in zip(dd.edges[:-1], dd.edges[1:], dd.counts)))
+                else:
+                    xi, dd, dr = eng.correlation(edges, pairs_random_points(pos, pairs_randoms, pairs_seed))
+                    f.write("# r_lo,r_hi,dd,dr,xi\n")
+                    f.write("".join("%.17g,%.17g,%d,%d,%.17g\n" % r for r in zip(dd.edges[:-1], dd.edges[1:], dd.counts, dr.counts, xi)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr, lagrange):
@@ -287,6 +307,15 @@ def field_grid_points(grid, box, positions) -> np.ndarray:
     xs = x0 + (np.arange(nx) + 0.5) * ((x1 - x0) / nx)
     ys = y0 + (np.arange(ny) + 0.5) * ((y1 - y0) / ny)
     return np.stack([np.tile(xs, ny), np.repeat(ys, nx)], axis=1)
+
+
+def pairs_random_points(positions, n_random: int, seed: int = 0) -> np.ndarray:
+    """The (n_random, 2) points of --pairs-randoms: uniform in the bounding box of `positions` from np.random.default_rng(seed)."""
+    p = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+    if len(p) == 0 or n_random < 1:
+        raise ValueError("random points need bodies to bound them and n_random >= 1")
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    return lo + (hi - lo) * np.random.default_rng(seed).random((int(n_random), 2))
 
 
 def profile_edges(bins: int, rng, spacing: str, positions, centre) -> np.ndarray:
@@ -387,6 +416,15 @@ def _parse(argv):
     ap.add_argument("--lagrange-every", type=int, default=0, metavar="K",
                     help="steps between two lines of --lagrange-file (0: first and last state only)")
     ap.add_argument("--lagrange-centre", nargs="+", default=None, metavar="C", help="density (default), com or X Y")
+    ap.add_argument("--pairs-file", default=None, metavar="PATH",
+                    help="after the last step, also write r_lo,r_hi,dd (the pairs of bodies per separation bin) of the final state; "
+                         "with --pairs-randoms also dr and the Davis-Peebles correlation xi (needs --pairs-bins and --pairs-range)")
+    ap.add_argument("--pairs-bins", type=int, default=None, metavar="NB", help="bins of --pairs-file (1 .. 1024)")
+    ap.add_argument("--pairs-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"), help="the separations the bins cover")
+    ap.add_argument("--pairs-spacing", choices=["log", "linear"], default=None, help="spacing of the bin edges (default log)")
+    ap.add_argument("--pairs-randoms", type=int, default=None, metavar="NR",
+                    help="random points, uniform in the bounding box of the final positions, for dr and xi")
+    ap.add_argument("--pairs-seed", type=int, default=None, metavar="S", help="seed of --pairs-randoms (default 0)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -432,6 +470,20 @@ def _parse(argv):
         ap.error("--lagrange-fractions, --lagrange-every and --lagrange-centre need --lagrange-file")
     if a.lagrange_fractions is not None and (len(a.lagrange_fractions) > 32 or not all(0.0 < f <= 1.0 for f in a.lagrange_fractions)):
         ap.error("--lagrange-fractions: at most 32, each in (0, 1]")
+    if a.pairs_file is not None and (a.pairs_bins is None or a.pairs_range is None):
+        ap.error("--pairs-file needs --pairs-bins and --pairs-range")
+    if a.pairs_file is None and any(v is not None for v in (a.pairs_bins, a.pairs_range, a.pairs_spacing, a.pairs_randoms, a.pairs_seed)):
+        ap.error("--pairs-bins, --pairs-range, --pairs-spacing, --pairs-randoms and --pairs-seed need --pairs-file")
+    if a.pairs_seed is not None and a.pairs_randoms is None:
+        ap.error("--pairs-seed needs --pairs-randoms")
+    if a.pairs_bins is not None and not 1 <= a.pairs_bins <= 1024:
+        ap.error("--pairs-bins: 1 .. 1024")
+    if a.pairs_range is not None and not (0.0 <= a.pairs_range[0] < a.pairs_range[1] < float("inf")):
+        ap.error("--pairs-range: 0 <= RMIN < RMAX, finite")
+    if a.pairs_range is not None and (a.pairs_spacing or "log") == "log" and a.pairs_range[0] <= 0.0:
+        ap.error("--pairs-range: log spacing needs RMIN > 0")
+    if a.pairs_randoms is not None and a.pairs_randoms < 1:
+        ap.error("--pairs-randoms: at least 1")
     a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     if a.groups_min is not None and a.groups_min < 1:
@@ -506,7 +558,9 @@ def main(argv=None) -> int:
         profile_file=a.profile_file, profile_bins=a.profile_bins, profile_range=a.profile_range,
         profile_spacing=a.profile_spacing, profile_centre=a.profile_centre, lagrange_file=a.lagrange_file,
         lagrange_fractions=(0.01, 0.1, 0.5, 0.9) if a.lagrange_fractions is None else tuple(a.lagrange_fractions),
-        lagrange_every=a.lagrange_every, lagrange_centre=a.lagrange_centre)
+        lagrange_every=a.lagrange_every, lagrange_centre=a.lagrange_centre, pairs_file=a.pairs_file, pairs_bins=a.pairs_bins,
+        pairs_range=a.pairs_range, pairs_spacing=a.pairs_spacing or "log", pairs_randoms=a.pairs_randoms,
+        pairs_seed=a.pairs_seed or 0)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

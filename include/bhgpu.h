@@ -529,6 +529,38 @@ int bh_neighbours(bh_ctx *ctx, const double *points, int64_t n_points, int32_t k
 int bh_count_within(bh_ctx *ctx, const double *points, int64_t n_points, double radius, uint32_t *counts);
 int bh_neighbours_times(bh_ctx *ctx, double *build_ms, double *query_ms);
 
+/* --- pair counts: how many pairs lie at each separation (DD(r), the raw material of the two-point correlation) ----------------
+ * Distance.  For a body j and a query q of the CURRENT state: dx = x_j - q.x; dy = y_j - q.y; d2 = dx * dx + dy * dy, in fp64
+ *   with nothing fused, in every precision (an fp32 state is widened first, exactly): the d2 of bh_count_within.  It is
+ *   symmetric in (i, j), bit for bit.
+ * Edges.  edges[nb + 1] must be finite, >= 0 and strictly ascending, 1 <= nb <= BH_PAIR_MAX_BINS.  e2_k = edges[k] * edges[k]
+ *   is formed once in fp64 on the host; the e2 must be finite and strictly ascending too.
+ * Bins.  counts[nb + 2]: counts[0] ("below") the pairs with d2 <= e2_0; counts[k + 1] those with e2_k < d2 <= e2_{k+1};
+ *   counts[nb + 1] ("beyond") those with d2 > e2_nb -- the bin index is the number of e2_k < d2.  The upper edge is inclusive,
+ *   as in bh_count_within and bh_groups, so coincident distinct bodies (d2 = 0) are always "below", even with edges[0] = 0.
+ * Auto mode (points == NULL, n_points must be n): every unordered pair i != j of the n bodies is counted exactly once; the
+ *   counts sum to n (n - 1) / 2.
+ * Cross mode (points[n_points][2], finite coordinates that are nobody's): every (point, body) combination is counted once,
+ *   nobody is left out; the counts sum to n_points * n.  A point on a body gives d2 = 0, which is "below".
+ * evals (may be NULL): the number of d2 the call computed -- deterministic for a given state and call, a measure of the work
+ *   and no part of the answer.  The search (the index of the neighbour queries, rebuilt on every call) takes a node whole when
+ *   both of its distance bounds fall in one bin; rounding cannot invert the bounds, so the counts are those of the brute-force
+ *   definition above, bit for bit.
+ * bh_pair_counts_times: HIP-event times of the last bh_pair_counts: the structure's build (bounds, sort, boxes) and the
+ *   traversals (a point launch's own sort included), the download excluded.
+ * It reads the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.  It waits for the stream.
+ * Unlike bh_count_within it is allowed in LET mode and with world > 1: it then counts THIS CONTEXT'S OWN bodies (all of the
+ *   bodies this context holds); the pairs across ranks are the caller's to add, as cross counts of another rank's positions.
+ * Errors: BH_ERR_ARG for nb or edges outside the rules above, a null edges or counts, n_points < 0, points == NULL with
+ *   n_points != n, a non-finite point (checked before anything is enqueued), and -- found by the bounds pass, with a message
+ *   that says so -- a non-finite body position in the state.  BH_ERR_STATE before any upload.  BH_ERR_CAPACITY for more than
+ *   2^24 bodies.  With n = 0 or n_points = 0 all counts are zero; n = 1 in auto mode gives all zeros. */
+#define BH_PAIR_MAX_BINS 1024
+int bh_pair_counts(bh_ctx *ctx, const double *points, int64_t n_points, const double *edges, int32_t nb, int64_t *counts,
+                   int64_t *evals);
+int bh_pair_counts_times(bh_ctx *ctx, double *build_ms, double *query_ms);
+
 /* --- groups: which bodies belong together (friends of friends), and a catalogue of the groups ---------------------------------
  * Distance.  For bodies i != j of the CURRENT state: dx = x_j - x_i; dy = y_j - y_i; d2 = dx * dx + dy * dy, in fp64 with nothing
  *   fused, in every precision (an fp32 state is widened first, exactly): the d2 of bh_count_within.  It is symmetric in (i, j).
