@@ -79,6 +79,16 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
                                    // (BH_SORT_BUCKET=0: always the LSD passes; 2: always the bucket sort, tests)
     uint64_t *splitters = nullptr;
     uint16_t *sort_dig = nullptr;  // bucket of every key (written by the histogram, read by the scatter)
+    // direct input of the bucket sort (bh_sort.hpp; fp32-tree builds): 1 = when at most sort_direct_max bodies changed bucket
+    // (BH_SORT_DIRECT=0: never; 2: whatever their number -- the list holds every body --, tests; BH_SORT_DIRECT_MAX: the threshold)
+    int sort_direct = 1;
+    int64_t sort_direct_max = kSortDirectMax;
+    uint64_t *keys_scatter = nullptr;     // the counting pass's own output array, so that both inputs end in keys[1] / vals[1]
+    uint64_t *direct_list = nullptr, *direct_range_keys = nullptr;
+    uint32_t *direct_count = nullptr;     // two counters: a build counts into one and clears the other for the next
+    uint32_t direct_cap = 0, direct_subcap = 0;
+    int direct_nsub = 1;
+    int direct_slot = 0;                  // the counter the next build counts into (zero by then)
     int build_items = 0;           // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
     bool hilbert = false;                // fp32 mode: Hilbert-ordered keys (BH_HILBERT=0 disables, A/B)
     bool chain_collapse = true;          // fp32 step build: slots link past single-child cell chains (BH_CHAIN_COLLAPSE=0 disables, A/B)
@@ -373,7 +383,7 @@ int enqueue_lsd_passes(hipStream_t st, uint64_t *const keys[2], uint32_t *const 
         const int shift = p * SB;
         auto scatter = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(nbl), dim3(kBlock), 0, st, keys[cur], packed ? nullptr : vals[cur], keys[cur ^ 1],
-                               vals[cur ^ 1], counts, rows, n, shift, (int)nbl, nullptr, nullptr);
+                               vals[cur ^ 1], counts, rows, n, shift, (int)nbl, nullptr, nullptr, nullptr, 0u, 0u, 1);
         };
         hipLaunchKernelGGL((radix_hist<SI, SB>), dim3(nbl), dim3(kBlock), 0, st, keys[cur], counts, n, shift, (int)nbl);
         hipLaunchKernelGGL(radix_rowscan, dim3(1 << SB), dim3(kBlock), 0, st, counts, rows, (int)nbl);
@@ -432,6 +442,21 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
                                         : ((n > (int64_t)3 << 20) ? kMaxSplitSamples : kBucketsBig);
         static_assert(kBucketMaxN == (int64_t)1 << 20 && kBucketMaxNBig == (int64_t)1 << 22, "BASELINE configs 3 and 4 fit");
         done.sort_bucket = bucket || single; done.sort_packed = pack;
+        // direct input (bh_sort.hpp): the state is in the sorted order of a recent build of these bodies, so the keys come out
+        // sorted but for the bodies that changed bucket; the device decides per build whether the counting pass has to run
+        const bool direct = bucket && !TREE64 && c->sort_direct != 0 && c->carry.samples_n == n;
+        SortDirect sd;
+        BucketDirect bd;
+        if (direct) {
+            const uint32_t len = (uint32_t)((n + nb - 1) / nb);
+            sd.count = c->direct_count + c->direct_slot * kDirectCounterWords;
+            sd.count_next = c->direct_count + (c->direct_slot ^ 1) * kDirectCounterWords;
+            sd.list = c->direct_list; sd.range_keys = c->direct_range_keys; sd.cap = c->direct_cap; sd.subcap = c->direct_subcap;
+            sd.len = len; sd.nsub = c->direct_nsub;
+            bd.count = sd.count; bd.list = sd.list; bd.range_keys = sd.range_keys; bd.keys = c->keys[0]; bd.scratch = c->keys_scatter;
+            bd.n = n; bd.cap = sd.cap; bd.subcap = sd.subcap; bd.len = len; bd.nb = nb; bd.nsub = sd.nsub;
+            c->direct_slot ^= 1;
+        }
         {
             const unsigned nkb = blocks_for(n, kBlock);
             auto keys_launch = [&](auto fs, auto pk, auto hil) {
@@ -441,7 +466,7 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
                 hipLaunchKernelGGL((keys_kernel<Real2, H, P, F>), dim3(nkb + (smp ? ns / kWave : 0)), dim3(kBlock), 0, st, pos, c->box,
                                    c->keys[0], c->vals[0], n, Dm, (smp && !TREE64) ? (const float2 *)c->spos : nullptr, c->splitters, nb, ns,
                                    slots, c->ctr, smp ? c->bsum_sort : nullptr, smp ? nb : 0, (smp && TREE64) ? c->perm : nullptr,
-                                   from_walk ? 1 : 0);
+                                   from_walk ? 1 : 0, smp ? sd : SortDirect{});
             };
             // (exact mode and BH_HILBERT=0: child-index keys, packed all the same)
             dispatch(keys_launch, slots != nullptr, pack, c->hilbert);
@@ -451,7 +476,7 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
         int cur = 0;
         if (single) {
             hipLaunchKernelGGL(bucket_sort_kernel, dim3(1), dim3(kBsThreads), 0, st, c->keys[0], c->keys[1], c->vals[1],
-                               nullptr, nullptr, &c->ctr->sort_spills, &c->ctr->sort_reruns, (int)n);
+                               nullptr, nullptr, &c->ctr->sort_spills, &c->ctr->sort_reruns, (int)n, BucketDirect{});
             cur = 1;
         } else if (bucket) {
             constexpr int SI = (ITEMS == kItems ? kSortItems : ITEMS);
@@ -465,17 +490,26 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
                                        c->keys[1], c->vals[1], c->radix_counts, c->bsum_sort, n, 0, (int)nbl, c->sort_dig,
                                        c->bsum_sort + kBucketStartOffset);
                 } else {
+                    // (direct: both kernels return at once unless the device took the decision for the counting pass, and the
+                    // scatter writes an array of its own -- the sort's output is keys[1] / vals[1] whichever input it had)
                     hipLaunchKernelGGL((radix_hist<SI, NBITS, true>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->radix_counts, n,
-                                       0, (int)nbl, c->splitters, c->sort_dig, c->bsum_sort);
+                                       0, (int)nbl, c->splitters, c->sort_dig, c->bsum_sort, sd.count, sd.cap, sd.subcap, sd.nsub);
                     hipLaunchKernelGGL((radix_scatter_w<SI, NBITS, 1, true>), dim3(nbl), dim3(kBlock), 0, st, c->keys[0], c->vals[0],
-                                       c->keys[1], c->vals[1], c->radix_counts, c->bsum_sort, n, 0, (int)nbl, c->sort_dig,
-                                       c->bsum_sort + kBucketStartOffset);
+                                       direct ? c->keys_scatter : c->keys[1], c->vals[1], c->radix_counts, c->bsum_sort, n, 0, (int)nbl,
+                                       c->sort_dig, c->bsum_sort + kBucketStartOffset, sd.count, sd.cap, sd.subcap, sd.nsub);
                 }
             };
             if (nb == kBuckets) pass(std::integral_constant<int, 8>{}); else pass(std::integral_constant<int, 10>{});
-            hipLaunchKernelGGL(bucket_sort_kernel, dim3(nb), dim3(kBsThreads), 0, st, c->keys[1], c->keys[0], c->vals[0],
-                               c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0);
-            cur = 0;
+            if (direct) {
+                hipLaunchKernelGGL(bucket_sort_kernel, dim3(nb), dim3(kBsThreads), 0, st, c->keys_scatter, c->keys[1], c->vals[1],
+                                   c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0, bd);
+                cur = 1;
+            } else {
+                hipLaunchKernelGGL(bucket_sort_kernel, dim3(nb), dim3(kBsThreads), 0, st, c->keys[1], c->keys[0], c->vals[0],
+                                   c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0,
+                                   BucketDirect{});
+                cur = 0;
+            }
         } else {
             constexpr int SI = (ITEMS == kItems ? kSortItems : ITEMS);
             cur = enqueue_lsd_passes<SI>(st, c->keys, c->vals, c->radix_counts, c->bsum_sort, n, 2 * Dm, pack);
@@ -971,6 +1005,9 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     c->exact_thresholds = c->mode == Mode::Exact && c->walk_asm && !(cfg->flags & BH_FLAG_WALK_PORTABLE);
     if (const char *e = std::getenv("BH_SORT_PACK")) c->sort_pack = std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_SORT_BUCKET")) c->sort_bucket = std::atoi(e);
+    if (const char *e = std::getenv("BH_SORT_DIRECT")) { const int d = std::atoi(e); c->sort_direct = (d >= 0 && d <= 2) ? d : 1; }
+    if (const char *e = std::getenv("BH_SORT_DIRECT_MAX")) c->sort_direct_max = std::max<long long>(0, std::atoll(e));
+    if (c->tree64()) c->sort_direct = 0;
     if (const char *e = std::getenv("BH_BUILD_ITEMS")) c->build_items = std::atoi(e);
     if (const char *e = std::getenv("BH_REORDER_EVERY")) c->reorder_every = std::max(0, std::atoi(e));
     c->hilbert = !c->tree64();
@@ -1020,6 +1057,19 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
       A(&c->bsum_sort, 2 * kBucketStartOffset);               // bucket totals, then bucket starts
       A(&c->splitters, kBucketsBig);
       A(&c->sort_dig, (size_t)std::min<int64_t>(cap, kBucketMaxNBig) + 16);
+      if (c->sort_direct) {
+          const int64_t most = std::min<int64_t>(cap, kBucketMaxNBig);        // (larger launches take the LSD passes)
+          c->direct_cap = (uint32_t)std::min<int64_t>(most, c->sort_direct == 2 ? most : c->sort_direct_max);
+          // adaptive: kDirectSubs lists, each with room for four times its share of T (a power of two, at least 16 -- and so at
+          // least T where T is small); every body listed: one list
+          c->direct_nsub = c->sort_direct == 2 ? 1 : kDirectSubs;
+          c->direct_subcap = c->direct_cap;
+          if (c->sort_direct != 2) { c->direct_subcap = 16; while ((int64_t)c->direct_subcap * (kDirectSubs / 4) < c->direct_cap) c->direct_subcap *= 2; }
+          A(&c->keys_scatter, (size_t)most);
+          A(&c->direct_list, std::max<size_t>((size_t)c->direct_nsub * c->direct_subcap, 1));
+          A(&c->direct_range_keys, kBucketsBig);
+          A(&c->direct_count, 2 * kDirectCounterWords);
+      }
     }
     // scan scratch (bsum_u32, bsum_d3): one record per scan tile, sized for the smallest tile
     const size_t scan_tiles = std::max<size_t>(blocks_for(cap + 1, kTile), blocks_for(std::min<int64_t>(cap, 1 << 22) + 1, kBlock * kSmallItems)) + 8;
@@ -1046,6 +1096,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     }
     if (rc) return bail(rc);
     if (hipMemset(c->ctr, 0, sizeof(TreeCounters)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
+    if (c->direct_count && hipMemset(c->direct_count, 0, 2 * kDirectCounterWords * sizeof(uint32_t)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
     if (!c->tree64()) {
         const void *wc[4] = {c->aux, c->spos, c->smass, nullptr};
         if (hipMemcpy(c->walk_consts, wc, sizeof(wc), hipMemcpyHostToDevice) != hipSuccess) { c->err = "hipMemcpy failed"; return bail(BH_ERR_DEVICE); }

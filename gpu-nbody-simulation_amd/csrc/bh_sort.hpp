@@ -87,6 +87,78 @@ __device__ __forceinline__ uint32_t bucket_of(uint64_t key, const uint64_t *spl)
     return (uint32_t)b;
 }
 
+// run-time NB (sorted spl, spl[0] = 0, nb a power of two): the same answer as bucket_of<NB>
+__device__ __forceinline__ uint32_t bucket_of_n(uint64_t key, const uint64_t *spl, int nb)
+{
+    int b = 0;
+    for (int s = nb >> 1; s >= 1; s >>= 1) b += (spl[b + s] <= key) ? s : 0;
+    return (uint32_t)b;
+}
+
+// ---- direct input (fp32-tree builds whose state is in the previous sorted order) ---------------------------
+// keys_kernel writes the packed keys in state order, and the state is the sorted order of a recent build: the
+// array is sorted but for the few bodies that overtook a neighbour since.  The counting pass above moves all of
+// it to move those few.  Direct input skips it:
+//   * bucket b owns the array range [b * L, (b + 1) * L) of keys[0], L = ceil(n / nb) (the last range is shorter,
+//     ranges that start at or beyond n are empty);
+//   * range key j is the key, in this build's box, of the body that stands at j * L (0 for j = 0, "infinity" for an
+//     empty range).  While the range keys are non-decreasing they are splitters like any others, and
+//     bucket_of(key, range keys) == b  <=>  range key b <= key < range key b + 1  (stays_in below -- the ONE test
+//     of keys_kernel and of bucket_sort_kernel; with equal range keys the left of the two buckets keeps nothing,
+//     exactly as bucket_of routes);
+//   * keys_kernel appends every key that does not stay in the bucket of its index (a "crosser") to one of kDirectSubs
+//     lists, each behind a counter of its own (atomics on one word cost ~3.5 ns apiece, lists chosen by wave number
+//     spread them over 64 words in 64 memory channels), and leaves keys[0] complete either way;
+//   * at most T crossers in all, no list overfull, nobody said otherwise (direct_total): radix_hist and radix_scatter_w
+//     return at once, and workgroup b of bucket_sort_kernel takes the keys of its range that stay plus the listed keys
+//     that bucket_of sends to b, in the order of their body index (which is the order the counting pass would have
+//     delivered them in: the result is the same stable sort);
+//   * otherwise -- more crossers, a list that ran over, half a wave crossing at once, range keys out of order (the first
+//     sample workgroup of keys_kernel looks) -- the counting pass runs as before.  The decision is a function of 65
+//     words in device memory, evaluated alike by every wave of the three kernels.
+// No kernel waits for another workgroup: every key workgroup forms the two or three range keys it needs itself.
+constexpr int64_t kSortDirectMax = 1024;                   // default T (below where the two paths cross, by the spread)
+constexpr int kDirectSubs = 64;                            // crosser lists (and counters) of an adaptive build
+constexpr int kDirectCounterWords = 64 * (1 + kDirectSubs);   // one build's counters
+constexpr uint32_t kDirectStride = 64;                     // words between two counters: 256 bytes, another memory channel
+constexpr uint64_t kRangeKeyInf = ~0ull;                   // range key of an empty range: above every 40-bit key
+struct SortDirect {
+    // the counters of THIS build (zero on entry), kDirectStride words apart: word 0 is set when the counting pass has to
+    // run whatever the counts, counter 1 + s belongs to list s; null: no direct input
+    uint32_t *count = nullptr;
+    uint32_t *count_next = nullptr; // the counters of the next build: keys_kernel clears them
+    uint64_t *list = nullptr;       // [nsub][subcap] the packed keys of the crossers, in arrival order
+    uint64_t *range_keys = nullptr; // [nb] written by keys_kernel's first sample workgroup
+    uint32_t cap = 0;               // T: most crossers in all lists together
+    uint32_t subcap = 0;            // room of one list
+    uint32_t len = 0;               // L
+    int nsub = 1;                   // lists (a power of two, <= 64: one lane each in direct_total)
+};
+// The decision, taken alike by every wave of every kernel of the build (all lanes call): the number of listed crossers, or
+// ~0u when the counting pass has to run -- told so, a list overfull, or more than cap crossers in all.
+// (in two halves: a kernel that has other work to start issues the loads first and decides after it, so that the build
+// that takes the counting pass does not wait for them)
+struct DirectWords { uint32_t v, off; };
+__device__ __forceinline__ DirectWords direct_load(const uint32_t *count, int nsub)
+{
+    const int l = threadIdx.x & 63;
+    return DirectWords{(l < nsub) ? count[kDirectStride * (1u + (uint32_t)l)] : 0u, count[0]};
+}
+__device__ __forceinline__ uint32_t direct_total(DirectWords w, uint32_t cap, uint32_t subcap)
+{
+    const uint32_t v = w.v, off = w.off;
+    uint32_t total = v;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) total += (uint32_t)__shfl_xor((int)total, o);
+    const bool bad = off != 0u || __ballot(v > subcap) != 0ull || total > cap;
+    return bad ? ~0u : total;
+}
+__device__ __forceinline__ uint32_t direct_total(const uint32_t *count, int nsub, uint32_t cap, uint32_t subcap)
+{
+    return direct_total(direct_load(count, nsub), cap, subcap);
+}
+__device__ __forceinline__ bool stays_in(uint64_t key40, uint64_t lo, uint64_t hi) { return lo <= key40 && key40 < hi; }
+
 // LDS atomics of one wave instruction that hit ONE counter are served lane after lane.  On sorted data -- the
 // bucket digit of a tile, the upper bytes of the keys of a bucket -- that is every instruction of the count
 // phase.  A full wave whose lanes all hold the same digit therefore adds 64 through one lane, and its ranks
@@ -117,8 +189,12 @@ __global__ __launch_bounds__(kBlock) void radix_hist(const uint64_t *__restrict_
                                                       int shift, int nblocks,
                                                       const uint64_t *__restrict__ splitters = nullptr,
                                                       uint16_t *__restrict__ dig16 = nullptr,
-                                                      uint32_t *__restrict__ row_total = nullptr)
+                                                      uint32_t *__restrict__ row_total = nullptr,
+                                                      const uint32_t *__restrict__ direct_count = nullptr,
+                                                      uint32_t direct_cap = 0, uint32_t direct_subcap = 0, int direct_nsub = 1)
 {
+    DirectWords dw{0u, 1u};
+    if (BUCKET && direct_count != nullptr) dw = direct_load(direct_count, direct_nsub);
     constexpr int R = 1 << BITS;
     __shared__ uint32_t h[R];
     __shared__ uint64_t spl[BUCKET ? R : 1];
@@ -132,6 +208,7 @@ __global__ __launch_bounds__(kBlock) void radix_hist(const uint64_t *__restrict_
         }
     for (int d = threadIdx.x; d < R; d += kBlock) h[d] = 0;
     __syncthreads();
+    if (BUCKET && direct_count != nullptr && direct_total(dw, direct_cap, direct_subcap) != ~0u) return;   // direct input: nothing to count
     const int64_t base = (int64_t)blockIdx.x * (kBlock * ITEMS);
     uint32_t guess = 0;
 #pragma unroll
@@ -197,9 +274,13 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_w(const uint64_t *__rest
                                                            const uint32_t *__restrict__ row_total, int64_t n,
                                                            int shift, int nblocks,
                                                            const uint16_t *__restrict__ dig16 = nullptr,
-                                                           uint32_t *__restrict__ bucket_start = nullptr)
+                                                           uint32_t *__restrict__ bucket_start = nullptr,
+                                                           const uint32_t *__restrict__ direct_count = nullptr,
+                                                           uint32_t direct_cap = 0, uint32_t direct_subcap = 0, int direct_nsub = 1)
 {
     static_assert(!BUCKET || PACK == 1, "the bucket pass moves packed keys");
+    DirectWords dw{0u, 1u};
+    if (BUCKET && direct_count != nullptr) dw = direct_load(direct_count, direct_nsub);
     // (4) the tile is first sorted by digit INTO LDS, then written out in that order: the keys a digit
     // has in a tile leave as one contiguous run instead of separate partial-line writes from
     // different rounds
@@ -222,6 +303,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_w(const uint64_t *__rest
 #pragma unroll
         for (int k = 0; k < kWavesPerBlock; ++k) { woff[k][d] = 0; match[k][d] = 0ull; }
     __syncthreads();
+    if (BUCKET && direct_count != nullptr && direct_total(dw, direct_cap, direct_subcap) != ~0u) return;   // direct input: nothing to move
 
     const int64_t tile_base = (int64_t)blockIdx.x * TILE;
     const int64_t base = tile_base + (int64_t)w * (kWave * ITEMS);
@@ -426,7 +508,7 @@ __device__ __forceinline__ uint32_t bs_scan256(uint32_t v, uint32_t *sm, uint32_
 // the full passes instead.  Either way the result is the stable order by key.
 constexpr int kFixRun = 8;
 template <int ITEMS>
-__device__ __forceinline__ void bucket_sort_lds(const uint64_t *__restrict__ in, int m, uint64_t *skey,
+__device__ __forceinline__ void bucket_sort_lds(const uint64_t *in, int m, uint64_t *skey,
                                                 uint32_t (*woff)[kDigits], uint64_t (*match)[kDigits],
                                                 uint32_t *sm, uint64_t *s_red, uint32_t *s_flag,
                                                 uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
@@ -572,13 +654,17 @@ __device__ __forceinline__ void bucket_sort_lds(const uint64_t *__restrict__ in,
         if (too_long) *s_flag = 1u;
         __syncthreads();
         if (*s_flag == 0u) return;
-        // a long run: the full passes from the input (rare: bodies piled up on a few key values under a wide span)
+        // a long run: the full passes (rare: bodies piled up on a few key values under a wide span).  They start from the
+        // keys as the three top passes left them in LDS, relative to kmin already -- keys equal in every bit are equal in
+        // their top bits and therefore still in input order there, so the stable passes end in the same order as from the
+        // input itself (which, with direct input, may BE this buffer and is gone)
         if (t == 0) atomicAdd(reruns, 1u);
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) {
             const int i = wbase + r * kWave + l;
-            key[r] = (i < m) ? in[i] - kmin : ~0ull;
+            key[r] = (i < m) ? skey[i] : ~0ull;
         }
+        __syncthreads();                                        // (every key is in registers before a pass writes the buffer)
         for (int k = t; k < kBsWaves * kDigits; k += kBsThreads) (&woff[0][0])[k] = 0;
         __syncthreads();
         first = 0; passes = full; fix = false;
@@ -590,16 +676,46 @@ __device__ __forceinline__ void bucket_sort_lds(const uint64_t *__restrict__ in,
     }
 }
 
+// What bucket_sort_kernel needs for direct input (see "direct input" above); count == nullptr: none.
+struct BucketDirect {
+    const uint32_t *count = nullptr;    // the crosser counters keys_kernel left
+    const uint64_t *list = nullptr;     // the crossers' packed keys, [nsub][subcap]
+    const uint64_t *range_keys = nullptr;
+    uint64_t *keys = nullptr;           // the packed keys in state order (keys_kernel's output)
+    uint64_t *scratch = nullptr;        // the counting pass's output array: free on this path
+    int64_t n = 0;
+    uint32_t cap = 0, subcap = 0, len = 0;
+    int nb = 0, nsub = 1;
+};
+constexpr int kDirectItems = 4;                                  // a range is at most 4 keys per thread of the workgroup
+constexpr int kMineCap = kBsWaves * kDigits - kBucketsBig;       // arrivals of one bucket held in LDS (3,072)
+
+// sum of v over the 1,024 threads (every thread calls); tmp: >= kBsWaves words of LDS
+__device__ __forceinline__ uint32_t bs_sum1024(uint32_t v, uint32_t *tmp, uint32_t &exclusive)
+{
+    const uint32_t inc = wave_inclusive_sum(v);
+    if (lane_id() == kWave - 1) tmp[wave_id()] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < kBsWaves; ++k) { const uint32_t q = tmp[k]; base += (k < wave_id()) ? q : 0u; tot += q; }
+    __syncthreads();
+    exclusive = base + inc - v;
+    return tot;
+}
+
 // One workgroup of 1,024 threads per bucket.  bucketed: the packed keys grouped by bucket (step 1's output);
 // kout / vout: the sorted plain keys and body indices; kout doubles as the second buffer of the
-// through-memory path.
+// through-memory path.  dz: direct input -- when the crosser counters allow it, the workgroup takes its keys from its
+// range of dz.keys and from the crosser list instead, and works out its place in the output from the list.
 __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__restrict__ bucketed,
                                                                   uint64_t *__restrict__ kout,
                                                                   uint32_t *__restrict__ vout,
                                                                   const uint32_t *__restrict__ bucket_total,
                                                                   const uint32_t *__restrict__ bucket_start,
                                                                   uint32_t *__restrict__ spills,
-                                                                  uint32_t *__restrict__ reruns, int single_m)
+                                                                  uint32_t *__restrict__ reruns, int single_m,
+                                                                  BucketDirect dz = BucketDirect{})
 {
     __shared__ uint64_t skey[kBucketCap];
     __shared__ uint32_t woff[kBsWaves][kDigits];
@@ -607,14 +723,121 @@ __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__res
     __shared__ uint32_t sm[8];
     __shared__ uint64_t s_or[2 * kBsWaves];
     __shared__ uint32_t s_flag;
+    __shared__ uint32_t s_dz[3];                                // direct input: arrivals, arrivals from lower ranges, departures
     const int t = threadIdx.x, w = wave_id(), l = lane_id();
     // where this bucket starts and how many keys it holds: the counting pass's scatter left both (wave-uniform loads)
     // (bucket_total == nullptr: a launch of at most kBucketCap keys is ONE bucket -- the keys as keys_kernel left them, no
     // counting pass in front: three launches less for the small launches whose builds are chains of 5 us launches)
-    const int64_t start = bucket_total ? (int64_t)bucket_start[blockIdx.x] : 0;
-    const int m = bucket_total ? (int)bucket_total[blockIdx.x] : single_m;
-    if (m == 0) return;
-    uint64_t *in = bucketed + start;
+    int64_t start;
+    int m;
+    uint64_t *in;
+    // (the counting pass's words are loaded before the decision is looked at: stale but readable when it is not taken)
+    const int64_t counted_start = bucket_total ? (int64_t)bucket_start[blockIdx.x] : 0;
+    const int counted_m = bucket_total ? (int)bucket_total[blockIdx.x] : single_m;
+    const uint32_t crossers = dz.count ? direct_total(dz.count, dz.nsub, dz.cap, dz.subcap) : ~0u;       // (uniform)
+    if (crossers == ~0u) {
+        start = counted_start;
+        m = counted_m;
+        if (m == 0) return;
+        in = bucketed + start;
+    } else {
+        const int b = (int)blockIdx.x;
+        const int64_t r0 = ((int64_t)b * dz.len < dz.n) ? (int64_t)b * dz.len : dz.n;
+        const int len = (int)((r0 + dz.len < dz.n ? r0 + dz.len : dz.n) - r0);
+        if (crossers == 0u) {                                    // nobody changed bucket: the range as it stands
+            start = r0; m = len;
+            if (m == 0) return;
+            in = dz.keys + r0;
+        } else {
+            // every workgroup routes the whole list (<= T binary searches over 1,024 threads, range keys in LDS): what
+            // every bucket gains and loses gives this bucket's place in the output, the keys sent here are set aside
+            uint64_t *spl = &match[0][0];                        // [nb]
+            uint64_t *mine = spl + kBucketsBig;                  // [kMineCap]
+            uint32_t *delta = &woff[0][0];                       // [nb] arrived - left (mod 2^32)
+            uint32_t *held = reinterpret_cast<uint32_t *>(skey);  // [nsub] entries of every list
+            for (int k = t; k < dz.nb; k += kBsThreads) { spl[k] = dz.range_keys[k]; delta[k] = 0u; }
+            if (t < 3) s_dz[t] = 0u;
+            if (t < dz.nsub) held[t] = dz.count[kDirectStride * (1u + (uint32_t)t)];
+            __syncthreads();
+            // every slot of every list is looked at (nsub * subcap slots: four per thread with the default capacity)
+            uint32_t most = 0;
+            for (int k = 0; k < dz.nsub; ++k) most = (held[k] > most) ? held[k] : most;
+            const uint32_t slots = (dz.nsub > 1) ? (uint32_t)dz.nsub * dz.subcap : most;
+            const uint32_t lg_sub = 31u - (uint32_t)__clz(dz.nsub > 1 ? (int)dz.subcap : 1);   // (subcap is a power of two then)
+            auto listed = [&](uint32_t x) -> bool { return dz.nsub > 1 ? (x & (dz.subcap - 1u)) < held[x >> lg_sub] : true; };
+            for (uint32_t e = (uint32_t)t; e < slots; e += kBsThreads) {
+                if (!listed(e)) continue;
+                const uint64_t word = dz.list[e];
+                const uint32_t idx = (uint32_t)(word >> kPackShift);
+                const int dst = (int)bucket_of_n(word & kKeyMask40, spl, dz.nb), src = (int)(idx / dz.len);
+                atomicAdd(&delta[dst], 1u);
+                atomicSub(&delta[src], 1u);
+                if (dst == b) {
+                    const uint32_t k = atomicAdd(&s_dz[0], 1u);
+                    if (k < (uint32_t)kMineCap) mine[k] = word;
+                    if ((int64_t)idx < r0) atomicAdd(&s_dz[1], 1u);
+                }
+                if (src == b) atomicAdd(&s_dz[2], 1u);
+            }
+            __syncthreads();
+            uint32_t part = 0, ex;
+            for (int k = t; k < b; k += kBsThreads) part += delta[k];
+            uint32_t *tmp = reinterpret_cast<uint32_t *>(s_or);
+            const uint32_t moved = bs_sum1024(part, tmp, ex);    // net arrivals of the buckets before this one (mod 2^32)
+            const uint32_t arrived = s_dz[0], lower = s_dz[1], left = s_dz[2];
+            start = r0 + (int64_t)(int32_t)moved;
+            m = len - (int)left + (int)arrived;
+            if (m <= 0 || start < 0 || start + m > dz.n) return; // (m == 0: an emptied range; the rest cannot happen)
+            if (arrived == 0u && left == 0u) {
+                in = dz.keys + r0;
+            } else {
+                // the bucket's input in body order: arrivals from lower ranges, the keys of the range that stay, arrivals
+                // from higher ranges -- into the sort's LDS buffer, or into this bucket's stretch of the scratch array when
+                // it is too large for LDS (the through-memory path below wants it in memory)
+                uint64_t *ko_ = kout + start;
+                const uint64_t *arr = mine;
+                if (arrived > (uint32_t)kMineCap) {              // more arrivals than LDS holds: listed in the output stretch
+                    __syncthreads();
+                    if (t == 0) s_dz[0] = 0u;
+                    __syncthreads();
+                    for (uint32_t e = (uint32_t)t; e < slots; e += kBsThreads) {
+                        if (!listed(e)) continue;
+                        const uint64_t word = dz.list[e];
+                        if ((int)bucket_of_n(word & kKeyMask40, spl, dz.nb) == b) ko_[atomicAdd(&s_dz[0], 1u)] = word;
+                    }
+                    __threadfence_block();
+                    __syncthreads();
+                    arr = ko_;
+                }
+                uint64_t *g = (m <= kBucketCap) ? skey : dz.scratch + start;
+                const uint64_t lo = spl[b], hi = (b + 1 < dz.nb) ? spl[b + 1] : kRangeKeyInf;
+                uint64_t own[kDirectItems];
+                uint32_t c = 0;
+#pragma unroll
+                for (int j = 0; j < kDirectItems; ++j) {
+                    const int i = kDirectItems * t + j;
+                    own[j] = (i < len) ? dz.keys[r0 + i] : kRangeKeyInf;
+                    c += (i < len && stays_in(own[j] & kKeyMask40, lo, hi)) ? 1u : 0u;
+                }
+                const uint32_t stay = bs_sum1024(c, tmp, ex);
+                uint32_t o = lower + ex;
+#pragma unroll
+                for (int j = 0; j < kDirectItems; ++j)
+                    if (kDirectItems * t + j < len && stays_in(own[j] & kKeyMask40, lo, hi)) { if (o < (uint32_t)m) g[o] = own[j]; ++o; }
+                for (uint32_t q = (uint32_t)t; q < arrived; q += kBsThreads) {
+                    const uint64_t word = arr[q];
+                    const uint32_t idx = (uint32_t)(word >> kPackShift);
+                    uint32_t rank = 0;
+                    for (uint32_t r = 0; r < arrived; ++r) rank += ((uint32_t)(arr[r] >> kPackShift) < idx) ? 1u : 0u;
+                    const uint32_t slot = rank + (((int64_t)idx < r0) ? 0u : stay);
+                    if (slot < (uint32_t)m) g[slot] = word;
+                }
+                __threadfence_block();
+                __syncthreads();
+                in = g;
+            }
+        }
+    }
     uint64_t *ko = kout + start;
     uint32_t *vo = vout + start;
 

@@ -165,20 +165,10 @@ __device__ __forceinline__ uint32_t hilbert3_entry(uint32_t t)
     return ((uint32_t)state << 6) | digits;
 }
 
+// the key of the finest-grid cell (ix, iy): Dm curve digits, high bits first
 template <bool HILBERT>
-__device__ __forceinline__ uint64_t key_of_fast(double x, double y, double x0, double x1, double y0, double y1, int Dm,
-                                                double scale_x, double scale_y, double margin_x, double margin_y,
-                                                const uint8_t *hil3 = nullptr)
+__device__ __forceinline__ uint64_t curve_key(uint32_t ix, uint32_t iy, int Dm, const uint8_t *hil3 = nullptr)
 {
-    const double side = (double)(1u << Dm);
-    const double tx = (x - x0) * scale_x, ty = (y - y0) * scale_y;
-    const double fx = floor(tx), fy = floor(ty);
-    const double rx = tx - fx, ry = ty - fy;
-    // (written so that a NaN or an infinity anywhere makes the test fail)
-    const bool sure = rx > margin_x && rx < 1.0 - margin_x && ry > margin_y && ry < 1.0 - margin_y &&
-                      fx >= 0.0 && fx < side && fy >= 0.0 && fy < side;
-    if (!sure) return key_of<HILBERT>(x, y, x0, x1, y0, y1, Dm);
-    const uint32_t ix = (uint32_t)fx, iy = (uint32_t)fy;
     uint64_t k = 0;
     int state = 0;
     int l = Dm - 1;
@@ -218,6 +208,22 @@ __device__ __forceinline__ uint64_t key_of_fast(double x, double y, double x0, d
     return k;
 }
 
+template <bool HILBERT>
+__device__ __forceinline__ uint64_t key_of_fast(double x, double y, double x0, double x1, double y0, double y1, int Dm,
+                                                double scale_x, double scale_y, double margin_x, double margin_y,
+                                                const uint8_t *hil3 = nullptr)
+{
+    const double side = (double)(1u << Dm);
+    const double tx = (x - x0) * scale_x, ty = (y - y0) * scale_y;
+    const double fx = floor(tx), fy = floor(ty);
+    const double rx = tx - fx, ry = ty - fy;
+    // (written so that a NaN or an infinity anywhere makes the test fail)
+    const bool sure = rx > margin_x && rx < 1.0 - margin_x && ry > margin_y && ry < 1.0 - margin_y &&
+                      fx >= 0.0 && fx < side && fy >= 0.0 && fy < side;
+    if (!sure) return key_of<HILBERT>(x, y, x0, x1, y0, y1, Dm);
+    return curve_key<HILBERT>((uint32_t)fx, (uint32_t)fy, Dm, hil3);
+}
+
 // PACK: the body index is written into bits 40..63 of the key word instead of the index array (bh_sort.hpp).
 // samples != nullptr (bucket sort, bh_sort.hpp): ns / 64 extra workgroups produce the nb (256 or 1,024) splitters
 // of this build -- the keys, in THIS build's box, of the positions that stood at the ranks j * n / nb of the previous
@@ -232,10 +238,14 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
                                                        uint64_t *__restrict__ splitters = nullptr, int nb = 0,
                                                        int ns = 0, double *slots = nullptr, TreeCounters *ctr = nullptr,
                                                        uint32_t *__restrict__ zero_words = nullptr, int n_zero = 0,
-                                                       const uint32_t *__restrict__ sample_perm = nullptr, int from_walk = 0)
+                                                       const uint32_t *__restrict__ sample_perm = nullptr, int from_walk = 0,
+                                                       SortDirect sd = SortDirect{})
 {
-    if (blockIdx.x == 0)                                         // (the bucket totals the histogram launch adds into: bh_sort.hpp)
+    if (blockIdx.x == 0) {                                       // (the bucket totals the histogram launch adds into: bh_sort.hpp)
         for (int k = threadIdx.x; k < n_zero; k += kBlock) zero_words[k] = 0u;
+        if (sd.count_next != nullptr)                            // (this build counts into sd.count)
+            for (int k = threadIdx.x; k <= sd.nsub; k += kBlock) sd.count_next[kDirectStride * k] = 0u;
+    }
     // FROM_SLOTS (all but LET mode, whose box is in memory already): the bounds of the positions are in kBoundSlots
     // records (bh_bounds.hpp), from the previous walk (from_walk) or from bounds_partial.  Every workgroup reduces them and
     // pads the box (project.cu:553-570), workgroup 0 also writes it out and clears the step's counters for the kernels that
@@ -292,6 +302,30 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
     }
     // (sample_perm: the exact modes keep no sorted copy of the positions -- their samples are pos[previous build's perm[rank]])
     const int nsb = (samples != nullptr || sample_perm != nullptr) ? ns / kWave : 0;      // extra workgroups in front of the key workgroups
+    __shared__ uint8_t s_hil3[HILBERT ? 256 : 1];
+    if (HILBERT) {
+        static_assert(kBlock == 256, "one table entry per thread");
+        s_hil3[threadIdx.x] = (uint8_t)hilbert3_entry(threadIdx.x);
+        __syncthreads();
+    }
+    // direct input of the bucket sort (bh_sort.hpp): range key j is the key of the body at j * L, by one multiply per axis in
+    // the box's precomputed scale, clamped into the box.  The first sample workgroup forms all of them and a key workgroup
+    // the few around its own bodies: the same statement on the same operands, the same bits.
+    const bool direct = PACK && sd.count != nullptr;
+    // (in two halves, so that a key workgroup has the position on its way while it forms its bodies' own keys)
+    auto range_has_body = [&](uint32_t j) -> bool { return j > 0u && j < (uint32_t)nb && (int64_t)j * sd.len < n; };
+    auto range_key_at = [&](uint32_t j, bool has_body, Real2 pp) -> uint64_t {
+        if (!has_body) return (j == 0u) ? 0ull : kRangeKeyInf;
+        const double side = (double)(1u << Dm), top = side - 1.0;
+        const double sx = (bk4 > 0.0) ? bk4 : side / (x1 - x0), sy = (bk5 > 0.0) ? bk5 : side / (y1 - y0);
+        const double fx = fmin(fmax(((double)pp.x - x0) * sx, 0.0), top);
+        const double fy = fmin(fmax(((double)pp.y - y0) * sy, 0.0), top);
+        return curve_key<HILBERT>((uint32_t)(int)fx, (uint32_t)(int)fy, Dm, HILBERT ? s_hil3 : nullptr);
+    };
+    auto range_key = [&](uint32_t j) -> uint64_t {
+        const bool has_body = range_has_body(j);
+        return range_key_at(j, has_body, has_body ? pos[(int64_t)j * sd.len] : Real2{});
+    };
     if ((int)blockIdx.x < nsb) {
         // ns sample positions -> keys -> ranks by counting -> every (ns / nb)-th in rank order is a splitter.
         // Every one of the ns / 64 sample workgroups forms all ns keys (cheap: one multiply per axis with the
@@ -301,6 +335,16 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
         // re-keyed samples are only as good as random ones; the largest bucket decides bucket_sort_kernel's time.)
         __shared__ uint64_t sk[kMaxSplitSamples];
         const int t = threadIdx.x;
+        if (direct && blockIdx.x == 0) {
+            // all nb range keys, for bucket_sort_kernel; out of order anywhere (a body at a range start overtook the one at
+            // the next): they are no splitters, this build takes the counting pass
+            for (int j = t; j < nb; j += kBlock) { const uint64_t v = range_key((uint32_t)j); sk[j] = v; sd.range_keys[j] = v; }
+            __syncthreads();
+            int bad = 0;
+            for (int j = t; j + 1 < nb; j += kBlock) bad |= (sk[j] > sk[j + 1]) ? 1 : 0;
+            bad = __syncthreads_or(bad);
+            if (bad && t == 0) sd.count[0] = 1u;
+        }
         // (a sample workgroup shares its CU with key workgroups, so its time is its instruction count: ns, nb are
         // powers of two -- shifts, not divisions.  All Dm levels: when close encounters have blown the root box up,
         // the bodies sit in a corner of it that 12 levels do not resolve, every splitter would be the same key
@@ -349,20 +393,63 @@ __global__ __launch_bounds__(kBlock) void keys_kernel(const Real2 *__restrict__ 
         if (part == 0 && (rank & ((1 << lg_os) - 1)) == 0) splitters[rank >> lg_os] = tagged >> 11;
         return;
     }
-    __shared__ uint8_t s_hil3[HILBERT ? 256 : 1];
-    if (HILBERT) {
-        static_assert(kBlock == 256, "one table entry per thread");
-        s_hil3[threadIdx.x] = (uint8_t)hilbert3_entry(threadIdx.x);
-        __syncthreads();
+    const int64_t i0 = ((int64_t)blockIdx.x - nsb) * kBlock;
+    const int64_t i = i0 + threadIdx.x;
+    __shared__ uint64_t s_rk[kBlock + 2];                        // direct: range keys b0 .. of the ranges this workgroup's bodies lie in
+    uint32_t b0 = 0, need = 0;
+    Real2 range_pos{};
+    bool range_body = false;
+    if (direct) {
+        b0 = (uint32_t)i0 / sd.len;                              // (the launch holds at most 2^22 bodies)
+        const int64_t last = ((i0 + kBlock < n) ? i0 + kBlock : n) - 1;
+        need = (uint32_t)last / sd.len - b0 + 1u;                // entries 0 .. need of s_rk (need <= kBlock)
+        range_body = threadIdx.x <= need && range_has_body(b0 + threadIdx.x);
+        if (range_body) range_pos = pos[(int64_t)(b0 + threadIdx.x) * sd.len];
+    } else if (i >= n) {
+        return;
     }
-    const int64_t i = ((int64_t)blockIdx.x - nsb) * kBlock + threadIdx.x;
-    if (i >= n) return;
     // (round 4: the exact modes take the one-multiply look-up too -- the proof is about the bisection's comparisons, not about the
     // order of the digits; bodies it cannot vouch for fall back to key_of, the reference's four-test DetermineChild)
-    const uint64_t k = key_of_fast<HILBERT>((double)pos[i].x, (double)pos[i].y, x0, x1, y0, y1, Dm, bk4, bk5, bk6, bk7,
-                                            HILBERT ? s_hil3 : nullptr);
+    uint64_t k = 0;
+    if (i < n) k = key_of_fast<HILBERT>((double)pos[i].x, (double)pos[i].y, x0, x1, y0, y1, Dm, bk4, bk5, bk6, bk7,
+                                        HILBERT ? s_hil3 : nullptr);
+    if (direct) {
+        if (threadIdx.x <= need) s_rk[threadIdx.x] = range_key_at(b0 + threadIdx.x, range_body, range_pos);
+        if (need == (uint32_t)kBlock && threadIdx.x == 0) s_rk[kBlock] = range_key(b0 + kBlock);   // (ranges of one body)
+        __syncthreads();
+        if (i >= n) return;
+    }
     if (PACK) {
-        keys[i] = k | ((uint64_t)i << kPackShift);
+        const uint64_t word = k | ((uint64_t)i << kPackShift);
+        keys[i] = word;
+        if (direct) {
+            // the bucket of the index, by a multiply (off < kBlock + L <= 2^13: exact in fp32, the quotient off by one at most)
+            const uint32_t off = (uint32_t)(i - (int64_t)b0 * sd.len);
+            uint32_t q = (uint32_t)((float)off * (1.0f / (float)sd.len));
+            if (q * sd.len > off) --q; else if ((q + 1u) * sd.len <= off) ++q;
+            // A crosser goes to one of nsub lists, each behind a counter of its own -- by the number of its wave, so that the
+            // crossers of neighbouring waves queue at different words (atomics on ONE word cost the kernel ~3.5 ns each:
+            // DESIGN.md section 3) --, a wave's crossers share one atomic, and nobody adds anything once the decision for the
+            // counting pass is taken: a list is full, or half a wave crosses at once (bodies in disorder).
+            const bool cross = !stays_in(k, s_rk[q], s_rk[q + 1u]);
+            const uint64_t who = __ballot(cross);
+            if (who != 0ull) {                                   // (uniform)
+                const uint32_t mine = (uint32_t)__popcll(who);
+                const uint32_t sub = ((uint32_t)(i0 >> 6) + (uint32_t)wave_id()) & (uint32_t)(sd.nsub - 1);
+                uint32_t *ctr = sd.count + kDirectStride * (1u + sub);
+                const int leader = __ffsll((unsigned long long)who) - 1;
+                uint32_t base = ~0u;
+                if (lane_id() == leader && mine <= (uint32_t)kWave / 2u && sd.count[0] == 0u &&
+                    __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= sd.subcap)
+                    base = atomicAdd(ctr, mine);
+                base = (uint32_t)__shfl((int)base, leader);
+                if (base == ~0u || base + mine > sd.subcap) {
+                    if (lane_id() == leader && sd.count[0] == 0u) sd.count[0] = 1u;   // (every writer writes the same word)
+                } else if (cross) {
+                    sd.list[(size_t)sub * sd.subcap + base + (uint32_t)__popcll(who & ((1ull << lane_id()) - 1ull))] = word;
+                }
+            }
+        }
     } else {
         keys[i] = k;
         idx[i] = (uint32_t)i;
