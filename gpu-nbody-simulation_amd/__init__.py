@@ -6,7 +6,7 @@ reference's text formats (`textio`), its step-loop entry points under their own 
 and the one-process-per-GPU driver (`distributed`).  There is no CPU fallback: without the HIP
 library and a GPU, every compute entry point raises.
 """
-from .engine import (BarnesHutEngine, BhConfig, BhError, BhForceError, BhGroups, BhLagrangian, BhMomentMap, BhPairCounts, BhRadialProfile,  # noqa: F401
+from .engine import (BarnesHutEngine, BhConfig, BhError, BhForceError, BhGroups, BhLagrangian, BhMomentMap, BhPairCounts, BhRadialProfile, BhSortSnapshot,  # noqa: F401
                      BhTimestep, LagrangianSelect, Precision, correlation_from, density_centre_from, force_error_stats, lagrangian_from,
                      local_density_from, radial_edges, radial_exponents, radial_profile_from_planes)
 from .textio import loadSimulationDataFromText, save_init_files  # noqa: F401
@@ -14,4 +14,4 @@ from .textio import loadSimulationDataFromText, save_init_files  # noqa: F401
 __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups", "BhMomentMap", "BhTimestep", "Precision",
            "force_error_stats", "local_density_from", "density_centre_from", "loadSimulationDataFromText", "save_init_files",
            "BhRadialProfile", "BhLagrangian", "LagrangianSelect", "radial_edges", "radial_exponents",
-           "radial_profile_from_planes", "lagrangian_from", "BhPairCounts", "correlation_from"]
+           "radial_profile_from_planes", "lagrangian_from", "BhPairCounts", "correlation_from", "BhSortSnapshot"]

@@ -143,6 +143,8 @@ SIGNATURES = {
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),
+    "bh_sort_snapshot": (C.c_int, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "bh_set_owned_fraction": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "bh_device_state": (C.c_int, [_ctx, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -89,7 +89,16 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     uint32_t direct_cap = 0, direct_subcap = 0;
     int direct_nsub = 1;
     int direct_slot = 0;                  // the counter the next build counts into (zero by then)
-    int build_items = 0;           // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
+    // what the last build's sort was given (bh_sort_snapshot): direct_slot has been flipped by the time anybody asks.
+    // offered: direct input was offered, and `count` is the block that build counted into; the output is keys_sorted / perm
+    struct SortRecord {
+        bool valid = false, offered = false;
+        int64_t n = 0;
+        int nb = 0, nsub = 0;
+        uint32_t len = 0, cap = 0, subcap = 0;
+        const uint32_t *count = nullptr;
+    } sort_rec;
+    int build_items = 0;          // 0 = automatic, else keys per thread in the sort / scan kernels (2, 4, 8)
     bool hilbert = false;                // fp32 mode: Hilbert-ordered keys (BH_HILBERT=0 disables, A/B)
     bool chain_collapse = true;          // fp32 step build: slots link past single-child cell chains (BH_CHAIN_COLLAPSE=0 disables, A/B)
     double *bslots = nullptr;      // kBoundSlots running bounds records (bh_bounds.hpp)
@@ -516,6 +525,7 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
         }
         c->keys_sorted = c->keys[cur];
         c->perm = c->vals[cur];
+        c->sort_rec = bh_ctx::SortRecord{true, direct, n, nb, direct ? sd.nsub : 0, sd.len, sd.cap, sd.subcap, sd.count};
         if constexpr (!TREE64) {
             if (may_reorder && c->reorder_every > 0 && c->carry.builds % c->reorder_every == 0) {
                 hipLaunchKernelGGL((reorder_state_kernel<Real2, Real>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, st,
@@ -568,6 +578,8 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
                                c->vals[0], n, Dm, nullptr, nullptr, 0, 0, slots, c->ctr);
         c->keys_sorted = c->keys[0];
         c->perm = c->vals[0];
+        c->sort_rec = bh_ctx::SortRecord{};
+        c->sort_rec.valid = true;
         if (time_groups) for (auto e : c->ev_grp) (void)hipEventRecord(e, st);
     }
 
@@ -2989,6 +3001,35 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
         out->build_bytes = (uint64_t)c->n * (keys_b + sort_b + prep_b + scan_b + nodes_b);
         out->walk_bytes = out->wave_nodes ? (uint64_t)c->n * 44u + out->wave_nodes * 20u : 0u;
     }
+    return BH_OK;
+}
+
+// What the last build's sort was given, decided and wrote: plain copies after a wait, no launch, no event of the run state.
+// Nothing between the sort and the next build writes keys[0] of a build that was offered direct input (its output is keys[1] /
+// vals[1], the counting pass scatters into keys_scatter); bh_migrate_pack does, and a LET context is refused for it.
+int bh_sort_snapshot(bh_ctx *c, int64_t info[8], uint32_t *decision, uint64_t *range_keys, uint64_t *list, uint64_t *keys_in,
+                     uint64_t *keys_sorted, uint32_t *perm)
+{
+    if (!c || !info) return fail(c, BH_ERR_ARG, "bh_sort_snapshot: null argument");
+    if (c->let_mode) return fail(c, BH_ERR_STATE, "bh_sort_snapshot: not in LET mode (bh_migrate_pack reuses the sort's buffers)");
+    if (!c->is.tree_valid || !c->sort_rec.valid) return fail(c, BH_ERR_STATE, "bh_sort_snapshot: no build to report (build a tree first)");
+    BH_HIP(c, hipSetDevice(c->device));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    const bh_ctx::SortRecord &r = c->sort_rec;
+    const int64_t out[8] = {r.offered ? 1 : 0, r.n, r.nb, (int64_t)r.len, (int64_t)r.cap, (int64_t)r.subcap, r.nsub, kDirectSubs};
+    for (int k = 0; k < 8; ++k) info[k] = out[k];
+    const size_t n = (size_t)r.n;
+    if (n > 0 && keys_sorted) BH_HIP(c, hipMemcpy(keys_sorted, c->keys_sorted, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (n > 0 && perm) BH_HIP(c, hipMemcpy(perm, c->perm, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!r.offered) return BH_OK;
+    if (decision) {
+        std::vector<uint32_t> block((size_t)kDirectCounterWords);
+        BH_HIP(c, hipMemcpy(block.data(), r.count, block.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int k = 0; k <= kDirectSubs; ++k) decision[k] = block[(size_t)kDirectStride * (size_t)k];
+    }
+    if (range_keys) BH_HIP(c, hipMemcpy(range_keys, c->direct_range_keys, (size_t)r.nb * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (list) BH_HIP(c, hipMemcpy(list, c->direct_list, (size_t)r.nsub * r.subcap * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (keys_in) BH_HIP(c, hipMemcpy(keys_in, c->keys[0], n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return BH_OK;
 }
 

@@ -406,6 +406,26 @@ def pair_counts_from(raw, edges, n_bodies: int, n_points=None, evals=None) -> Bh
                         None if n_points is None else int(n_points), None if evals is None else int(evals), np.cumsum(raw[:-1]))
 
 
+@dataclass
+class BhSortSnapshot:
+    """What the sort of the most recent build was given, decided and wrote (sort_snapshot).  The last six
+    arrays are None unless direct input was offered to that build."""
+    offered: bool                # direct input was offered (the device then decided: `counting`)
+    n: int
+    nb: int                      # buckets; bucket b is the range [b L, (b + 1) L) of keys_in
+    L: int
+    cap: int                     # T: most crossers in all
+    subcap: int                  # room of one list
+    nsub: int                    # lists
+    keys_sorted: np.ndarray      # (n,) uint64: the sort's output (offered: the 40 key bits)
+    perm: np.ndarray             # (n,) uint32: the slot each sorted key came from
+    decision: np.ndarray | None = None     # (65,) uint32: word 0, then the 64 list counters of that build
+    range_keys: np.ndarray | None = None   # (nb,) uint64
+    lists: np.ndarray | None = None        # (nsub, subcap) uint64: the listed packed keys (counter s of them valid in list s)
+    keys_in: np.ndarray | None = None      # (n,) uint64: key | slot << 40 in state order, as keys_kernel left them
+    counting: bool | None = None           # the decision of direct_total on `decision`: the counting pass ran
+
+
 def correlation_from(dd, dr, n: int, n_r: int) -> np.ndarray:
     """The Davis-Peebles estimate xi_k = (n_r / (n - 1)) * (2 * dd_k / dr_k) - 1 of the two-point correlation from the
     unordered auto counts dd of n bodies and the cross counts dr of n_r random points against them; NaN where dr_k = 0."""
@@ -1006,6 +1026,28 @@ class BarnesHutEngine:
                        s.wave_nodes, s.last_step_ms, s.build_ms, s.walk_ms, s.device_bytes, s.keys_ms, s.sort_ms,
                        s.scan_ms, s.nodes_ms, s.build_bytes, s.walk_bytes, s.wave_quads, s.sort_spill_buckets,
                        s.let_tree_ms, s.let_pack_ms, s.sort_rerun_buckets, s.wave_accepts, s.walk_launches)
+
+    def sort_snapshot(self) -> BhSortSnapshot:
+        """The most recent build's sort (bh_sort_snapshot): whether direct input was offered, its geometry, the 65 decision
+        words, range keys, crosser lists and input keys of that build, and its output.  Waits, then copies: the run is not
+        perturbed."""
+        info = (C.c_int64 * 8)()
+        none = [None] * 6
+        self._check(self._lib.bh_sort_snapshot(self._h, info, *none))
+        offered, n, nb, L, cap, subcap, nsub, words = (int(v) for v in info)
+        u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        ks, pm = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+        if not offered:
+            self._check(self._lib.bh_sort_snapshot(self._h, info, None, None, None, None, ks.ctypes.data_as(u64), pm.ctypes.data_as(u32)))
+            return BhSortSnapshot(False, n, nb, L, cap, subcap, nsub, ks[:n], pm[:n])
+        dec, rk = np.zeros(1 + words, dtype=np.uint32), np.zeros(nb, dtype=np.uint64)
+        lst, kin = np.zeros(max(nsub * subcap, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(self._lib.bh_sort_snapshot(self._h, info, dec.ctypes.data_as(u32), rk.ctypes.data_as(u64), lst.ctypes.data_as(u64),
+                                               kin.ctypes.data_as(u64), ks.ctypes.data_as(u64), pm.ctypes.data_as(u32)))
+        held = dec[1:1 + nsub].astype(np.int64)
+        counting = bool(dec[0] != 0 or (held > subcap).any() or held.sum() > cap)
+        return BhSortSnapshot(True, n, nb, L, cap, subcap, nsub, ks[:n], pm[:n], dec, rk, lst[:nsub * subcap].reshape(nsub, subcap),
+                              kin[:n], counting)
 
     def step_times(self):
         """(step_ms[k], walk_ms[k]) of the steps of the last step() call (at most 4,096): HIP events per step."""

@@ -616,6 +616,21 @@ int bh_stats(bh_ctx *ctx, bh_stats_t *out);
  * context's stream.  The reference accumulates one total per run (project.cu:985-1007); a spread needs the steps.
  * *n_out receives the number of steps available even when cap is too small; step_ms / walk_ms may be NULL. */
 int bh_step_times(bh_ctx *ctx, double *step_ms, double *walk_ms, int32_t cap, int32_t *n_out);
+/* What the sort of the most recent tree build (of a step, bh_build_tree, or a diagnostic's quiet build) was given, decided and
+ * wrote -- for tests of the bucket sort's direct input.  Waits for the stream, then plain copies: no
+ * launch, nothing a step or bh_stats reads is touched, a following bh_step is bit for bit what it would have been.
+ * info = {offered, n, nb, L, T, room of one list, lists, counter words that follow word 0 (64)}: offered = 1 when direct input was
+ *   offered to that build (the device then decided per its counters); n bodies in nb buckets, bucket b the range [b L, (b + 1) L).
+ * Every array may be NULL.  keys_sorted[n], perm[n]: the sort's output as the later kernels read it (a build that was offered
+ *   direct input: the 40 key bits, and the slot each came from).  Only when offered = 1, untouched otherwise:
+ *   decision[65]: word 0 (non-zero: the counting pass was ordered outright) and the 64 list counters of the block that build
+ *     counted into; range_keys[nb]; list[lists * room]: list s at s * room; keys_in[n]: the packed keys in state order,
+ *     key | slot << 40, as keys_kernel left them.
+ * Call it with NULL arrays first to learn the sizes.
+ * Errors: BH_ERR_STATE without a valid tree (before the first build, after bh_upload, bh_drift, bh_migrate_pack) and in LET mode,
+ *   where bh_migrate_pack reuses the buffers. */
+int bh_sort_snapshot(bh_ctx *ctx, int64_t info[8], uint32_t *decision, uint64_t *range_keys, uint64_t *list, uint64_t *keys_in,
+                     uint64_t *keys_sorted, uint32_t *perm);
 
 /* --- multi-GPU plumbing -----------------------------------------------------------------
  * The reference is single-GPU.  One process per GPU owns a contiguous range [lo, hi) of

@@ -1,119 +1,26 @@
 """The bucket sort's direct input (csrc/bh_sort.hpp) on the device: bit for bit the counting pass, bit for
-bit the LSD passes.
+bit the LSD passes, and the path every build took pinned to the numpy twin.
 
-Every case runs the same bodies three times -- BH_SORT_BUCKET=2 with the direct input under test, BH_SORT_BUCKET=2 with
-BH_SORT_DIRECT=0 (the counting pass every time) and BH_SORT_BUCKET=0 (the LSD passes) -- and compares the exported tree of a
-later build and the downloaded positions and velocities with ==.  N is between 8,200 and 20,000, so with 256 buckets a range
-holds 33 to 79 keys and every workgroup of bucket_sort_kernel has work.
-
-The bodies sit on a jittered lattice with tiny masses: they do not move by themselves ("frozen"), and the state order the
-first build leaves (the state is re-ordered at build 0) can be read back slot by slot.  The cases therefore know which bodies
-stand at range starts, move only others -- the range keys stay in order, the direct path is taken for as long as the crosser
-list holds -- and know which bucket a mover lands in: it is sent next to the body of a chosen slot."""
+The harness is tests/sort_direct_case.py: every case runs the same bodies three times and compares trees and state with ==, and
+the build whose tree is exported is snapshotted -- the decision the device took, its list counters, the listed words and the
+range keys are the twin's for the keys the device formed, and the sort's output is numpy's stable sort of them.  What a case's
+docstring says about the path its build takes is asserted (path, k = crossers, why = the rule that sends it to the counting
+pass).  N is between 8,200 and 20,000, so with 256 buckets a range holds 33 to 79 keys and every workgroup of bucket_sort_kernel
+has work.  The decision's edges, the pile-ups and the range-length edges are in tests/test_gpu_sort_direct_edges.py."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 import gpu_nbody_simulation_amd as G  # noqa: E402
-
-NB = 256
-
-
-def f32(a):
-    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
-
-
-def lattice(n, seed):
-    """n bodies on a jittered square lattice in [-1, 1]^2 (one body per lattice cell: positions identify bodies), masses that
-    move nobody within a few steps"""
-    rng = np.random.default_rng(seed)
-    side = int(np.ceil(np.sqrt(n)))
-    cells = rng.permutation(side * side)[:n]
-    h = 2.0 / side
-    p = np.stack([(cells % side + 0.5) * h - 1.0, (cells // side + 0.5) * h - 1.0], axis=1) + rng.uniform(-0.2 * h, 0.2 * h, (n, 2))
-    return f32(rng.uniform(1e-9, 2e-9, n)), f32(p), np.zeros((n, 2)), side
-
-
-def engine(n, precision=G.Precision.F32, **kw):
-    kw.setdefault("max_depth", 21)
-    kw.setdefault("reference_compat", False)
-    return G.BarnesHutEngine(G.BhConfig(capacity=n, precision=precision, **kw))
-
-
-def state_order(m, p, side, precision=G.Precision.F32):
-    """slot -> caller index after the first build of these bodies at rest (read from the device's state arrays)"""
-    import ctypes
-    n = len(m)
-    with engine(n, precision=precision) as e:
-        e.upload(p, np.zeros((n, 2)), m)
-        e.step(1)
-        e.sync()
-        ptr = e.device_state()[0]
-        sp = np.empty((n, 2), dtype=np.float32 if precision == G.Precision.F32 else np.float64)
-        hip = ctypes.CDLL("libamdhip64.so")                         # (already in the process: libbhgpu links it)
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert hip.hipMemcpy(sp.ctypes.data, ptr, sp.nbytes, 2) == 0  # 2 = device to host
-        sp = sp.astype(np.float64)
-    cell = lambda q: (np.floor((q[:, 1] + 1.0) * side / 2.0).astype(np.int64) * side + np.floor((q[:, 0] + 1.0) * side / 2.0).astype(np.int64))
-    where = {c: i for i, c in enumerate(cell(p))}
-    assert len(where) == n
-    order = np.array([where[c] for c in cell(sp)])
-    assert np.array_equal(np.sort(order), np.arange(n))
-    return order
-
-
-def run(monkeypatch, env, m, p, v, steps, precision=G.Precision.F32, **kw):
-    for k in ("BH_SORT_BUCKET", "BH_SORT_DIRECT", "BH_SORT_DIRECT_MAX", "BH_REORDER_EVERY"):
-        monkeypatch.delenv(k, raising=False)
-    for k, val in env.items():
-        monkeypatch.setenv(k, val)
-    n = len(m)
-    with engine(n, precision=precision, **kw) as e:
-        e.upload(p, v, m)
-        e.step(steps)
-        e.build_tree()
-        nodes, depth = e.export_tree()
-        e.step(1)
-        pos, vel = e.download()[:2]
-        st = e.stats()
-    return nodes, depth, pos, vel, st
-
-
-def compare(monkeypatch, m, p, v, steps, direct="1", extra=None, **kw):
-    extra = extra or {}
-    new = run(monkeypatch, dict(BH_SORT_BUCKET="2", BH_SORT_DIRECT=direct, **extra), m, p, v, steps, **kw)
-    reorder = {k: val for k, val in extra.items() if k == "BH_REORDER_EVERY"}
-    old = run(monkeypatch, dict(BH_SORT_BUCKET="2", BH_SORT_DIRECT="0", **reorder), m, p, v, steps, **kw)
-    lsd = run(monkeypatch, dict(BH_SORT_BUCKET="0", **reorder), m, p, v, steps, **kw)
-    for other in (old, lsd):
-        for x, y in zip(new[:4], other[:4]):
-            if x.dtype.names:
-                for f in x.dtype.names:
-                    assert np.array_equal(x[f], y[f], equal_nan=True), f
-            else:
-                assert np.array_equal(x, y)
-    assert np.isfinite(new[2]).all() and np.isfinite(new[3]).all()
-    return new[4], old[4]
-
-
-def send(p, v, order, movers, targets, steps):
-    """the bodies of the slots `movers` travel to just beside the bodies of the slots `targets` in `steps` steps (dt = 1)"""
-    v = v.copy()
-    for a, b in zip(movers, targets):
-        v[order[a]] = f32((p[order[b]] + 1e-4 - p[order[a]]) / steps)
-    return v
-
-
-def off_starts(slots, L):
-    """the slots, each moved on by one where it is a range start"""
-    return [s + 1 if s % L == 0 else s for s in slots]
+from sort_direct_case import NB, compare, hull_slots, lattice, off_starts, send, state_order  # noqa: E402
 
 
 def test_frozen_bodies_have_no_crosser(monkeypatch):
     m, p, v, _ = lattice(9001, 1)
-    new, old = compare(monkeypatch, m, p, v, 3)
-    assert new.sort_spill_buckets == 0 and old.sort_spill_buckets == 0
+    c = compare(monkeypatch, m, p, v, 3, path="direct", k=0)
+    assert c.new.sort_spill_buckets == 0 and c.old.sort_spill_buckets == 0
+    assert not c.snap.decision.any()
 
 
 def test_a_dozen_bodies_cross_the_domain(monkeypatch):
@@ -129,8 +36,9 @@ def test_a_dozen_bodies_cross_the_domain(monkeypatch):
                          150 * L + 13, 249 * L + 3], L)
     targets = [120 * L + 4, 120 * L + 9, 120 * L + 14, 120 * L + 19, 2, 5, n - 3, n - 6, 230 * L + 8, 20 * L + 8, 60 * L + 8, 9 * L + 8]
     v = send(p, v, order, movers, targets, 3)
-    compare(monkeypatch, m, p, v, 3)
-    compare(monkeypatch, m, p, v, 1)                            # (the build that is compared is the first with crossers)
+    compare(monkeypatch, m, p, v, 3, path="direct", k=12)       # (all twelve have arrived, each in another bucket than its own)
+    c = compare(monkeypatch, m, p, v, 1, path="direct")         # (the build that is compared is the first with crossers)
+    assert 1 <= c.twin.k <= 12                                  # (a third of the way: nobody else can have left its range)
 
 
 @pytest.mark.parametrize("movers", [8, 9])
@@ -144,7 +52,9 @@ def test_both_sides_of_the_capacity(monkeypatch, movers):
     src = off_starts([11 + 25 * L * k for k in range(movers)], L)
     dst = [(s + 120 * L) % n for s in src]
     v = send(p, v, order, src, dst, 4)
-    compare(monkeypatch, m, p, v, 3, extra=dict(BH_SORT_DIRECT_MAX="8"))
+    want = dict(path="direct", why=()) if movers == 8 else dict(path="counting", why=("total",))
+    c = compare(monkeypatch, m, p, v, 3, extra=dict(BH_SORT_DIRECT_MAX="8"), k=movers, **want)
+    assert (c.snap.cap, c.snap.subcap, c.snap.nsub) == (8, 16, 64)
 
 
 def test_a_third_of_the_bodies_cross_with_the_list_sized_for_all(monkeypatch):
@@ -158,23 +68,30 @@ def test_a_third_of_the_bodies_cross_with_the_list_sized_for_all(monkeypatch):
     src = np.array([s for s in range(n) if s % 3 == 1 and s % L != 0])
     dst = rng.permutation(src)
     v = send(p, v, order, src, dst, 4)
-    compare(monkeypatch, m, p, v, 3, direct="2")
-    compare(monkeypatch, m, p, v, 1, direct="2")
+    c = compare(monkeypatch, m, p, v, 3, direct="2", path="direct")
+    assert c.twin.k > n // 4 and (c.snap.cap, c.snap.subcap, c.snap.nsub) == (n, n, 1)
+    compare(monkeypatch, m, p, v, 1, direct="2", path="direct")
 
 
 def test_a_body_flung_far_moves_the_root_box(monkeypatch):
     """One body leaves at 40 box widths per step: the root box jumps, every key changes and so does the order along the curve --
     range keys out of order or crossers by the thousand, the builds take the counting pass, whatever the list holds; the same
-    body coming to rest inside the hull (second run: it only crosses the box) leaves the later builds on the direct path."""
+    body on its way across the box -- inside the hull at every build, and not one of the bodies that carry the root box --
+    leaves the later builds on the direct path, with one crosser.  (Sent to arrive in two steps, as this case first had it, the
+    body is twice as far at the fourth and outside the hull: the box grows, the range keys fall out of order, and those builds
+    take the counting pass too -- the snapshot says so.)"""
     n = 12000
     m, p, v, side = lattice(n, 6)
     order = state_order(m, p, side)
     L = (n + NB - 1) // NB
     far = v.copy()
     far[order[50 * L + 3]] = [80.0, 55.0]
-    compare(monkeypatch, m, p, far, 4)
-    compare(monkeypatch, m, p, far, 4, direct="2")
-    compare(monkeypatch, m, p, send(p, v, order, [50 * L + 3], [200 * L + 3], 2), 4)
+    compare(monkeypatch, m, p, far, 4, path="counting")
+    compare(monkeypatch, m, p, far, 4, direct="2", path="counting")
+    compare(monkeypatch, m, p, send(p, v, order, [50 * L + 3], [200 * L + 3], 2), 4, path="counting")
+    hull = hull_slots(p, order)
+    mover = next(s for s in range(50 * L + 3, 51 * L) if s not in hull)
+    compare(monkeypatch, m, p, send(p, v, order, [mover], [200 * L + 3], 6), 4, path="direct", k=1)
 
 
 def test_coincident_bodies_on_a_range_boundary(monkeypatch):
@@ -192,8 +109,12 @@ def test_coincident_bodies_on_a_range_boundary(monkeypatch):
         p[order[s]] = p[order[90 * L]]
     v2 = send(p, v, order, [60 * L + 2, 90 * L + 5], [10 * L + 5, 200 * L + 7], 3)
     for direct in ("1", "2"):
-        compare(monkeypatch, m, p, v, 3, direct=direct, softening=1e-3)
-        compare(monkeypatch, m, p, v2, 3, direct=direct, softening=1e-3)
+        # (the path is whatever the twin says for the keys the device formed; a run of more than eight equal keys in a bucket
+        # that spans more than 24 bits sends its workgroup through the LDS sort's re-run -- on the direct path from a buffer
+        # that IS the input)
+        for vel in (v, v2):
+            c = compare(monkeypatch, m, p, vel, 3, direct=direct, softening=1e-3)
+            assert c.new.sort_rerun_buckets > 0 and c.rise.reruns > 0
 
 
 def test_reordering_every_second_build(monkeypatch):
@@ -203,6 +124,7 @@ def test_reordering_every_second_build(monkeypatch):
     L = (n + NB - 1) // NB
     src = off_starts([9 + 13 * L * k for k in range(15)], L)
     v = send(p, v, order, src, [(s + 97 * L) % n for s in src], 6)
+    # (a re-ordering may leave a mover at a range start: the path is the twin's for the keys the device formed)
     compare(monkeypatch, m, p, v, 5, extra=dict(BH_REORDER_EVERY="2"))
     compare(monkeypatch, m, p, v, 5, direct="2", extra=dict(BH_REORDER_EVERY="2"))
 
@@ -217,7 +139,7 @@ def test_ranges_of_unequal_length(monkeypatch):
         last = ((n - 1) // L) * L
         src = off_starts([5, last + 1, 100 * L + 2, n - 1], L)
         v = send(p, v, order, src, [last + 2, 3, n - 2, 30 * L + 2], 3)
-        compare(monkeypatch, m, p, v, 3)
+        compare(monkeypatch, m, p, v, 3, path="direct", k=4)
 
 
 def test_mixed_precision(monkeypatch):
@@ -227,5 +149,5 @@ def test_mixed_precision(monkeypatch):
     L = (n + NB - 1) // NB
     src = off_starts([4, 33 * L + 2, 99 * L + 7, 170 * L + 1, 240 * L + 9], L)
     v = send(p, v, order, src, [200 * L + 3, 1, 98 * L + 1, 171 * L + 4, 12 * L + 2], 3)
-    compare(monkeypatch, m, p, v, 3, precision=G.Precision.MIXED)
-    compare(monkeypatch, m, p, v, 3, direct="2", precision=G.Precision.MIXED)
+    compare(monkeypatch, m, p, v, 3, precision=G.Precision.MIXED, path="direct", k=5)
+    compare(monkeypatch, m, p, v, 3, direct="2", precision=G.Precision.MIXED, path="direct", k=5)

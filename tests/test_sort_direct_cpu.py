@@ -1,113 +1,32 @@
-"""A numpy twin of the bucket sort's direct input (csrc/bh_sort.hpp, "direct input") against np.argsort(kind="stable").
-
-The twin follows the device code statement by statement: bucket b owns the array range [b * L, (b + 1) * L), L = ceil(n / nb);
-range key j is the key at j * L (0 for j = 0, "infinity" for a range that starts at or beyond n); a key stays iff
-range key b <= key < range key b + 1 -- which is bucket_of(key) == b while the range keys are in order --, every other key is
-a crosser, routed by bucket_of; a bucket's input is its arrivals from lower ranges, its stayers, its arrivals from higher
-ranges, each in body order; the bucket is sorted stably on the 40 key bits; its place in the output follows from what the
-buckets before it gained and lost.  Range keys out of order, or more crossers than the list holds: the counting pass, i.e.
-the stable order by bucket among the SORTED range keys and then the same sort of every bucket."""
+"""The numpy twin of the bucket sort's direct input (tests/sort_direct_ref.py: the algorithm and the device's decision rules are
+described there) against np.argsort(kind="stable"), the loop version against the vectorised one, and both sides of every rule
+of the decision."""
 import numpy as np
 import pytest
 
-PACK_SHIFT = 40
-KEY_MASK = (1 << PACK_SHIFT) - 1
-INF = np.uint64(0xFFFFFFFFFFFFFFFF)
+from sort_direct_ref import WAVE, direct_sort, direct_sort_fast, expect, pack
 
 
-def pack(keys40):
-    keys40 = np.asarray(keys40, dtype=np.uint64)
-    return keys40 | (np.arange(len(keys40), dtype=np.uint64) << np.uint64(PACK_SHIFT))
+def same(a, b):
+    """two Twins agree in everything"""
+    assert a.path == b.path and a.k == b.k and a.why == b.why and a.L == b.L
+    for f in ("out", "rk", "crossers", "below", "above", "left", "m"):
+        x, y = getattr(a, f), getattr(b, f)
+        assert (x is None) == (y is None), f
+        assert x is None or np.array_equal(x, y), f
 
 
-def bucket_of(key40, spl):
-    """largest j with spl[j] <= key: the device's binary search (spl in order, spl[0] = 0, len a power of two)"""
-    b, s = 0, len(spl) >> 1
-    while s >= 1:
-        b += s if spl[b + s] <= key40 else 0
-        s >>= 1
-    return b
-
-
-def range_keys(words, nb):
-    n = len(words)
-    L = (n + nb - 1) // nb
-    rk = np.full(nb, INF, dtype=np.uint64)
-    for j in range(nb):
-        if j == 0:
-            rk[j] = 0
-        elif j * L < n:
-            rk[j] = words[j * L] & np.uint64(KEY_MASK)
-    return rk, L
-
-
-def sort_bucket_stable(words):
-    """what bucket_sort_kernel does to one bucket's input: the stable order by the 40 key bits"""
-    words = np.asarray(words, dtype=np.uint64)
-    return words[np.argsort(words & np.uint64(KEY_MASK), kind="stable")]
-
-
-def direct_sort(words, nb, cap):
-    """-> (sorted packed words, 'direct' | 'counting', number of crossers or None)"""
-    words = np.asarray(words, dtype=np.uint64)
-    n = len(words)
-    rk, L = range_keys(words, nb)
-    in_order = bool(np.all(rk[:-1] <= rk[1:]))
-    key40 = words & np.uint64(KEY_MASK)
-    crossers = []
-    if in_order:
-        for i in range(n):
-            b = i // L
-            hi = rk[b + 1] if b + 1 < nb else INF
-            if not (rk[b] <= key40[i] < hi):
-                crossers.append(i)
-    if not in_order or len(crossers) > cap:
-        spl = np.sort(rk)
-        dest = np.array([bucket_of(k, spl) for k in key40], dtype=np.int64)
-        out = []
-        for b in range(nb):
-            out.append(sort_bucket_stable(words[dest == b]))               # (boolean mask: body order, as the stable scatter leaves it)
-        return np.concatenate(out), "counting", (len(crossers) if in_order else None)
-    # the direct path
-    dest = {i: bucket_of(key40[i], rk) for i in crossers}
-    for i, d in dest.items():
-        assert d != i // L                                                   # stays_in and bucket_of agree
-    gone = set(crossers)
-    out = np.empty(n, dtype=np.uint64)
-    starts = []
-    pos = 0
-    for b in range(nb):
-        r0, r1 = min(n, b * L), min(n, (b + 1) * L)
-        arrivals = sorted(i for i, d in dest.items() if d == b)
-        lower = [words[i] for i in arrivals if i < r0]
-        upper = [words[i] for i in arrivals if i >= r0]
-        stay = [words[i] for i in range(r0, r1) if i not in gone]
-        left = sum(1 for i in crossers if i // L == b)
-        assert len(stay) == (r1 - r0) - left
-        m = len(lower) + len(stay) + len(upper)
-        # the device's start: range start + net arrivals of the buckets before
-        net_before = sum(1 for i, d in dest.items() if d < b) - sum(1 for i in crossers if i // L < b)
-        assert r0 + net_before == pos
-        starts.append(pos)
-        out[pos:pos + m] = sort_bucket_stable(np.array(lower + stay + upper, dtype=np.uint64))
-        pos += m
-    assert pos == n
-    return out, "direct", len(crossers)
-
-
-def expect(words):
-    words = np.asarray(words, dtype=np.uint64)
-    return words[np.argsort(words & np.uint64(KEY_MASK), kind="stable")]
-
-
-def check(keys40, nb=256, cap=1 << 30, want=None):
+def check(keys40, nb=256, cap=1 << 30, want=None, subcap=None, nsub=1, half_wave=WAVE // 2):
     words = pack(keys40)
-    got, path, k = direct_sort(words, nb, cap)
-    assert np.array_equal(got, expect(words))
+    tw = direct_sort(words, nb, cap, subcap, nsub, half_wave)
+    same(tw, direct_sort_fast(words, nb, cap, subcap, nsub, half_wave))
+    assert np.array_equal(tw.out, expect(words))
     # (the body index in the word: equal keys must come out in body order, which array_equal on the words checks)
     if want is not None:
-        assert path == want, (path, k)
-    return path, k
+        assert tw.path == want, (tw.path, tw.k, tw.why)
+    if tw.path == "direct":
+        assert tw.below.sum() + tw.above.sum() == tw.left.sum() == tw.k == len(tw.crossers)
+    return tw.path, tw.k
 
 
 RNG = np.random.default_rng(17)
@@ -164,9 +83,11 @@ def test_all_keys_equal():
     for n in (4097, 9000):
         # every range key but the first is the one value: bucket_of sends every body to the LAST range that has that key,
         # and only the bodies of that range stay
-        path, k = check(np.full(n, 123456789, dtype=np.uint64), want="direct")
+        # (whole waves cross: the device's wave rule sends such a build to the counting pass; the routing is checked without it)
+        path, k = check(np.full(n, 123456789, dtype=np.uint64), want="direct", half_wave=WAVE)
         L = (n + 255) // 256
         assert k == ((n - 1) // L) * L
+        assert check(np.full(n, 123456789, dtype=np.uint64), want="counting") == ("counting", k)
 
 
 def test_runs_of_equal_keys_across_range_boundaries():
@@ -175,12 +96,18 @@ def test_runs_of_equal_keys_across_range_boundaries():
     keys = sorted_keys(n)
     keys[5 * L - 3:7 * L + 4] = keys[5 * L - 3]            # one value across two boundaries: range keys 5, 6 and 7 are equal
     keys[20 * L - 1:20 * L + 1] = keys[20 * L - 1]           # ... and a pair astride one
-    path, k = check(keys, want="direct")
+    # (2 L = 70 neighbours cross, more than half of some wave: routed without the wave rule, the counting pass with it)
+    path, k = check(keys, want="direct", half_wave=WAVE)
     assert k > 0                                              # (the run's bodies left of the last equal range key cross)
+    check(keys, want="counting")
     # the same with some of the run moved to the far end of the array
     keys2 = keys.copy()
     keys2[240 * L + 1:240 * L + 6] = keys[5 * L]
-    check(keys2, want="direct")
+    check(keys2, want="direct", half_wave=WAVE)
+    # a run short enough for the rule: a dozen equal keys astride one boundary
+    keys3 = sorted_keys(n)
+    keys3[30 * L - 6:30 * L + 6] = keys3[30 * L - 6]
+    assert check(keys3, want="direct") == ("direct", 6)
 
 
 @pytest.mark.parametrize("n", [4097, 4099, 8191 + 4 * 64 + 1, 12345])
@@ -205,3 +132,86 @@ def test_a_third_of_the_bodies_crossing():
     keys[idx] = keys[RNG.permutation(idx)]
     path, k = check(keys, want="direct")
     assert k > n // 5
+
+
+# ---- the decision in full: T crossers in all, 64 lists of `subcap`, no wave with more than half its bodies crossing ----------------
+N, NB, T, SUBCAP, NSUB = 20000, 256, 1024, 64, 64            # the device's defaults: list = (slot >> 6) & 63
+LEN = (N + NB - 1) // NB                                      # 79
+
+
+def moved(slots):
+    """sorted distinct keys in which the bodies of `slots` (no range starts) have the key of a body half the array away"""
+    keys = np.sort(np.random.default_rng(23).choice(1 << 40, N, replace=False).astype(np.uint64))
+    orig = keys.copy()
+    slots = np.asarray(slots, dtype=np.int64)
+    assert len(set(slots.tolist())) == len(slots) and (slots % LEN != 0).all()
+    keys[slots] = orig[(slots + 120 * LEN) % N]
+    return keys, slots
+
+
+def in_wave(w, count):
+    """the first `count` slots of wave w that are no range starts"""
+    return [s for s in range(WAVE * w, WAVE * (w + 1)) if s % LEN != 0][:count]
+
+
+def decide(slots, want, why=()):
+    keys, slots = moved(slots)
+    words = pack(keys)
+    for f in (direct_sort, direct_sort_fast):
+        tw = f(words, NB, T, SUBCAP, NSUB)
+        assert (tw.path, tw.why, tw.k) == (want, why, len(slots))
+        assert np.array_equal(tw.crossers, np.sort(slots))
+        assert np.array_equal(tw.out, expect(words))
+    same(direct_sort(words, NB, T, SUBCAP, NSUB), direct_sort_fast(words, NB, T, SUBCAP, NSUB))
+
+
+def test_a_list_holds_its_room_and_not_one_more():
+    # waves 5, 69, 133 and 197 share list 5
+    four = sum((in_wave(w, 16) for w in (5, 69, 133, 197)), [])
+    decide(four, "direct")
+    decide(four + [in_wave(261, 1)[0]], "counting", ("list",))
+    decide(four + [in_wave(6, 1)[0]], "direct")                # (the 65th crosser in ANOTHER list changes nothing)
+
+
+def test_half_a_wave_may_cross_and_not_one_more():
+    decide(in_wave(7, 32), "direct")
+    decide(in_wave(7, 33), "counting", ("wave",))
+    decide(in_wave(7, 32) + in_wave(8, 32), "direct")          # (two neighbouring waves, half of each)
+
+
+def test_the_total_holds_t_and_not_one_more():
+    full = sum((in_wave(w, 16) for w in range(64)), [])        # 16 in every list: no list over 64, no wave over 32
+    assert len(full) == T
+    decide(full, "direct")
+    decide(full + [in_wave(100, 1)[0]], "counting", ("total",))
+
+
+def test_range_keys_out_of_order_are_named():
+    keys, _ = moved([])
+    keys[3 * LEN], keys[200 * LEN] = keys[200 * LEN], keys[3 * LEN]
+    for f in (direct_sort, direct_sort_fast):
+        tw = f(pack(keys), NB, T, SUBCAP, NSUB)
+        assert (tw.path, tw.why, tw.k, tw.crossers) == ("counting", ("order",), None, None)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_the_two_twins_agree_on_random_small_inputs(seed):
+    """random sizes, bucket counts, rooms and disorder -- range starts included, so every rule fires in some case"""
+    rng = np.random.default_rng(100 + seed)
+    fired = set()
+    for _ in range(12):
+        nb = int(rng.choice([4, 16, 64]))
+        n = int(rng.integers(nb + 1, 1500))
+        keys = np.sort(rng.integers(0, 1 << int(rng.choice([6, 40])), n, dtype=np.uint64))
+        for _ in range(int(rng.choice([0, 1, 3, 40, 400]))):
+            i, j = rng.integers(0, n, 2)
+            keys[i] = keys[j]
+        nsub = int(rng.choice([1, 4, 64]))
+        cap = int(rng.choice([2, 8, 64, 1 << 20]))
+        subcap = None if nsub == 1 else int(rng.choice([1, 4, 16]))
+        words = pack(keys)
+        a, b = direct_sort(words, nb, cap, subcap, nsub), direct_sort_fast(words, nb, cap, subcap, nsub)
+        same(a, b)
+        assert np.array_equal(a.out, expect(words))
+        fired.update(a.why or ("none",))
+    assert len(fired) >= 3
