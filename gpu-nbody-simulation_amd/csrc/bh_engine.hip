@@ -1,4 +1,7 @@
-// bh_engine.hip -- libbhgpu.so: context, per-step pipeline and the C-ABI of include/bhgpu.h.
+// bh_engine.hip -- libbhgpu.so: the C-ABI of include/bhgpu.h.  In this file: the context and its helpers, the tree build, the
+// walks' launchers, the step and the split operators, the diagnostics, direct sums and force check, tree export, the
+// locally-essential trees and migration.  The analysis queries' host code -- moment maps, radial profiles, field at points,
+// neighbours, pair counts, groups -- is bh_queries_host.hpp, included below as part of this unit.
 // Compiled with -ffp-contract=off (tree build + exact walk must not fuse multiply-adds; the fp32
 // walk lives in bh_walk_fast.hip, compiled separately).  gfx950 only, no CPU fallback.
 #include "../../include/bhgpu.h"
@@ -31,6 +34,7 @@
 #include "bh_groups.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
+#include "bh_queries_state.hpp"
 
 using namespace bh;
 
@@ -157,21 +161,13 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     double *diag_part = nullptr, *diag_out = nullptr;
     // the split operators (bh_split.hpp; is.forces_current): the records of bh_timestep are allocated on first use
     TsRecord *ts_part = nullptr, *ts_out = nullptr;
-    // moment maps (bh_moments.hpp), allocated on first use: the first pass's record, the body counter, and the 4-plane int64
-    // grid, which grows to the largest map asked for (map_cells of them per plane)
-    MapMax *map_max = nullptr;
-    unsigned long long *map_count = nullptr;
-    long long *map_planes = nullptr;
-    int64_t map_cells = 0;
-    // radial profiles and Lagrangian radii (bh_radial.hpp), allocated on first use: the first pass's record, the select's flags,
-    // the squared edges, the 6-plane int64 profile of up to BH_RADIAL_MAX_BINS + 2 slots, a round's histograms
-    RadMax *rad_max = nullptr;
-    unsigned long long *rad_flags = nullptr;
-    double *rad_e2 = nullptr;
-    long long *rad_planes = nullptr, *rad_hist = nullptr;
-    int rad_blocks = 512;              // BH_RADIAL_BLOCKS: most persistent workgroups of the radial kernels
-    hipEvent_t rad_ev[4 + 2 * kRadRounds] = {};                     // around the first pass, the deposit, and every select round
-    double rad_max_ms = 0.0, rad_main_ms = 0.0, rad_round_ms[kRadRounds] = {};     // of the last call (bh_radial_times)
+    // the analysis queries (bh_queries_host.hpp; one struct per family, bh_queries_state.hpp), all allocated on first use
+    MapState map;
+    RadState rad;
+    FieldState field;
+    NbState nb;
+    PairState pair;
+    FofState fof;
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -183,50 +179,6 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     double2 *direct_out = nullptr;
     void *check_force = nullptr;
     uint32_t *check_counts = nullptr, *check_cost = nullptr;
-    // the field at arbitrary points (bh_field.hpp), allocated on first use: one block for a launch of up to field_cap points --
-    // the points, their results, two key arrays and the sorted order, the sort's count matrix and row totals
-    char *field_block = nullptr;
-    int64_t field_cap = 0;
-    uint64_t field_bytes = 0;
-    double2 *field_points = nullptr, *field_accel = nullptr;
-    uint64_t *field_keys[2] = {nullptr, nullptr};
-    double *field_phi = nullptr;
-    uint32_t *field_order = nullptr, *field_counts = nullptr, *field_radix = nullptr, *field_rows = nullptr;
-    // neighbour queries (bh_neighbours.hpp), allocated on first use and grown as the field's block: one block for the search
-    // structure of up to nb_cap bodies, one for a launch of up to nb_rows queries with nb_entries list entries in all
-    char *nb_block = nullptr, *nb_qblock = nullptr;
-    int64_t nb_cap = 0, nb_rows = 0, nb_entries = 0;
-    uint64_t nb_bytes = 0, nb_qbytes = 0;
-    uint64_t *nb_keys[2] = {nullptr, nullptr}, *nb_pkeys[2] = {nullptr, nullptr};
-    uint32_t *nb_slot = nullptr, *nb_sidx = nullptr, *nb_radix = nullptr, *nb_rowsum = nullptr, *nb_order = nullptr, *nb_evals = nullptr;
-    double2 *nb_spos = nullptr, *nb_points = nullptr;
-    NbBox *nb_boxes = nullptr;
-    NbBounds *nb_bounds = nullptr;
-    double *nb_box = nullptr, *nb_d2 = nullptr;
-    int32_t *nb_off = nullptr;
-    int64_t *nb_idx = nullptr;
-    hipEvent_t nb_ev[4] = {nullptr, nullptr, nullptr, nullptr};    // around the build and around a launch's sort and search
-    double nb_build_ms = 0.0, nb_query_ms = 0.0;                    // of the last call (bh_neighbours_times)
-    // pair counts (bh_pairs.hpp), allocated on first use: the squared edges, then the int64 histogram and the evals word
-    double *pair_e2 = nullptr;
-    unsigned long long *pair_hist = nullptr;
-    double pair_build_ms = 0.0, pair_query_ms = 0.0;                // of the last call (bh_pair_counts_times)
-    // friends-of-friends groups (bh_groups.hpp), allocated on first use: one block for up to fof_cap bodies beside the
-    // neighbour structure's, and the catalogue of the last bh_groups call on the host (no record of bh_run_state.hpp: it is
-    // that call's result, whatever the run does afterwards)
-    char *fof_block = nullptr;
-    int64_t fof_cap = 0;
-    uint64_t fof_bytes = 0;
-    uint32_t *fof_parent = nullptr, *fof_root = nullptr, *fof_minidx = nullptr, *fof_count = nullptr, *fof_rec_label = nullptr,
-             *fof_rec_count = nullptr;
-    long long *fof_label = nullptr;
-    unsigned long long *fof_sums = nullptr;
-    GrpCounters *fof_ctr = nullptr;
-    GrpMax *fof_max = nullptr;
-    hipEvent_t fof_ev[2] = {nullptr, nullptr};                      // after the labels, after the catalogue
-    double fof_build_ms = 0.0, fof_link_ms = 0.0, fof_cat_ms = 0.0; // of the last call (bh_groups_times)
-    std::vector<int64_t> fof_cat_labels, fof_cat_counts, fof_cat_sums;
-    int32_t fof_cat_exp[kGrpPlanes] = {0, 0, 0, 0, 0};
     bool sort_pack = true;              // BH_SORT_PACK=0: separate key and index arrays in every pass (A/B)
     unsigned long long *orb_hist = nullptr;
     double *mig_send = nullptr, *mig_recv = nullptr;
@@ -908,6 +860,20 @@ bool forces_cover_all(const bh_ctx *c) { return !c->let_mode && c->world == 1; }
 // BH_ERR_STATE with the caller's text unless a body set has been uploaded
 int need_upload(bh_ctx *c, const std::string &text) { return c->is.uploaded ? BH_OK : fail(c, BH_ERR_STATE, text); }
 
+// uploaded, and one context holds every body: else BH_ERR_STATE, `what` + `why_single` for the second
+int single_gpu_check(bh_ctx *c, const char *what, const char *why_single)
+{
+    if (int rc = need_upload(c, std::string(what) + " before bh_upload")) return rc;
+    return forces_cover_all(c) ? BH_OK : fail(c, BH_ERR_STATE, std::string(what) + why_single);
+}
+
+// the diagnostics and the analysis queries that need a tree or every body
+int diag_check(bh_ctx *c, const char *what)
+{
+    return single_gpu_check(c, what, ": single GPU only -- in LET mode bh_let_potential / bh_let_energy give the potential "
+                                     "and the energy sums; the replicated scheme (world > 1) and the other diagnostics have no distributed form");
+}
+
 // the LET calls' preconditions (c may be null): configured, and on demand bodies or a tree in the buffers
 enum LetNeed { kLetConfigured, kLetBodies, kLetTree };
 int let_check(bh_ctx *c, const char *who, LetNeed need)
@@ -971,6 +937,10 @@ int quietly(bh_ctx *c, unsigned opts, Body body)
 
 }  // namespace
 
+// the analysis queries: moment maps, radial profiles, field at points, neighbours, pair counts, groups -- and the helpers they
+// share, which the diagnostics below use as well
+#include "bh_queries_host.hpp"
+
 // ================================================================================================
 
 extern "C" {
@@ -1025,7 +995,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     c->hilbert = !c->tree64();
     if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_CHAIN_COLLAPSE")) c->chain_collapse = std::atoi(e) != 0;
-    if (const char *e = std::getenv("BH_RADIAL_BLOCKS")) { const int b = std::atoi(e); if (b >= 1 && b <= 65536) c->rad_blocks = b; }
+    if (const char *e = std::getenv("BH_RADIAL_BLOCKS")) { const int b = std::atoi(e); if (b >= 1 && b <= 65536) c->rad.blocks = b; }
     auto bail = [&](int rc) { g_create_error = c->err; bh_destroy(c); return rc; };
 
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(BH_ERR_DEVICE); }
@@ -1130,8 +1100,8 @@ void bh_destroy(bh_ctx *c)
     c->exp.destroy(c->n);
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
-    destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb_ev);
-    destroy(c->fof_ev); destroy(c->rad_ev);
+    destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1350,12 +1320,6 @@ int bh_step(bh_ctx *c, int32_t nsteps)
 }
 
 // ---- the split operators (bh_split.hpp): kick, drift, the time-step criterion, and the leapfrog built from them
-// uploaded, and one context holds every body: else BH_ERR_STATE, `what` + `why_single` for the second
-static int single_gpu_check(bh_ctx *c, const char *what, const char *why_single)
-{
-    if (int rc = need_upload(c, std::string(what) + " before bh_upload")) return rc;
-    return forces_cover_all(c) ? BH_OK : fail(c, BH_ERR_STATE, std::string(what) + why_single);
-}
 static int split_check(bh_ctx *c, const char *what) { return single_gpu_check(c, what, ": single GPU only (not in LET mode or with world > 1)"); }
 
 static int need_forces(bh_ctx *c, const char *what)
@@ -1445,11 +1409,7 @@ int bh_timestep(bh_ctx *c, double eta, double length, bh_timestep_t *out)
         return fail(c, BH_ERR_ARG, "bh_timestep: needs a finite length > 0, or a softening length to take its place");
     if (int rc = need_forces(c, "bh_timestep")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
-    if (!c->ts_part) {
-        int rc = dev_alloc(c, &c->ts_part, (size_t)kTsParts);
-        if (!rc) rc = dev_alloc(c, &c->ts_out, 1);
-        if (rc) { dev_free(c, c->ts_part); dev_free(c, c->ts_out); c->ts_part = c->ts_out = nullptr; return rc; }
-    }
+    if (!c->ts_part) { if (int rc = alloc_all(c, {part(&c->ts_part, (size_t)kTsParts), part(&c->ts_out, 1)})) return rc; }
     const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
     if (c->tree64())
         hipLaunchKernelGGL((timestep_partial_kernel<double2>), dim3(kTsParts), dim3(kBlock), 0, c->stream, (const double2 *)c->force,
@@ -1500,497 +1460,6 @@ int bh_step_kdk(bh_ctx *c, int32_t nsteps)
     return BH_OK;
 }
 
-// ---- moment maps (bh_moments.hpp).  They read pos / vel / mass as they lie in memory and write buffers of their own: no
-// tree, no record of bh_run_state.hpp, so a step before and after runs bit for bit as it would have.
-static int map_check(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme)
-{
-    const std::string w(who);
-    if (!box) return fail(c, BH_ERR_ARG, w + ": null box");
-    if (nx < 1 || ny < 1) return fail(c, BH_ERR_ARG, w + ": nx and ny must be at least 1");
-    if ((int64_t)nx * ny > kMapMaxCells)
-        return fail(c, BH_ERR_ARG, w + ": nx * ny exceeds BH_MAP_MAX_CELLS = " + std::to_string(kMapMaxCells));
-    if (scheme != BH_MAP_NGP && scheme != BH_MAP_CIC) return fail(c, BH_ERR_ARG, w + ": scheme must be BH_MAP_NGP or BH_MAP_CIC");
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(box[k])) return fail(c, BH_ERR_ARG, w + ": the box is not finite");
-    if (!(box[0] < box[1]) || !(box[2] < box[3])) return fail(c, BH_ERR_ARG, w + ": the box is empty (needs xmin < xmax and ymin < ymax)");
-    if (!std::isfinite(box[1] - box[0]) || !std::isfinite(box[3] - box[2]) || !std::isfinite((double)nx / (box[1] - box[0])) ||
-        !std::isfinite((double)ny / (box[3] - box[2])))
-        return fail(c, BH_ERR_ARG, w + ": the box's extent or the cells per unit length overflow fp64");
-    return need_upload(c, w + " before bh_upload/bh_initialize");
-}
-
-static int map_alloc(bh_ctx *c, int64_t cells)
-{
-    if (!c->map_max) {
-        int rc = dev_alloc(c, &c->map_max, 1);
-        if (!rc) rc = dev_alloc(c, &c->map_count, 1);
-        if (rc) { dev_free(c, c->map_max); dev_free(c, c->map_count); c->map_max = nullptr; c->map_count = nullptr; return rc; }
-    }
-    if (cells > c->map_cells) {
-        dev_free(c, c->map_planes);
-        c->map_planes = nullptr;
-        c->map_cells = 0;
-        if (int rc = dev_alloc(c, &c->map_planes, (size_t)kMapPlanes * cells)) return rc;
-        c->map_cells = cells;
-    }
-    return BH_OK;
-}
-
-// pass 1: the four maxima on the host when this returns; BH_ERR_ARG when a body is not finite
-static int map_maxima(bh_ctx *c, const char *who, double (&maxabs)[kMapPlanes])
-{
-    for (double &v : maxabs) v = 0.0;
-    if (c->n == 0) return BH_OK;
-    if (int rc = map_alloc(c, 0)) return rc;
-    BH_HIP(c, hipMemsetAsync(c->map_max, 0, sizeof(MapMax), c->stream));
-    with_state(c, [&](auto r2) {
-        using Real2 = decltype(r2);
-        using Real = decltype(r2.x);
-        hipLaunchKernelGGL((moment_max_kernel<Real2, Real>), dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream,
-                           static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass),
-                           c->n, c->map_max);
-    });
-    BH_HIP(c, hipGetLastError());
-    MapMax r{};
-    BH_HIP(c, hipMemcpyAsync(&r, c->map_max, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    if (r.bad)
-        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a moment m v, m |v|^2 that "
-                                   "overflows fp64)");
-    for (int p = 0; p < kMapPlanes; ++p) std::memcpy(&maxabs[p], &r.bits[p], sizeof(double));
-    return BH_OK;
-}
-
-// ceil(log2(max(n, 1)))
-static int map_log2_ceil(int64_t n)
-{
-    int L = 0;
-    while (((int64_t)1 << L) < n) ++L;
-    return L;
-}
-
-// pass 2 with the exponents e: the grid stays on the device (map_planes), *n_deposited on the host.  The exponents must
-// cover this context's own maxima and body count -- else a contribution or a sum could leave int64.
-static int map_deposit(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *e,
-                       const double (&maxabs)[kMapPlanes], int64_t *n_deposited)
-{
-    const int L = map_log2_ceil(c->n);
-    for (int p = 0; p < kMapPlanes; ++p) {
-        int E = 0;
-        if (maxabs[p] != 0.0) (void)std::frexp(maxabs[p], &E);
-        if (maxabs[p] != 0.0 && (int64_t)E + e[p] + L > 62)
-            return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
-                                       " is too large for this context's bodies (at most " + std::to_string(62 - E - L) + ")");
-    }
-    const int64_t cells = (int64_t)nx * ny;
-    if (int rc = map_alloc(c, cells)) return rc;
-    BH_HIP(c, hipMemsetAsync(c->map_planes, 0, (size_t)kMapPlanes * cells * sizeof(long long), c->stream));
-    BH_HIP(c, hipMemsetAsync(c->map_count, 0, sizeof(unsigned long long), c->stream));
-    if (c->n > 0) {
-        MapGrid g{};
-        g.xmin = box[0]; g.xmax = box[1]; g.ymin = box[2]; g.ymax = box[3];
-        g.sx = (double)nx / (box[1] - box[0]);
-        g.sy = (double)ny / (box[3] - box[2]);
-        g.nx = nx; g.ny = ny;
-        for (int p = 0; p < kMapPlanes; ++p) g.e[p] = e[p];
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            dispatch([&](auto cic) {
-                hipLaunchKernelGGL((moment_deposit_kernel<decltype(cic)::value, Real2, Real>), dim3(blocks_for(c->n, kBlock)), dim3(kBlock),
-                                   0, c->stream, static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
-                                   static_cast<const Real *>(c->mass), c->n, g, c->map_planes, c->map_count);
-            }, scheme == BH_MAP_CIC);
-        });
-        BH_HIP(c, hipGetLastError());
-    }
-    unsigned long long cnt = 0;
-    BH_HIP(c, hipMemcpyAsync(&cnt, c->map_count, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    *n_deposited = (int64_t)cnt;
-    return BH_OK;
-}
-
-int bh_moment_map_max(bh_ctx *c, double *maxabs)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_moment_map_max: null output");
-    if (int rc = need_upload(c, "bh_moment_map_max before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kMapPlanes];
-    if (int rc = map_maxima(c, "bh_moment_map_max", m)) return rc;
-    std::copy(m, m + kMapPlanes, maxabs);
-    return BH_OK;
-}
-
-int bh_moment_map_deposit(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *exponents,
-                          void **planes_dev, int64_t *n_deposited)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!exponents || !planes_dev || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map_deposit: null argument");
-    if (int rc = map_check(c, "bh_moment_map_deposit", box, nx, ny, scheme)) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kMapPlanes];
-    if (int rc = map_maxima(c, "bh_moment_map_deposit", m)) return rc;
-    if (int rc = map_deposit(c, "bh_moment_map_deposit", box, nx, ny, scheme, exponents, m, n_deposited)) return rc;
-    *planes_dev = c->map_planes;
-    return BH_OK;
-}
-
-int bh_moment_map(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, int64_t *planes, int32_t *exponents,
-                  int64_t *n_deposited)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!planes || !exponents || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map: null argument");
-    if (int rc = map_check(c, "bh_moment_map", box, nx, ny, scheme)) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kMapPlanes];
-    if (int rc = map_maxima(c, "bh_moment_map", m)) return rc;
-    const int L = map_log2_ceil(c->n);
-    int32_t e[kMapPlanes];
-    for (int p = 0; p < kMapPlanes; ++p) {
-        int E = 0;
-        e[p] = 0;
-        if (m[p] != 0.0) { (void)std::frexp(m[p], &E); e[p] = 62 - E - L; }
-    }
-    if (int rc = map_deposit(c, "bh_moment_map", box, nx, ny, scheme, e, m, n_deposited)) return rc;
-    BH_HIP(c, hipMemcpy(planes, c->map_planes, (size_t)kMapPlanes * nx * ny * sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::copy(e, e + kMapPlanes, exponents);
-    return BH_OK;
-}
-
-// ---- radial profiles and Lagrangian radii (bh_radial.hpp).  As the moment maps: they read pos / vel / mass as they lie in
-// memory and write buffers of their own -- no tree, no build, so there is nothing for a quiet scope (bh_run_state.hpp) to put
-// back: no record of it is touched, and a step before and after runs bit for bit as it would have.
-static int rad_alloc(bh_ctx *c)
-{
-    for (auto &e : c->rad_ev)
-        if (!e) BH_HIP(c, hipEventCreate(&e));
-    if (c->rad_max) return BH_OK;
-    int rc = dev_alloc(c, &c->rad_max, 1);
-    if (!rc) rc = dev_alloc(c, &c->rad_flags, 1);
-    if (!rc) rc = dev_alloc(c, &c->rad_e2, (size_t)kRadMaxBins + 1);
-    if (!rc) rc = dev_alloc(c, &c->rad_planes, (size_t)(kRadPlanes + 1) * (kRadMaxBins + 2));
-    if (!rc) rc = dev_alloc(c, &c->rad_hist, (size_t)kRadMaxFractions * kRadDigits * 2);
-    if (rc) {
-        for (void *p : {(void *)c->rad_max, (void *)c->rad_flags, (void *)c->rad_e2, (void *)c->rad_planes, (void *)c->rad_hist}) dev_free(c, p);
-        c->rad_max = nullptr; c->rad_flags = nullptr; c->rad_e2 = nullptr; c->rad_planes = nullptr; c->rad_hist = nullptr;
-    }
-    return rc;
-}
-
-static int rad_centre(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, RadCentre *out)
-{
-    if (!centre) return fail(c, BH_ERR_ARG, std::string(who) + ": null centre");
-    *out = RadCentre{centre[0], centre[1], centre_vel ? centre_vel[0] : 0.0, centre_vel ? centre_vel[1] : 0.0};
-    if (!(std::isfinite(out->cx) && std::isfinite(out->cy) && std::isfinite(out->ux) && std::isfinite(out->uy)))
-        return fail(c, BH_ERR_ARG, std::string(who) + ": the centre or its velocity is not finite");
-    return BH_OK;
-}
-
-// the squared edges on the host; BH_ERR_ARG unless the edges and their squares are finite, >= 0 and strictly ascending
-static int rad_edges(bh_ctx *c, const char *who, const double *edges, int32_t nb, std::vector<double> &e2)
-{
-    const std::string w(who);
-    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
-    if (nb < 1 || nb > kRadMaxBins) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_RADIAL_MAX_BINS = " + std::to_string(kRadMaxBins));
-    e2.resize((size_t)nb + 1);
-    for (int k = 0; k <= nb; ++k) {
-        e2[(size_t)k] = edges[k] * edges[k];
-        if (!std::isfinite(edges[k]) || !std::isfinite(e2[(size_t)k])) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
-        if (edges[k] < 0.0) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
-        if (k > 0 && !(edges[k - 1] < edges[k] && e2[(size_t)k - 1] < e2[(size_t)k]))
-            return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
-    }
-    return BH_OK;
-}
-
-// persistent workgroups: at most rad_blocks of them, and none without a body
-static unsigned rad_grid(const bh_ctx *c) { return std::min<unsigned>((unsigned)c->rad_blocks, blocks_for(c->n, kBlock)); }
-
-// pass 1: the five maxima on the host when this returns (with_vel = false: the mass alone, the velocities are not read);
-// BH_ERR_ARG when a body is not finite, or -- no_negative -- when a mass is negative
-static int rad_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, bool with_vel, bool no_negative, double (&maxabs)[kRadPlanes])
-{
-    for (double &v : maxabs) v = 0.0;
-    c->rad_max_ms = 0.0;
-    if (c->n == 0) return BH_OK;
-    if (int rc = rad_alloc(c)) return rc;
-    BH_HIP(c, hipEventRecord(c->rad_ev[0], c->stream));
-    BH_HIP(c, hipMemsetAsync(c->rad_max, 0, sizeof(RadMax), c->stream));
-    with_state(c, [&](auto r2) {
-        using Real2 = decltype(r2);
-        using Real = decltype(r2.x);
-        dispatch([&](auto vel) {
-            hipLaunchKernelGGL((radial_max_kernel<decltype(vel)::value, Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), 0,
-                               c->stream, static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
-                               static_cast<const Real *>(c->mass), c->n, ctr, c->rad_max);
-        }, with_vel);
-    });
-    BH_HIP(c, hipGetLastError());
-    BH_HIP(c, hipEventRecord(c->rad_ev[1], c->stream));
-    RadMax r{};
-    BH_HIP(c, hipMemcpyAsync(&r, c->rad_max, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[0], c->rad_ev[1]));
-    c->rad_max_ms = (double)ms;
-    if (r.bad)
-        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a squared radius or a "
-                                   "moment m vr, m vt, m vr^2, m vt^2 that overflows fp64)");
-    if (no_negative && r.negative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
-    for (int p = 0; p < kRadPlanes; ++p) std::memcpy(&maxabs[p], &r.bits[p], sizeof(double));
-    return BH_OK;
-}
-
-static int32_t rad_exponent(double maxabs, int L)
-{
-    int E = 0;
-    if (maxabs == 0.0) return 0;
-    (void)std::frexp(maxabs, &E);
-    return 62 - E - L;
-}
-
-// pass 2 with the exponents e: the planes stay on the device (rad_planes, 6 x (nb + 2))
-static int rad_deposit(bh_ctx *c, const char *who, const RadCentre &ctr, const std::vector<double> &e2, int32_t nb, const int32_t *e,
-                       const double (&maxabs)[kRadPlanes])
-{
-    const int L = map_log2_ceil(c->n);
-    for (int p = 0; p < kRadPlanes; ++p) {
-        int E = 0;
-        if (maxabs[p] != 0.0) (void)std::frexp(maxabs[p], &E);
-        if (maxabs[p] != 0.0 && (int64_t)E + e[p] + L > 62)
-            return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
-                                       " is too large for this context's bodies (at most " + std::to_string(62 - E - L) + ")");
-    }
-    if (int rc = rad_alloc(c)) return rc;
-    const int S = nb + 2;
-    c->rad_main_ms = 0.0;
-    for (double &v : c->rad_round_ms) v = 0.0;
-    BH_HIP(c, hipEventRecord(c->rad_ev[2], c->stream));
-    BH_HIP(c, hipMemsetAsync(c->rad_planes, 0, (size_t)(kRadPlanes + 1) * S * sizeof(long long), c->stream));
-    if (c->n > 0) {
-        BH_HIP(c, hipMemcpyAsync(c->rad_e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        RadExp ex{};
-        for (int p = 0; p < kRadPlanes; ++p) ex.e[p] = e[p];
-        const bool priv = S <= kRadLdsSlots;
-        const size_t lds = priv ? ((size_t)(kRadPlanes + 1) * S + (size_t)nb + 1) * 8 : (size_t)(kRadPlanes + 1) * kRadLdsSlots * 8;
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            dispatch([&](auto p) {
-                hipLaunchKernelGGL((radial_deposit_kernel<decltype(p)::value, Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), lds, c->stream,
-                                   static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel),
-                                   static_cast<const Real *>(c->mass), c->n, ctr, c->rad_e2, (int)nb, ex, c->rad_planes);
-            }, priv);
-        });
-        BH_HIP(c, hipGetLastError());
-    }
-    BH_HIP(c, hipEventRecord(c->rad_ev[3], c->stream));
-    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 is the caller's until the copy has run)
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[2], c->rad_ev[3]));
-    c->rad_main_ms = (double)ms;
-    return BH_OK;
-}
-
-int bh_radial_max(bh_ctx *c, const double *centre, const double *centre_vel, double *maxabs)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_radial_max: null output");
-    RadCentre ctr{};
-    if (int rc = rad_centre(c, "bh_radial_max", centre, centre_vel, &ctr)) return rc;
-    if (int rc = need_upload(c, "bh_radial_max before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kRadPlanes];
-    if (int rc = rad_maxima(c, "bh_radial_max", ctr, true, false, m)) return rc;
-    std::copy(m, m + kRadPlanes, maxabs);
-    return BH_OK;
-}
-
-int bh_radial_deposit(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb,
-                      const int32_t *exponents, void **planes_dev)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!exponents || !planes_dev) return fail(c, BH_ERR_ARG, "bh_radial_deposit: null argument");
-    RadCentre ctr{};
-    std::vector<double> e2;
-    if (int rc = rad_centre(c, "bh_radial_deposit", centre, centre_vel, &ctr)) return rc;
-    if (int rc = rad_edges(c, "bh_radial_deposit", edges, nb, e2)) return rc;
-    if (int rc = need_upload(c, "bh_radial_deposit before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kRadPlanes];
-    if (int rc = rad_maxima(c, "bh_radial_deposit", ctr, true, false, m)) return rc;
-    if (int rc = rad_deposit(c, "bh_radial_deposit", ctr, e2, nb, exponents, m)) return rc;
-    *planes_dev = c->rad_planes;
-    return BH_OK;
-}
-
-int bh_radial_profile(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int64_t *planes,
-                      int32_t *exponents)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_radial_profile: null argument");
-    RadCentre ctr{};
-    std::vector<double> e2;
-    if (int rc = rad_centre(c, "bh_radial_profile", centre, centre_vel, &ctr)) return rc;
-    if (int rc = rad_edges(c, "bh_radial_profile", edges, nb, e2)) return rc;
-    if (int rc = need_upload(c, "bh_radial_profile before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kRadPlanes];
-    if (int rc = rad_maxima(c, "bh_radial_profile", ctr, true, false, m)) return rc;
-    const int L = map_log2_ceil(c->n);
-    int32_t e[kRadPlanes];
-    for (int p = 0; p < kRadPlanes; ++p) e[p] = rad_exponent(m[p], L);
-    if (int rc = rad_deposit(c, "bh_radial_profile", ctr, e2, nb, e, m)) return rc;
-    BH_HIP(c, hipMemcpy(planes, c->rad_planes, (size_t)(kRadPlanes + 1) * (nb + 2) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::copy(e, e + kRadPlanes, exponents);
-    return BH_OK;
-}
-
-// one round: rad_hist[np][256][2] on the device and complete when this returns; timed between rad_ev[4 + 2 round] and the next
-static int rad_select_round(bh_ctx *c, const char *who, const RadCentre &ctr, int32_t e0, int32_t round, const uint64_t *prefixes,
-                            int32_t np)
-{
-    if (int rc = rad_alloc(c)) return rc;
-    const int L = map_log2_ceil(c->n);
-    BH_HIP(c, hipEventRecord(c->rad_ev[4 + 2 * round], c->stream));
-    BH_HIP(c, hipMemsetAsync(c->rad_hist, 0, (size_t)np * kRadDigits * 2 * sizeof(long long), c->stream));
-    BH_HIP(c, hipMemsetAsync(c->rad_flags, 0, sizeof(unsigned long long), c->stream));
-    for (int32_t p0 = 0; p0 < np && c->n > 0; p0 += kRadSelChunk) {
-        RadSelect s{};
-        s.cx = ctr.cx; s.cy = ctr.cy;
-        s.m_limit = std::ldexp(1.0, 62 - L - e0);
-        s.e0 = e0;
-        s.hi_shift = 64 - kRadDigitBits * round;
-        s.lo_shift = 64 - kRadDigitBits * (round + 1);
-        s.np = std::min<int32_t>(kRadSelChunk, np - p0);
-        for (int k = 0; k < s.np; ++k) s.prefix[k] = prefixes[p0 + k];
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            hipLaunchKernelGGL((radial_select_kernel<Real2, Real>), dim3(rad_grid(c)), dim3(kBlock), 0, c->stream,
-                               static_cast<const Real2 *>(c->pos), static_cast<const Real *>(c->mass), c->n, s,
-                               c->rad_hist + (size_t)p0 * kRadDigits * 2, c->rad_flags);
-        });
-        BH_HIP(c, hipGetLastError());
-    }
-    BH_HIP(c, hipEventRecord(c->rad_ev[5 + 2 * round], c->stream));
-    unsigned long long flags = 0;
-    BH_HIP(c, hipMemcpyAsync(&flags, c->rad_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    BH_HIP(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->rad_ev[4 + 2 * round], c->rad_ev[5 + 2 * round]));
-    c->rad_round_ms[round] = (double)ms;
-    if (flags & kRadFlagBad) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position or mass (or a squared radius that overflows fp64)");
-    if (flags & kRadFlagNegative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
-    if (flags & kRadFlagLarge)
-        return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e0) + " is too large for this context's masses and body count");
-    return BH_OK;
-}
-
-static int rad_select_args(bh_ctx *c, const char *who, int32_t round, const uint64_t *prefixes, int32_t np)
-{
-    const std::string w(who);
-    if (round < 0 || round >= kRadRounds) return fail(c, BH_ERR_ARG, w + ": round must be 0 .. 7");
-    if (!prefixes) return fail(c, BH_ERR_ARG, w + ": null prefixes");
-    if (np < 1 || np > kRadMaxFractions) return fail(c, BH_ERR_ARG, w + ": np must be 1 .. BH_RADIAL_MAX_FRACTIONS");
-    if (round == 0 && (np != 1 || prefixes[0] != 0)) return fail(c, BH_ERR_ARG, w + ": round 0 has the one prefix 0");
-    for (int32_t a = 0; a < np; ++a) {
-        if (round > 0 && (prefixes[a] >> (kRadDigitBits * round)) != 0) return fail(c, BH_ERR_ARG, w + ": a prefix has more digits than the round");
-        for (int32_t b = 0; b < a; ++b)
-            if (prefixes[a] == prefixes[b]) return fail(c, BH_ERR_ARG, w + ": the prefixes must be distinct");
-    }
-    return BH_OK;
-}
-
-int bh_radial_select(bh_ctx *c, const double *centre, int32_t exponent, int32_t round, const uint64_t *prefixes, int32_t np,
-                     void **hist_dev)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!hist_dev) return fail(c, BH_ERR_ARG, "bh_radial_select: null output");
-    RadCentre ctr{};
-    if (int rc = rad_centre(c, "bh_radial_select", centre, nullptr, &ctr)) return rc;
-    if (int rc = rad_select_args(c, "bh_radial_select", round, prefixes, np)) return rc;
-    if (int rc = need_upload(c, "bh_radial_select before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    c->rad_max_ms = 0.0; c->rad_main_ms = 0.0;
-    for (double &v : c->rad_round_ms) v = 0.0;
-    if (int rc = rad_select_round(c, "bh_radial_select", ctr, exponent, round, prefixes, np)) return rc;
-    c->rad_main_ms = c->rad_round_ms[round];
-    *hist_dev = c->rad_hist;
-    return BH_OK;
-}
-
-int bh_lagrangian_radii(bh_ctx *c, const double *centre, const double *fractions, int32_t nf, double *r2, int64_t *count, int64_t *mass,
-                        int32_t *exponent)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!fractions || !r2 || !count || !mass || !exponent) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: null argument");
-    RadCentre ctr{};
-    if (int rc = rad_centre(c, "bh_lagrangian_radii", centre, nullptr, &ctr)) return rc;
-    if (nf < 1 || nf > kRadMaxFractions) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: nf must be 1 .. BH_RADIAL_MAX_FRACTIONS = 32");
-    for (int32_t f = 0; f < nf; ++f)
-        if (!(std::isfinite(fractions[f]) && fractions[f] > 0.0 && fractions[f] <= 1.0))
-            return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: a fraction must be finite, > 0 and <= 1");
-    if (int rc = need_upload(c, "bh_lagrangian_radii before bh_upload/bh_initialize")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    double m[kRadPlanes];
-    if (int rc = rad_maxima(c, "bh_lagrangian_radii", ctr, false, true, m)) return rc;
-    const int32_t e0 = rad_exponent(m[0], map_log2_ceil(c->n));
-    *exponent = e0;
-    c->rad_main_ms = 0.0;
-    for (double &v : c->rad_round_ms) v = 0.0;
-    // the decisions between the rounds are made here, on the host, from the downloaded histograms
-    uint64_t prefix[kRadMaxFractions] = {0};                     // the digits decided so far, per fraction
-    int64_t below_w[kRadMaxFractions] = {0}, below_n[kRadMaxFractions] = {0}, target[kRadMaxFractions] = {0};
-    std::vector<int64_t> hist((size_t)kRadMaxFractions * kRadDigits * 2);
-    for (int32_t round = 0; round < kRadRounds; ++round) {
-        uint64_t distinct[kRadMaxFractions];
-        int32_t which[kRadMaxFractions], np = 0;
-        for (int32_t f = 0; f < nf; ++f) {
-            int32_t k = 0;
-            while (k < np && distinct[k] != prefix[f]) ++k;
-            if (k == np) distinct[np++] = prefix[f];
-            which[f] = k;
-        }
-        if (int rc = rad_select_round(c, "bh_lagrangian_radii", ctr, e0, round, distinct, np)) return rc;
-        c->rad_main_ms += c->rad_round_ms[round];
-        BH_HIP(c, hipMemcpy(hist.data(), c->rad_hist, (size_t)np * kRadDigits * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (round == 0) {
-            int64_t W = 0;
-            for (int d = 0; d < kRadDigits; ++d) W += hist[(size_t)d * 2];
-            if (W == 0) {
-                for (int32_t f = 0; f < nf; ++f) { r2[f] = std::nan(""); count[f] = 0; mass[f] = 0; }
-                return BH_OK;
-            }
-            for (int32_t f = 0; f < nf; ++f)
-                target[f] = std::min<int64_t>(W, std::max<int64_t>(1, (int64_t)std::ceil(fractions[f] * (double)W)));
-        }
-        for (int32_t f = 0; f < nf; ++f) {
-            const int64_t *h = hist.data() + (size_t)which[f] * kRadDigits * 2;
-            int d = 0;
-            while (d < kRadDigits - 1 && below_w[f] + h[2 * d] < target[f]) { below_w[f] += h[2 * d]; below_n[f] += h[2 * d + 1]; ++d; }
-            prefix[f] = (prefix[f] << kRadDigitBits) | (uint64_t)d;
-            if (round == kRadRounds - 1) {
-                std::memcpy(&r2[f], &prefix[f], sizeof(double));
-                count[f] = below_n[f] + h[2 * d + 1];
-                mass[f] = below_w[f] + h[2 * d];
-            }
-        }
-    }
-    return BH_OK;
-}
-
-int bh_radial_times(bh_ctx *c, double *max_ms, double *main_ms, double *rounds_ms)
-{
-    if (!c || !max_ms || !main_ms) return fail(c, BH_ERR_ARG, "bh_radial_times: null argument");
-    *max_ms = c->rad_max_ms;
-    *main_ms = c->rad_main_ms;
-    if (rounds_ms) std::copy(c->rad_round_ms, c->rad_round_ms + kRadRounds, rounds_ms);
-    return BH_OK;
-}
-
 // A walk's output `dev` holds forces (fp64 tree) or accelerations (fp32 / mixed); the other is converted with the masses
 // (a = F / m_i: updateAccelerations, project.cu:795-801)
 static int forces_or_accels(bh_ctx *c, const void *dev, double *out, bool forces)
@@ -2034,23 +1503,12 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
 // A tree of the current state is built in a quiet scope (quietly) for the potential walk and the force check.
 // The walk writes phi and its own term counts only: force, body_counts, group_cost, partial, the event timings and
 // walk_launches are not touched.
-static int diag_check(bh_ctx *c, const char *what)
-{
-    return single_gpu_check(c, what, ": single GPU only -- in LET mode bh_let_potential / bh_let_energy give the potential "
-                                     "and the energy sums; the replicated scheme (world > 1) and the other diagnostics have no distributed form");
-}
-
 static int diag_alloc(bh_ctx *c)
 {
     if (c->phi) return BH_OK;
     const size_t cap = (size_t)std::max<int64_t>(c->cfg.capacity, 1);
-    int rc = dev_alloc(c, &c->phi, cap);
-    if (!rc) rc = dev_alloc(c, &c->phi_counts, cap);
-    if (!rc) rc = dev_alloc(c, &c->diag_part, (size_t)kDiagParts * 2 * kDiagQuantities);
-    if (!rc) rc = dev_alloc(c, &c->diag_out, (size_t)kDiagQuantities);
-    if (rc) { for (void *p : {(void *)c->phi, (void *)c->phi_counts, (void *)c->diag_part, (void *)c->diag_out}) dev_free(c, p);
-              c->phi = nullptr; c->phi_counts = nullptr; c->diag_part = c->diag_out = nullptr; }
-    return rc;
+    return alloc_all(c, {part(&c->phi, cap), part(&c->phi_counts, cap), part(&c->diag_part, (size_t)kDiagParts * 2 * kDiagQuantities),
+                         part(&c->diag_out, (size_t)kDiagQuantities)});
 }
 
 static int enqueue_potential(bh_ctx *c)
@@ -2116,12 +1574,9 @@ int bh_get_potential(bh_ctx *c, double *phi, uint32_t *counts)
 // the eight sums of bh_diag.hpp over the state and phi, in the two fixed-shape passes: q on the host when this returns
 static int energy_sums(bh_ctx *c, double (&q)[kDiagQuantities])
 {
-    with_state(c, [&](auto r2) {
-        using Real2 = decltype(r2);
-        using Real = decltype(r2.x);
-        hipLaunchKernelGGL((energy_partial_kernel<Real2, Real>), dim3(kDiagParts), dim3(kBlock), 0, c->stream,
-                           static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass),
-                           c->phi, c->n, c->diag_part);
+    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+        hipLaunchKernelGGL((energy_partial_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(kDiagParts), dim3(kBlock), 0,
+                           c->stream, pos, vel, mass, c->phi, c->n, c->diag_part);
     });
     hipLaunchKernelGGL(energy_final_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->diag_part, c->diag_out);
     BH_HIP(c, hipGetLastError());
@@ -2175,11 +1630,7 @@ static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targe
 {
     if (n_targets == 0) return BH_OK;
     const int64_t chunk = std::max<int64_t>(c->cfg.capacity, 1);
-    if (!c->direct_out) {
-        int rc = dev_alloc(c, &c->direct_targets, (size_t)chunk);
-        if (!rc) rc = dev_alloc(c, &c->direct_out, (size_t)chunk);
-        if (rc) { dev_free(c, c->direct_targets); dev_free(c, c->direct_out); c->direct_targets = nullptr; c->direct_out = nullptr; return rc; }
-    }
+    if (!c->direct_out) { if (int rc = alloc_all(c, {part(&c->direct_targets, (size_t)chunk), part(&c->direct_out, (size_t)chunk)})) return rc; }
     const uint32_t *slot_of = nullptr;
     if (!c->tree64() && !c->is.orig_identity) {            // (fp32 / mixed after a physical re-order: slots are not caller indices)
         if (!c->slot_of) { if (int rc = dev_alloc(c, &c->slot_of, (size_t)chunk)) return rc; }
@@ -2190,12 +1641,9 @@ static int direct_forces_host(bh_ctx *c, const int64_t *targets, int64_t n_targe
         const int64_t k = std::min(chunk, n_targets - t0);
         if (targets) BH_HIP(c, hipMemcpyAsync(c->direct_targets, targets + t0, k * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         const int64_t *tg = targets ? c->direct_targets : nullptr;
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            hipLaunchKernelGGL((direct_forces_kernel<Real2, Real>), dim3(blocks_for(k, kBlock)), dim3(kBlock), 0, c->stream,
-                               (const Real2 *)c->pos, (const Real *)c->mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->eps2,
-                               c->direct_out);
+        state_ptrs(c, [&](auto pos, auto, auto mass) {
+            hipLaunchKernelGGL((direct_forces_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(blocks_for(k, kBlock)),
+                               dim3(kBlock), 0, c->stream, pos, mass, slot_of, tg, t0, k, c->n, c->cfg.G, c->eps2, c->direct_out);
         });
         BH_HIP(c, hipGetLastError());
         BH_HIP(c, hipMemcpyAsync(out + 2 * t0, c->direct_out, k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
@@ -2250,566 +1698,6 @@ int bh_force_check(bh_ctx *c, const int64_t *targets, int64_t n_targets, double 
         tree[2 * t] = all[2 * i]; tree[2 * t + 1] = all[2 * i + 1];
     }
     return direct_forces_host(c, targets, n_targets, direct);
-}
-
-// ---- the field at arbitrary points (bh_field.hpp)
-// The tree comes from a quiet build (quietly), with the walk counters of bh_stats copied aside and put back as in
-// check_walk (keys_kernel clears them).  The kernels read the tree and the call's own buffers and write the call's own buffers
-// only: force, body_counts, group_cost, phi, the event timings and walk_launches are not touched.
-static int field_alloc(bh_ctx *c, int64_t want)
-{
-    if (want <= c->field_cap) return BH_OK;
-    int64_t cap = 1024;
-    while (cap < want) cap <<= 1;                              // (want <= kFieldChunk, a power of two)
-    if (c->field_block) {                                      // (the previous call has waited for its stream)
-        dev_free(c, c->field_block);
-        c->device_bytes -= c->field_bytes;
-        c->field_block = nullptr; c->field_cap = 0; c->field_bytes = 0;
-    }
-    const size_t nbl = blocks_for(cap, kBlock * kFieldSortItems);
-    const size_t per_point = 2 * sizeof(double2) + 2 * sizeof(uint64_t) + sizeof(double) + 2 * sizeof(uint32_t);
-    const size_t bytes = (size_t)cap * per_point + ((size_t)kRadix * nbl + kRadix) * sizeof(uint32_t);
-    char *b = nullptr;
-    if (int rc = dev_alloc(c, &b, bytes)) return rc;
-    c->field_block = b; c->field_cap = cap; c->field_bytes = bytes;
-    auto take = [&](auto **out, size_t count) {
-        using T = typename std::remove_reference<decltype(**out)>::type;
-        *out = reinterpret_cast<T *>(b);
-        b += count * sizeof(T);
-    };
-    take(&c->field_points, (size_t)cap); take(&c->field_accel, (size_t)cap);       // (16-byte records first: every array aligned)
-    take(&c->field_keys[0], (size_t)cap); take(&c->field_keys[1], (size_t)cap); take(&c->field_phi, (size_t)cap);
-    take(&c->field_order, (size_t)cap); take(&c->field_counts, (size_t)cap);
-    take(&c->field_radix, (size_t)kRadix * nbl); take(&c->field_rows, (size_t)kRadix);
-    return BH_OK;
-}
-
-// one launch of k <= field_cap points that are in field_points: keys, sort, walk; results at the points' places
-static int enqueue_field(bh_ctx *c, int64_t k)
-{
-    hipStream_t st = c->stream;
-    const unsigned grid = blocks_for(k, kBlock);
-    hipLaunchKernelGGL(field_keys_kernel, dim3(grid), dim3(kBlock), 0, st, c->field_points, k, c->box, c->field_keys[0]);
-    static_assert(kFieldKeyBits % kSortBits == 0 && kFieldKeyBits <= kPackShift && kFieldChunk <= ((int64_t)1 << (64 - kPackShift)),
-                  "the keys and the indices of a launch share a word");
-    uint32_t *const order[2] = {c->field_order, c->field_order};  // (packed: written by the last pass only, wherever it ends)
-    enqueue_lsd_passes<kFieldSortItems>(st, c->field_keys, order, c->field_radix, c->field_rows, k, kFieldKeyBits, true);
-    if (c->tree64()) {
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, c->gd, c->ld, c->field_order, c->field_points, k, c->cfg.theta,
-                               c->cfg.G, c->eps2, c->ctr, c->field_accel, c->field_phi, c->field_counts);
-        };
-        if (c->mode == Mode::F64) go(field_f64_kernel<kAcceptThr>);
-        else if (c->exact_thresholds) go(field_f64_kernel<kAcceptExactThr>);
-        else go(field_f64_kernel<kAcceptSize>);
-    } else {
-        hipLaunchKernelGGL(field_f32_kernel, dim3(grid), dim3(kBlock), 0, st, c->qf, c->aux, c->spos, c->smass, c->field_order,
-                           c->field_points, k, c->cfg.G, c->eps2f, c->ctr, c->field_accel, c->field_phi, c->field_counts);
-    }
-    BH_HIP(c, hipGetLastError());
-    return BH_OK;
-}
-
-int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel, double *phi, uint32_t *counts)
-{
-    if (!c) return BH_ERR_ARG;
-    if (n_points < 0 || (n_points > 0 && !points) || (!accel && !phi && !counts))
-        return fail(c, BH_ERR_ARG, "bh_field_at: n_points < 0, null points or no output array");
-    if (int rc = diag_check(c, "bh_field_at")) return rc;
-    for (int64_t i = 0; i < 2 * n_points; ++i)
-        if (!std::isfinite(points[i]))
-            return fail(c, BH_ERR_ARG, "bh_field_at: point " + std::to_string(i / 2) + " has a non-finite coordinate");
-    if (n_points == 0) return BH_OK;
-    if (c->n == 0) {                                           // no bodies: no field, no terms
-        if (accel) std::fill(accel, accel + 2 * n_points, 0.0);
-        if (phi) std::fill(phi, phi + n_points, 0.0);
-        if (counts) std::fill(counts, counts + n_points, 0u);
-        return BH_OK;
-    }
-    BH_HIP(c, hipSetDevice(c->device));
-    if (int rc = field_alloc(c, std::min(n_points, kFieldChunk))) return rc;
-    int rc = quietly(c, kQuietCounters, [&] { return enqueue_build(c, false); });
-    if (!rc) rc = check_overflow(c);
-    if (rc) return rc;
-    for (int64_t t0 = 0; t0 < n_points; t0 += kFieldChunk) {
-        const int64_t k = std::min(kFieldChunk, n_points - t0);
-        BH_HIP(c, hipMemcpyAsync(c->field_points, points + 2 * t0, (size_t)k * sizeof(double2), hipMemcpyHostToDevice, c->stream));
-        if ((rc = enqueue_field(c, k))) return rc;
-        if (accel) BH_HIP(c, hipMemcpyAsync(accel + 2 * t0, c->field_accel, (size_t)k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-        if (phi) BH_HIP(c, hipMemcpyAsync(phi + t0, c->field_phi, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (counts) BH_HIP(c, hipMemcpyAsync(counts + t0, c->field_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        BH_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    return BH_OK;
-}
-
-// ---- neighbour queries (bh_neighbours.hpp).  They read pos (and orig) as they lie in memory and write buffers of their own: no
-// force tree, no record of bh_run_state.hpp, no counter and no timing of the run, so a step before and after runs bit for bit as
-// it would have.
-constexpr int64_t kNbChunk = kFieldChunk;       // queries per launch: a point's index travels in its key word
-
-// the structure's block for n bodies and the launch block for `rows` queries of `entries` list entries in all
-static int nb_alloc(bh_ctx *c, int64_t n, int64_t rows, int64_t entries)
-{
-    auto carve = [](char *&b, auto **out, size_t count) {
-        using T = typename std::remove_reference<decltype(**out)>::type;
-        *out = reinterpret_cast<T *>(b);
-        b += (count * sizeof(T) + 15) / 16 * 16;
-    };
-    for (auto &e : c->nb_ev)
-        if (!e) BH_HIP(c, hipEventCreate(&e));
-    if (n > c->nb_cap) {
-        int64_t cap = 1024;
-        while (cap < n) cap <<= 1;
-        if (c->nb_block) {                                     // (the previous call has waited for its stream)
-            dev_free(c, c->nb_block);
-            c->device_bytes -= c->nb_bytes;
-            c->nb_block = nullptr; c->nb_cap = 0; c->nb_bytes = 0;
-        }
-        int32_t off[kNbMaxLevels + 1];
-        nb_levels(cap, off);
-        const size_t nodes = (size_t)off[kNbMaxLevels] + kNbMaxLevels;            // (n <= cap has at most a node more per level)
-        const size_t nbl = blocks_for(std::max(cap, kNbChunk), kBlock * kFieldSortItems);
-        const size_t bytes = (size_t)cap * (sizeof(double2) + 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + nodes * sizeof(NbBox) +
-                             ((size_t)kRadix * nbl + kRadix) * sizeof(uint32_t) + sizeof(NbBounds) + 4 * sizeof(double) +
-                             (kNbMaxLevels + 1) * sizeof(int32_t) + 16 * 12;
-        char *b = nullptr;
-        if (int rc = dev_alloc(c, &b, bytes)) return rc;
-        c->nb_block = b; c->nb_cap = cap; c->nb_bytes = bytes;
-        carve(b, &c->nb_spos, (size_t)cap); carve(b, &c->nb_boxes, nodes);
-        carve(b, &c->nb_keys[0], (size_t)cap); carve(b, &c->nb_keys[1], (size_t)cap);
-        carve(b, &c->nb_bounds, 1); carve(b, &c->nb_box, 4);
-        carve(b, &c->nb_slot, (size_t)cap); carve(b, &c->nb_sidx, (size_t)cap);
-        carve(b, &c->nb_radix, (size_t)kRadix * nbl); carve(b, &c->nb_rowsum, (size_t)kRadix);
-        carve(b, &c->nb_off, (size_t)kNbMaxLevels + 1);
-    }
-    if (rows > c->nb_rows || entries > c->nb_entries) {
-        int64_t cap = std::max<int64_t>(c->nb_rows, 1024);
-        while (cap < rows) cap <<= 1;
-        const int64_t ent = std::max(entries, c->nb_entries);
-        if (c->nb_qblock) {
-            dev_free(c, c->nb_qblock);
-            c->device_bytes -= c->nb_qbytes;
-            c->nb_qblock = nullptr; c->nb_rows = 0; c->nb_entries = 0; c->nb_qbytes = 0;
-        }
-        const size_t bytes = (size_t)cap * (sizeof(double2) + 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) +
-                             (size_t)ent * (sizeof(int64_t) + sizeof(double)) + 16 * 8;
-        char *b = nullptr;
-        if (int rc = dev_alloc(c, &b, bytes)) return rc;
-        c->nb_qblock = b; c->nb_rows = cap; c->nb_entries = ent; c->nb_qbytes = bytes;
-        carve(b, &c->nb_points, (size_t)cap); carve(b, &c->nb_pkeys[0], (size_t)cap); carve(b, &c->nb_pkeys[1], (size_t)cap);
-        carve(b, &c->nb_idx, (size_t)ent); carve(b, &c->nb_d2, (size_t)ent);
-        carve(b, &c->nb_order, (size_t)cap); carve(b, &c->nb_evals, (size_t)cap);
-    }
-    return BH_OK;
-}
-
-// bounds, keys, sort, sorted copies and boxes of the current state (n > 0); BH_ERR_ARG when a position is not finite.  *levels:
-// the levels of the hierarchy.
-static int nb_build(bh_ctx *c, const char *who, int *levels)
-{
-    hipStream_t st = c->stream;
-    const int64_t n = c->n;
-    const unsigned grid = blocks_for(n, kBlock);
-    const NbBounds empty{~0ull, 0ull, ~0ull, 0ull, 0ull};
-    BH_HIP(c, hipEventRecord(c->nb_ev[0], st));
-    BH_HIP(c, hipMemcpyAsync(c->nb_bounds, &empty, sizeof(empty), hipMemcpyHostToDevice, st));
-    BH_HIP(c, hipStreamSynchronize(st));                        // (`empty` lives on this stack)
-    with_state(c, [&](auto r2) {
-        using Real2 = decltype(r2);
-        hipLaunchKernelGGL((nb_bounds_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos), n, c->nb_bounds);
-    });
-    BH_HIP(c, hipGetLastError());
-    NbBounds got{};
-    BH_HIP(c, hipMemcpyAsync(&got, c->nb_bounds, sizeof(got), hipMemcpyDeviceToHost, st));
-    BH_HIP(c, hipStreamSynchronize(st));
-    if (got.bad)
-        return fail(c, BH_ERR_ARG, std::string(who) + ": a body of the state has a non-finite position (found by the bounds pass)");
-    hipLaunchKernelGGL(nb_setup_kernel, dim3(1), dim3(1), 0, st, c->nb_bounds, n, c->nb_box, c->nb_off);
-    const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
-    static_assert(kFieldKeyBits % kSortBits == 0 && ((kFieldKeyBits / kSortBits) & 1) == 0, "the sorted keys end in the first array");
-    with_state(c, [&](auto r2) {
-        using Real2 = decltype(r2);
-        const Real2 *pos = static_cast<const Real2 *>(c->pos);
-        hipLaunchKernelGGL((nb_keys_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, n, c->nb_box, c->nb_keys[0]);
-        uint32_t *const slot[2] = {c->nb_slot, c->nb_slot};    // (packed: written by the last pass only)
-        enqueue_lsd_passes<kFieldSortItems>(st, c->nb_keys, slot, c->nb_radix, c->nb_rowsum, n, kFieldKeyBits, true);
-        hipLaunchKernelGGL((nb_gather_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, c->nb_slot, orig, n, c->nb_spos, c->nb_sidx);
-    });
-    int32_t off[kNbMaxLevels + 1];
-    *levels = nb_levels(n, off);
-    hipLaunchKernelGGL(nb_leaf_kernel, dim3(blocks_for(off[1], kBlock)), dim3(kBlock), 0, st, c->nb_spos, n, off[1], c->nb_boxes);
-    for (int l = 1; l < *levels; ++l) {
-        const int32_t count = off[l + 1] - off[l], below = off[l] - off[l - 1];
-        hipLaunchKernelGGL(nb_level_kernel, dim3(blocks_for(count, kBlock)), dim3(kBlock), 0, st, c->nb_boxes + off[l - 1], below,
-                           c->nb_boxes + off[l], count);
-    }
-    BH_HIP(c, hipGetLastError());
-    BH_HIP(c, hipEventRecord(c->nb_ev[1], st));
-    return BH_OK;
-}
-
-// Both queries.  k > 0: bh_neighbours; k == 0: bh_count_within at r2.  Rows come back in the launch's sorted order and are put
-// at their caller places here.
-static int nb_query(bh_ctx *c, const char *who, const double *points, int64_t n_points, int32_t k, double r2, int64_t *idx,
-                    double *d2, uint32_t *evals)
-{
-    const std::string w(who);
-    if (int rc = diag_check(c, who)) return rc;
-    if (!points && n_points != c->n) return fail(c, BH_ERR_ARG, w + ": without points, n_points must be the number of bodies");
-    for (int64_t i = 0; points && i < 2 * n_points; ++i)
-        if (!std::isfinite(points[i])) return fail(c, BH_ERR_ARG, w + ": point " + std::to_string(i / 2) + " has a non-finite coordinate");
-    if (n_points == 0) return BH_OK;
-    const int64_t n = c->n;
-    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, w + ": more than 2^24 bodies (their indices share a key word)");
-    const int64_t kk = std::max<int32_t>(k, 1);               // entries per row on the host side (counts: one)
-    if (n == 0) {                                              // no bodies: nobody is near
-        if (idx) std::fill(idx, idx + n_points * kk, (int64_t)-1);
-        if (d2) std::fill(d2, d2 + n_points * kk, (double)INFINITY);
-        if (evals) std::fill(evals, evals + n_points, 0u);
-        return BH_OK;
-    }
-    BH_HIP(c, hipSetDevice(c->device));
-    const int64_t rows_max = std::min(n_points, kNbChunk);
-    if (int rc = nb_alloc(c, n, rows_max, rows_max * k)) return rc;
-    int levels = 0;
-    if (int rc = nb_build(c, who, &levels)) return rc;
-    hipStream_t st = c->stream;
-    std::vector<uint32_t> dest((size_t)rows_max), hev((size_t)rows_max);
-    std::vector<int64_t> hidx(idx ? (size_t)(rows_max * k) : 0);
-    std::vector<double> hd2(d2 ? (size_t)(rows_max * k) : 0);
-    std::vector<uint32_t> sidx;
-    if (!points) {
-        sidx.resize((size_t)n);
-        BH_HIP(c, hipMemcpyAsync(sidx.data(), c->nb_sidx, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    c->nb_query_ms = 0.0;
-    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
-        const int64_t rows = std::min(kNbChunk, n_points - t0);
-        BH_HIP(c, hipEventRecord(c->nb_ev[2], st));
-        if (points) {
-            BH_HIP(c, hipMemcpyAsync(c->nb_points, points + 2 * t0, (size_t)rows * sizeof(double2), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(field_keys_kernel, dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_points, rows, c->nb_box,
-                               c->nb_pkeys[0]);
-            uint32_t *const order[2] = {c->nb_order, c->nb_order};
-            enqueue_lsd_passes<kFieldSortItems>(st, c->nb_pkeys, order, c->nb_radix, c->nb_rowsum, rows, kFieldKeyBits, true);
-        }
-        auto launch = [&](auto pts) {
-            constexpr bool PTS = decltype(pts)::value;
-            if (k > 0)
-                hipLaunchKernelGGL((nb_knn_kernel<PTS>), dim3(blocks_for(rows, kWave)), dim3(kWave), (size_t)k * kWave * 12, st, c->nb_spos,
-                                   c->nb_sidx, c->nb_keys[0], c->nb_boxes, c->nb_off, levels, (int32_t)n, k, c->nb_points, c->nb_order,
-                                   c->nb_pkeys[0], t0, rows, c->nb_idx, c->nb_d2, c->nb_evals);
-            else
-                hipLaunchKernelGGL((nb_count_kernel<PTS>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_spos, c->nb_boxes,
-                                   c->nb_off, levels, (int32_t)n, c->nb_points, c->nb_order, t0, rows, r2, c->nb_evals);
-        };
-        dispatch(launch, points != nullptr);
-        BH_HIP(c, hipGetLastError());
-        BH_HIP(c, hipEventRecord(c->nb_ev[3], st));
-        if (points) BH_HIP(c, hipMemcpyAsync(dest.data(), c->nb_order, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (idx) BH_HIP(c, hipMemcpyAsync(hidx.data(), c->nb_idx, (size_t)(rows * k) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (d2) BH_HIP(c, hipMemcpyAsync(hd2.data(), c->nb_d2, (size_t)(rows * k) * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (evals) BH_HIP(c, hipMemcpyAsync(hev.data(), c->nb_evals, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipStreamSynchronize(st));
-        float ms = 0.f;
-        BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[2], c->nb_ev[3]));
-        c->nb_query_ms += (double)ms;
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t at = points ? t0 + (int64_t)dest[(size_t)r] : (int64_t)sidx[(size_t)(t0 + r)];
-            if (idx) std::copy(hidx.begin() + r * k, hidx.begin() + (r + 1) * k, idx + at * k);
-            if (d2) std::copy(hd2.begin() + r * k, hd2.begin() + (r + 1) * k, d2 + at * k);
-            if (evals) evals[at] = hev[(size_t)r];
-        }
-    }
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
-    c->nb_build_ms = (double)ms;
-    return BH_OK;
-}
-
-int bh_neighbours(bh_ctx *c, const double *points, int64_t n_points, int32_t k, int64_t *idx, double *d2, uint32_t *evals)
-{
-    if (!c) return BH_ERR_ARG;
-    if (k < 1 || k > kNbMaxK) return fail(c, BH_ERR_ARG, "bh_neighbours: k must be 1 .. BH_NEIGHBOURS_MAX_K = 32");
-    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_neighbours: n_points < 0");
-    if (!idx && !d2) return fail(c, BH_ERR_ARG, "bh_neighbours: no output array (idx and d2 are both null)");
-    return nb_query(c, "bh_neighbours", points, n_points, k, 0.0, idx, d2, evals);
-}
-
-int bh_count_within(bh_ctx *c, const double *points, int64_t n_points, double radius, uint32_t *counts)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(c, BH_ERR_ARG, "bh_count_within: the radius must be finite and >= 0");
-    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_count_within: n_points < 0");
-    if (!counts) return fail(c, BH_ERR_ARG, "bh_count_within: null counts");
-    return nb_query(c, "bh_count_within", points, n_points, 0, radius * radius, nullptr, nullptr, counts);
-}
-
-int bh_neighbours_times(bh_ctx *c, double *build_ms, double *query_ms)
-{
-    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_neighbours_times: null argument");
-    *build_ms = c->nb_build_ms;
-    *query_ms = c->nb_query_ms;
-    return BH_OK;
-}
-
-// ---- pair counts (bh_pairs.hpp) on the structure of the neighbour queries.  They read pos as it lies in memory and write buffers
-// of their own: a step before and after runs bit for bit as it would have.  Allowed in LET mode and with world > 1: the
-// bodies are this context's own.
-int bh_pair_counts(bh_ctx *c, const double *points, int64_t n_points, const double *edges, int32_t nb, int64_t *counts, int64_t *evals)
-{
-    if (!c) return BH_ERR_ARG;
-    if (nb < 1 || nb > kPairMaxBins) return fail(c, BH_ERR_ARG, "bh_pair_counts: 1 .. BH_PAIR_MAX_BINS = 1024 bins");
-    if (!edges || !counts) return fail(c, BH_ERR_ARG, "bh_pair_counts: null edges or counts");
-    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_pair_counts: n_points < 0");
-    std::vector<double> e2((size_t)nb + 1);
-    for (int32_t k = 0; k <= nb; ++k) {
-        e2[(size_t)k] = edges[k] * edges[k];
-        if (!std::isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1])))
-            return fail(c, BH_ERR_ARG, "bh_pair_counts: the edges must be finite, >= 0 and strictly ascending");
-        if (!std::isfinite(e2[(size_t)k]) || (k > 0 && !(e2[(size_t)k] > e2[(size_t)k - 1])))
-            return fail(c, BH_ERR_ARG, "bh_pair_counts: the squared edges must be finite and strictly ascending");
-    }
-    if (int rc = need_upload(c, "bh_pair_counts before bh_upload/bh_initialize")) return rc;
-    const int64_t n = c->n;
-    if (!points && n_points != n) return fail(c, BH_ERR_ARG, "bh_pair_counts: without points, n_points must be the number of bodies");
-    for (int64_t i = 0; points && i < 2 * n_points; ++i)
-        if (!std::isfinite(points[i]))
-            return fail(c, BH_ERR_ARG, "bh_pair_counts: point " + std::to_string(i / 2) + " has a non-finite coordinate");
-    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_pair_counts: more than 2^24 bodies (their indices share a key word)");
-    std::fill(counts, counts + nb + 2, (int64_t)0);
-    if (evals) *evals = 0;
-    c->pair_build_ms = c->pair_query_ms = 0.0;
-    if (n == 0 || n_points == 0) return BH_OK;
-    BH_HIP(c, hipSetDevice(c->device));
-    if (int rc = nb_alloc(c, n, points ? std::min(n_points, kNbChunk) : 0, 0)) return rc;
-    if (!c->pair_e2) {
-        if (int rc = dev_alloc(c, &c->pair_e2, (size_t)kPairMaxBins + 1)) return rc;
-        if (int rc = dev_alloc(c, &c->pair_hist, (size_t)kPairMaxBins + 3)) return rc;
-    }
-    int levels = 0;
-    if (int rc = nb_build(c, "bh_pair_counts", &levels)) return rc;
-    hipStream_t st = c->stream;
-    const size_t words = (size_t)nb + 3;                       // the bins, then the evals word
-    BH_HIP(c, hipMemcpyAsync(c->pair_e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    BH_HIP(c, hipMemsetAsync(c->pair_hist, 0, words * sizeof(unsigned long long), st));
-    const size_t lds = (2 * (size_t)nb + 4) * sizeof(unsigned long long);
-    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
-        const int64_t rows = std::min(kNbChunk, n_points - t0);
-        BH_HIP(c, hipEventRecord(c->nb_ev[2], st));
-        if (points) {
-            BH_HIP(c, hipMemcpyAsync(c->nb_points, points + 2 * t0, (size_t)rows * sizeof(double2), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(field_keys_kernel, dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, c->nb_points, rows, c->nb_box,
-                               c->nb_pkeys[0]);
-            uint32_t *const order[2] = {c->nb_order, c->nb_order};
-            enqueue_lsd_passes<kFieldSortItems>(st, c->nb_pkeys, order, c->nb_radix, c->nb_rowsum, rows, kFieldKeyBits, true);
-        }
-        dispatch([&](auto pts) {
-            hipLaunchKernelGGL((pair_count_kernel<decltype(pts)::value>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), lds, st,
-                               c->nb_spos, c->nb_boxes, c->nb_off, levels, (int32_t)n, c->nb_points, c->nb_order, t0, rows, c->pair_e2, nb,
-                               c->pair_hist, c->pair_hist + nb + 2);
-        }, points != nullptr);
-        BH_HIP(c, hipGetLastError());
-        BH_HIP(c, hipEventRecord(c->nb_ev[3], st));
-        BH_HIP(c, hipStreamSynchronize(st));                    // (the next chunk overwrites the points; the events are read here)
-        float ms = 0.f;
-        BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[2], c->nb_ev[3]));
-        c->pair_query_ms += (double)ms;
-    }
-    std::vector<unsigned long long> got(words);
-    BH_HIP(c, hipMemcpyAsync(got.data(), c->pair_hist, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    BH_HIP(c, hipStreamSynchronize(st));
-    for (int32_t k = 0; k < nb + 2; ++k) counts[k] = (int64_t)got[(size_t)k];
-    if (evals) *evals = (int64_t)got[(size_t)nb + 2];
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
-    c->pair_build_ms = (double)ms;
-    return BH_OK;
-}
-
-int bh_pair_counts_times(bh_ctx *c, double *build_ms, double *query_ms)
-{
-    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_pair_counts_times: null argument");
-    *build_ms = c->pair_build_ms;
-    *query_ms = c->pair_query_ms;
-    return BH_OK;
-}
-
-// ---- friends-of-friends groups (bh_groups.hpp) on the structure of the neighbour queries.  They read pos, vel, mass and orig as
-// they lie in memory and write buffers of their own: a step before and after runs bit for bit as it would have.
-static int fof_alloc(bh_ctx *c, int64_t n)
-{
-    auto carve = [](char *&b, auto **out, size_t count) {
-        using T = typename std::remove_reference<decltype(**out)>::type;
-        *out = reinterpret_cast<T *>(b);
-        b += (count * sizeof(T) + 15) / 16 * 16;
-    };
-    for (auto &e : c->fof_ev)
-        if (!e) BH_HIP(c, hipEventCreate(&e));
-    if (n <= c->fof_cap) return BH_OK;
-    int64_t cap = 1024;
-    while (cap < n) cap <<= 1;
-    if (c->fof_block) {                                            // (the previous call has waited for its stream)
-        dev_free(c, c->fof_block);
-        c->device_bytes -= c->fof_bytes;
-        c->fof_block = nullptr; c->fof_cap = 0; c->fof_bytes = 0;
-    }
-    const size_t bytes = (size_t)cap * (6 * sizeof(uint32_t) + sizeof(long long) + kGrpPlanes * sizeof(unsigned long long)) +
-                         sizeof(GrpCounters) + sizeof(GrpMax) + 16 * 10;
-    char *b = nullptr;
-    if (int rc = dev_alloc(c, &b, bytes)) return rc;
-    c->fof_block = b; c->fof_cap = cap; c->fof_bytes = bytes;
-    carve(b, &c->fof_sums, (size_t)cap * kGrpPlanes); carve(b, &c->fof_label, (size_t)cap);
-    carve(b, &c->fof_ctr, 1); carve(b, &c->fof_max, 1);
-    carve(b, &c->fof_parent, (size_t)cap); carve(b, &c->fof_root, (size_t)cap); carve(b, &c->fof_minidx, (size_t)cap);
-    carve(b, &c->fof_count, (size_t)cap); carve(b, &c->fof_rec_label, (size_t)cap); carve(b, &c->fof_rec_count, (size_t)cap);
-    return BH_OK;
-}
-
-int bh_groups(bh_ctx *c, double linking_length, int64_t min_members, int64_t *label, int64_t *n_groups, int64_t *n_catalogue,
-              uint64_t *stats)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!(linking_length >= 0.0) || !std::isfinite(linking_length))
-        return fail(c, BH_ERR_ARG, "bh_groups: the linking length must be finite and >= 0");
-    if (min_members < 1) return fail(c, BH_ERR_ARG, "bh_groups: min_members must be at least 1");
-    if (!n_groups) return fail(c, BH_ERR_ARG, "bh_groups: null n_groups");
-    if (int rc = diag_check(c, "bh_groups")) return rc;
-    const int64_t n = c->n;
-    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_groups: more than 2^24 bodies (their indices share a key word)");
-    c->fof_cat_labels.clear(); c->fof_cat_counts.clear(); c->fof_cat_sums.clear();
-    std::fill(c->fof_cat_exp, c->fof_cat_exp + kGrpPlanes, 0);
-    c->fof_build_ms = c->fof_link_ms = c->fof_cat_ms = 0.0;
-    *n_groups = 0;
-    if (n_catalogue) *n_catalogue = 0;
-    if (stats) stats[0] = stats[1] = stats[2] = 0;
-    if (n == 0) return BH_OK;
-    const double b2 = linking_length * linking_length;
-    BH_HIP(c, hipSetDevice(c->device));
-    if (int rc = nb_alloc(c, n, 0, 0)) return rc;
-    if (int rc = fof_alloc(c, n)) return rc;
-    int levels = 0;
-    if (int rc = nb_build(c, "bh_groups", &levels)) return rc;
-    hipStream_t st = c->stream;
-    const unsigned grid = blocks_for(n, kBlock);
-    const int32_t n32 = (int32_t)n;
-    BH_HIP(c, hipMemsetAsync(c->fof_ctr, 0, sizeof(GrpCounters), st));
-    BH_HIP(c, hipMemsetAsync(c->fof_minidx, 0xff, (size_t)n * sizeof(uint32_t), st));
-    BH_HIP(c, hipMemsetAsync(c->fof_count, 0, (size_t)n * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(grp_init_kernel, dim3(grid), dim3(kBlock), 0, st, c->nb_boxes, c->nb_off, levels, n32, b2, c->fof_parent, c->fof_ctr);
-    hipLaunchKernelGGL(grp_link_kernel, dim3(grid), dim3(kBlock), 0, st, c->nb_spos, c->nb_boxes, c->nb_off, levels, n32, b2,
-                       c->fof_parent, c->fof_ctr);
-    hipLaunchKernelGGL(grp_flatten_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_parent, c->nb_sidx, n32, c->fof_root, c->fof_minidx,
-                       c->fof_count, c->fof_ctr);
-    hipLaunchKernelGGL(grp_label_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_root, c->fof_minidx, c->nb_sidx, n32, c->fof_label);
-    BH_HIP(c, hipGetLastError());
-    BH_HIP(c, hipEventRecord(c->fof_ev[0], st));
-    GrpExp ex{};
-    GrpCounters ctr{};
-    if (n_catalogue) {
-        BH_HIP(c, hipMemsetAsync(c->fof_max, 0, sizeof(GrpMax), st));
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            hipLaunchKernelGGL((grp_max_kernel<Real2, Real>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos),
-                               static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass), n, c->fof_max);
-        });
-        // (gid: the parents are not read any more)
-        hipLaunchKernelGGL(grp_compact_kernel, dim3(grid), dim3(kBlock), 0, st, c->fof_root, c->fof_minidx, c->fof_count, n32,
-                           (uint32_t)std::min<int64_t>(min_members, (int64_t)UINT32_MAX), c->fof_parent, c->fof_rec_label,
-                           c->fof_rec_count, c->fof_ctr);
-        BH_HIP(c, hipGetLastError());
-        GrpMax mx{};
-        BH_HIP(c, hipMemcpyAsync(&mx, c->fof_max, sizeof(mx), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipMemcpyAsync(&ctr, c->fof_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipStreamSynchronize(st));
-        if (mx.bad)
-            return fail(c, BH_ERR_ARG, "bh_groups: a body has a non-finite velocity or mass (or a moment m x, m v that overflows fp64)");
-        const int L = map_log2_ceil(n);
-        for (int p = 0; p < kGrpPlanes; ++p) {
-            double m = 0.0;
-            std::memcpy(&m, &mx.bits[p], sizeof(double));
-            int E = 0;
-            if (m != 0.0) { (void)std::frexp(m, &E); ex.e[p] = 62 - E - L; }
-        }
-    }
-    if (!n_catalogue) {
-        BH_HIP(c, hipMemcpyAsync(&ctr, c->fof_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipStreamSynchronize(st));
-    }
-    const int64_t kept = (int64_t)ctr.kept;
-    if (n_catalogue && kept > 0) {
-        BH_HIP(c, hipMemsetAsync(c->fof_sums, 0, (size_t)kept * kGrpPlanes * sizeof(unsigned long long), st));
-        with_state(c, [&](auto r2) {
-            using Real2 = decltype(r2);
-            using Real = decltype(r2.x);
-            hipLaunchKernelGGL((grp_sum_kernel<Real2, Real>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos),
-                               static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass), c->nb_slot, c->fof_root,
-                               c->fof_count, c->fof_parent, n32, (uint32_t)std::min<int64_t>(min_members, (int64_t)UINT32_MAX), ex,
-                               c->fof_sums);
-        });
-        BH_HIP(c, hipGetLastError());
-    }
-    BH_HIP(c, hipEventRecord(c->fof_ev[1], st));
-    std::vector<uint32_t> rl((size_t)kept), rc_((size_t)kept);
-    std::vector<int64_t> sums((size_t)kept * kGrpPlanes);
-    if (kept > 0) {
-        BH_HIP(c, hipMemcpyAsync(rl.data(), c->fof_rec_label, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipMemcpyAsync(rc_.data(), c->fof_rec_count, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        BH_HIP(c, hipMemcpyAsync(sums.data(), c->fof_sums, sums.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    if (label) BH_HIP(c, hipMemcpyAsync(label, c->fof_label, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    BH_HIP(c, hipStreamSynchronize(st));
-    float ms = 0.f;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[0], c->nb_ev[1]));
-    c->fof_build_ms = (double)ms;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->nb_ev[1], c->fof_ev[0]));
-    c->fof_link_ms = (double)ms;
-    BH_HIP(c, hipEventElapsedTime(&ms, c->fof_ev[0], c->fof_ev[1]));
-    c->fof_cat_ms = (double)ms;
-    // the records in the order (count descending, label ascending): the device numbered them as its atomics fell
-    std::vector<int64_t> order((size_t)kept);
-    for (int64_t g = 0; g < kept; ++g) order[(size_t)g] = g;
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        return rc_[(size_t)a] != rc_[(size_t)b] ? rc_[(size_t)a] > rc_[(size_t)b] : rl[(size_t)a] < rl[(size_t)b];
-    });
-    c->fof_cat_labels.resize((size_t)kept); c->fof_cat_counts.resize((size_t)kept); c->fof_cat_sums.resize((size_t)kept * kGrpPlanes);
-    for (int64_t k = 0; k < kept; ++k) {
-        const size_t g = (size_t)order[(size_t)k];
-        c->fof_cat_labels[(size_t)k] = (int64_t)rl[g];
-        c->fof_cat_counts[(size_t)k] = (int64_t)rc_[g];
-        std::copy(sums.begin() + g * kGrpPlanes, sums.begin() + (g + 1) * kGrpPlanes, c->fof_cat_sums.begin() + (size_t)k * kGrpPlanes);
-    }
-    std::copy(ex.e, ex.e + kGrpPlanes, c->fof_cat_exp);
-    *n_groups = (int64_t)ctr.roots;
-    if (n_catalogue) *n_catalogue = kept;
-    if (stats) { stats[0] = ctr.evals; stats[1] = ctr.pairs; stats[2] = ctr.hooks; }
-    return BH_OK;
-}
-
-int bh_groups_catalogue(bh_ctx *c, int64_t max_records, int64_t *labels, int64_t *counts, int64_t *sums, int32_t *exponents,
-                        int64_t *n_out)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!n_out || max_records < 0) return fail(c, BH_ERR_ARG, "bh_groups_catalogue: null n_out or max_records < 0");
-    const int64_t g = (int64_t)c->fof_cat_labels.size();
-    *n_out = g;
-    if (exponents) std::copy(c->fof_cat_exp, c->fof_cat_exp + kGrpPlanes, exponents);
-    if (g > max_records) return fail(c, BH_ERR_CAPACITY, "bh_groups_catalogue: the catalogue has " + std::to_string(g) + " records");
-    if (labels) std::copy(c->fof_cat_labels.begin(), c->fof_cat_labels.end(), labels);
-    if (counts) std::copy(c->fof_cat_counts.begin(), c->fof_cat_counts.end(), counts);
-    if (sums) std::copy(c->fof_cat_sums.begin(), c->fof_cat_sums.end(), sums);
-    return BH_OK;
-}
-
-int bh_groups_times(bh_ctx *c, double *build_ms, double *link_ms, double *catalogue_ms)
-{
-    if (!c || !build_ms || !link_ms || !catalogue_ms) return fail(c, BH_ERR_ARG, "bh_groups_times: null argument");
-    *build_ms = c->fof_build_ms;
-    *link_ms = c->fof_link_ms;
-    *catalogue_ms = c->fof_cat_ms;
-    return BH_OK;
 }
 
 // ---- tree export: DFS pre-order, children in index order (TraverseTreeToFile, project.cu:504-534)

@@ -1,0 +1,927 @@
+// bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, the field
+// at points, neighbour queries, pair counts and friends-of-friends groups, with their entry points of include/bhgpu.h.
+// Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers (fail, BH_HIP,
+// dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp, bh_radial.hpp,
+// bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp and bh_groups.hpp, the state in bh_queries_state.hpp, the arithmetic that
+// needs no device in bh_query_host.hpp.  What every family shares comes first.
+#pragma once
+
+#include "bh_query_host.hpp"
+
+static_assert(LagrangianSelect::kDigitBits == kRadDigitBits && LagrangianSelect::kMaxFractions == kRadMaxFractions,
+              "the host's select and the select kernel cut the same digits");
+
+namespace {
+
+template <typename P>
+using Pointee = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+// f(pos, vel, mass) with the state arrays as they are typed: const double2 * / double *, or const float2 * / float *
+template <typename F>
+void state_ptrs(const bh_ctx *c, F &&f)
+{
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        using Real = decltype(r2.x);
+        f(static_cast<const Real2 *>(c->pos), static_cast<const Real2 *>(c->vel), static_cast<const Real *>(c->mass));
+    });
+}
+
+// A timed span is two marks on the stream and, once the caller has waited for the stream, span_ms between them.
+int mark(bh_ctx *c, hipEvent_t &e)
+{
+    if (!e) BH_HIP(c, hipEventCreate(&e));
+    BH_HIP(c, hipEventRecord(e, c->stream));
+    return BH_OK;
+}
+
+int span_ms(bh_ctx *c, hipEvent_t from, hipEvent_t to, double *ms, bool add = false)
+{
+    float f = 0.f;
+    BH_HIP(c, hipEventElapsedTime(&f, from, to));
+    *ms = (add ? *ms : 0.0) + (double)f;
+    return BH_OK;
+}
+
+// every array of a small set or none of them: after a failure all the pointers are null again, so the next call starts over
+int alloc_all(bh_ctx *c, std::initializer_list<BlockPart> parts)
+{
+    std::vector<char *> got(parts.size(), nullptr);
+    int rc = BH_OK;
+    size_t k = 0;
+    for (const BlockPart &p : parts)
+        if (!rc) rc = dev_alloc(c, &got[k++], p.count * p.size);
+    if (rc)
+        for (char *&a : got) { dev_free(c, a); a = nullptr; }
+    k = 0;
+    for (const BlockPart &p : parts) std::memcpy(p.slot, &got[k++], sizeof(char *));
+    return rc;
+}
+
+// a block of `parts` for `cap` items in place of the one b holds (the previous call has waited for its stream); the parts'
+// pointers are set.  The caller decides when: b.cap is too small.  After a failure b is empty and the next call starts over.
+int block_regrow(bh_ctx *c, DevBlock &b, int64_t cap, std::initializer_list<BlockPart> parts)
+{
+    if (b.base) { dev_free(c, b.base); c->device_bytes -= b.bytes; b = DevBlock{}; }
+    const size_t bytes = lay_out(parts);
+    char *base = nullptr;
+    if (int rc = dev_alloc(c, &base, bytes)) return rc;
+    b.base = base; b.bytes = bytes; b.cap = cap;
+    lay_out(parts, base);
+    return BH_OK;
+}
+
+// a first pass's record {bits[P], flag words} on the host when this returns, with its maxima as doubles; the flags are the
+// caller's to test.  also: one more download that rides on the same wait.
+template <typename Rec, int P>
+int read_maxima(bh_ctx *c, const Rec *dev, Rec *rec, double (&maxabs)[P], void *also = nullptr, const void *also_dev = nullptr,
+                size_t also_bytes = 0)
+{
+    BH_HIP(c, hipMemcpyAsync(rec, dev, sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
+    if (also) BH_HIP(c, hipMemcpyAsync(also, also_dev, also_bytes, hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    for (int p = 0; p < P; ++p) std::memcpy(&maxabs[p], &rec->bits[p], sizeof(double));
+    return BH_OK;
+}
+
+// the caller's exponents must cover this context's own maxima and body count -- else a contribution or a sum could leave int64
+template <int P>
+int exponents_fit(bh_ctx *c, const char *who, const int32_t *e, const double (&maxabs)[P])
+{
+    const int L = log2_ceil(c->n);
+    for (int p = 0; p < P; ++p) {
+        int32_t most = 0;
+        if (!exponent_fits(e[p], maxabs[p], L, &most))
+            return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
+                                       " is too large for this context's bodies (at most " + std::to_string(most) + ")");
+    }
+    return BH_OK;
+}
+
+int points_finite(bh_ctx *c, const char *who, const double *points, int64_t n_points)
+{
+    const int64_t i = first_nonfinite_point(points, n_points);
+    return i < 0 ? BH_OK : fail(c, BH_ERR_ARG, std::string(who) + ": point " + std::to_string(i) + " has a non-finite coordinate");
+}
+
+// one launch's query points: `rows` of them from the host into `points`, their keys in `box`, and the launch's sorted order
+// (the index of a point travels in its key word: written by the last pass only, wherever it ends)
+int sorted_query_chunk(bh_ctx *c, const double *host_points, int64_t rows, double2 *points, const double *box, uint64_t *const keys[2],
+                       uint32_t *order, uint32_t *radix, uint32_t *rowsum)
+{
+    static_assert(kFieldKeyBits % kSortBits == 0 && kFieldKeyBits <= kPackShift && kFieldChunk <= ((int64_t)1 << (64 - kPackShift)),
+                  "the keys and the indices of a launch share a word");
+    BH_HIP(c, hipMemcpyAsync(points, host_points, (size_t)rows * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(field_keys_kernel, dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, c->stream, points, rows, box, keys[0]);
+    uint32_t *const into[2] = {order, order};
+    enqueue_lsd_passes<kFieldSortItems>(c->stream, keys, into, radix, rowsum, rows, kFieldKeyBits, true);
+    return BH_OK;
+}
+
+// ---- moment maps (bh_moments.hpp).  They read pos / vel / mass as they lie in memory and write buffers of their own: no
+// tree, no record of bh_run_state.hpp, so a step before and after runs bit for bit as it would have.
+int map_check(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme)
+{
+    const std::string w(who);
+    if (!box) return fail(c, BH_ERR_ARG, w + ": null box");
+    if (nx < 1 || ny < 1) return fail(c, BH_ERR_ARG, w + ": nx and ny must be at least 1");
+    if ((int64_t)nx * ny > kMapMaxCells)
+        return fail(c, BH_ERR_ARG, w + ": nx * ny exceeds BH_MAP_MAX_CELLS = " + std::to_string(kMapMaxCells));
+    if (scheme != BH_MAP_NGP && scheme != BH_MAP_CIC) return fail(c, BH_ERR_ARG, w + ": scheme must be BH_MAP_NGP or BH_MAP_CIC");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(box[k])) return fail(c, BH_ERR_ARG, w + ": the box is not finite");
+    if (!(box[0] < box[1]) || !(box[2] < box[3])) return fail(c, BH_ERR_ARG, w + ": the box is empty (needs xmin < xmax and ymin < ymax)");
+    if (!std::isfinite(box[1] - box[0]) || !std::isfinite(box[3] - box[2]) || !std::isfinite((double)nx / (box[1] - box[0])) ||
+        !std::isfinite((double)ny / (box[3] - box[2])))
+        return fail(c, BH_ERR_ARG, w + ": the box's extent or the cells per unit length overflow fp64");
+    return need_upload(c, w + " before bh_upload/bh_initialize");
+}
+
+int map_alloc(bh_ctx *c, int64_t cells)
+{
+    MapState &s = c->map;
+    if (!s.max) { if (int rc = alloc_all(c, {part(&s.max, 1), part(&s.count, 1)})) return rc; }
+    if (cells > s.cells) {
+        dev_free(c, s.planes); s.planes = nullptr; s.cells = 0;
+        if (int rc = dev_alloc(c, &s.planes, (size_t)kMapPlanes * cells)) return rc;
+        s.cells = cells;
+    }
+    return BH_OK;
+}
+
+// pass 1: the four maxima on the host when this returns; BH_ERR_ARG when a body is not finite
+int map_maxima(bh_ctx *c, const char *who, double (&maxabs)[kMapPlanes])
+{
+    for (double &v : maxabs) v = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = map_alloc(c, 0)) return rc;
+    BH_HIP(c, hipMemsetAsync(c->map.max, 0, sizeof(MapMax), c->stream));
+    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+        hipLaunchKernelGGL((moment_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(blocks_for(c->n, kBlock)),
+                           dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, c->map.max);
+    });
+    BH_HIP(c, hipGetLastError());
+    MapMax r{};
+    if (int rc = read_maxima(c, c->map.max, &r, maxabs)) return rc;
+    if (r.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a moment m v, m |v|^2 that "
+                                   "overflows fp64)");
+    return BH_OK;
+}
+
+// both passes.  e: the caller's exponents `given` or, without, the rule's own from this context's maxima.  The grid stays on the
+// device (map.planes), *n_deposited on the host.
+int map_passes(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *given,
+               int32_t (&e)[kMapPlanes], int64_t *n_deposited)
+{
+    if (int rc = map_check(c, who, box, nx, ny, scheme)) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double maxabs[kMapPlanes];
+    if (int rc = map_maxima(c, who, maxabs)) return rc;
+    for (int p = 0; p < kMapPlanes; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
+    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    const int64_t cells = (int64_t)nx * ny;
+    if (int rc = map_alloc(c, cells)) return rc;
+    BH_HIP(c, hipMemsetAsync(c->map.planes, 0, (size_t)kMapPlanes * cells * sizeof(long long), c->stream));
+    BH_HIP(c, hipMemsetAsync(c->map.count, 0, sizeof(unsigned long long), c->stream));
+    if (c->n > 0) {
+        MapGrid g{};
+        g.xmin = box[0]; g.xmax = box[1]; g.ymin = box[2]; g.ymax = box[3];
+        g.sx = (double)nx / (box[1] - box[0]);
+        g.sy = (double)ny / (box[3] - box[2]);
+        g.nx = nx; g.ny = ny;
+        for (int p = 0; p < kMapPlanes; ++p) g.e[p] = e[p];
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            dispatch([&](auto cic) {
+                hipLaunchKernelGGL((moment_deposit_kernel<decltype(cic)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>),
+                                   dim3(blocks_for(c->n, kBlock)), dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, g, c->map.planes,
+                                   c->map.count);
+            }, scheme == BH_MAP_CIC);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    unsigned long long cnt = 0;
+    BH_HIP(c, hipMemcpyAsync(&cnt, c->map.count, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    *n_deposited = (int64_t)cnt;
+    return BH_OK;
+}
+
+// ---- radial profiles and Lagrangian radii (bh_radial.hpp).  As the moment maps: they read pos / vel / mass as they lie in
+// memory and write buffers of their own -- no tree, no build, so there is nothing for a quiet scope (bh_run_state.hpp) to put
+// back: no record of it is touched, and a step before and after runs bit for bit as it would have.
+int rad_alloc(bh_ctx *c)
+{
+    RadState &s = c->rad;
+    if (s.max) return BH_OK;
+    return alloc_all(c, {part(&s.max, 1), part(&s.flags, 1), part(&s.e2, (size_t)kRadMaxBins + 1),
+                         part(&s.planes, (size_t)(kRadPlanes + 1) * (kRadMaxBins + 2)),
+                         part(&s.hist, (size_t)kRadMaxFractions * kRadDigits * 2)});
+}
+
+int rad_centre(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, RadCentre *out)
+{
+    if (!centre) return fail(c, BH_ERR_ARG, std::string(who) + ": null centre");
+    *out = RadCentre{centre[0], centre[1], centre_vel ? centre_vel[0] : 0.0, centre_vel ? centre_vel[1] : 0.0};
+    if (!(std::isfinite(out->cx) && std::isfinite(out->cy) && std::isfinite(out->ux) && std::isfinite(out->uy)))
+        return fail(c, BH_ERR_ARG, std::string(who) + ": the centre or its velocity is not finite");
+    return BH_OK;
+}
+
+// persistent workgroups: at most rad.blocks of them, and none without a body
+unsigned rad_grid(const bh_ctx *c) { return std::min<unsigned>((unsigned)c->rad.blocks, blocks_for(c->n, kBlock)); }
+
+// pass 1: the five maxima on the host when this returns (with_vel = false: the mass alone, the velocities are not read);
+// BH_ERR_ARG when a body is not finite, or -- no_negative -- when a mass is negative
+int rad_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, bool with_vel, bool no_negative, double (&maxabs)[kRadPlanes])
+{
+    RadState &s = c->rad;
+    for (double &v : maxabs) v = 0.0;
+    s.max_ms = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = rad_alloc(c)) return rc;
+    if (int rc = mark(c, s.ev[0])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(RadMax), c->stream));
+    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+        dispatch([&](auto v) {
+            hipLaunchKernelGGL((radial_max_kernel<decltype(v)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(rad_grid(c)),
+                               dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, s.max);
+        }, with_vel);
+    });
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[1])) return rc;
+    RadMax r{};
+    if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
+    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.max_ms)) return rc;
+    if (r.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a squared radius or a "
+                                   "moment m vr, m vt, m vr^2, m vt^2 that overflows fp64)");
+    if (no_negative && r.negative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
+    return BH_OK;
+}
+
+// both passes.  e: the caller's exponents `given` or, without, the rule's own from this context's maxima.  The planes stay on the
+// device (rad.planes, 6 x (nb + 2)).
+int rad_passes(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, const double *edges, int32_t nb,
+               const int32_t *given, int32_t (&e)[kRadPlanes])
+{
+    RadState &s = c->rad;
+    const std::string w(who);
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = rad_centre(c, who, centre, centre_vel, &ctr)) return rc;
+    // the squared edges on the host: BH_ERR_ARG unless the edges and their squares are finite, >= 0 and strictly ascending
+    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
+    const unsigned why = squared_edges(edges, nb, kRadMaxBins, e2);
+    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_RADIAL_MAX_BINS = " + std::to_string(kRadMaxBins));
+    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
+    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
+    if (why) return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
+    if (int rc = need_upload(c, w + " before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double maxabs[kRadPlanes];
+    if (int rc = rad_maxima(c, who, ctr, true, false, maxabs)) return rc;
+    for (int p = 0; p < kRadPlanes; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
+    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    if (int rc = rad_alloc(c)) return rc;
+    const int S = nb + 2;
+    s.main_ms = 0.0;
+    for (double &v : s.round_ms) v = 0.0;
+    if (int rc = mark(c, s.ev[2])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)(kRadPlanes + 1) * S * sizeof(long long), c->stream));
+    if (c->n > 0) {
+        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        RadExp ex{};
+        for (int p = 0; p < kRadPlanes; ++p) ex.e[p] = e[p];
+        const bool priv = S <= kRadLdsSlots;
+        const size_t lds = priv ? ((size_t)(kRadPlanes + 1) * S + (size_t)nb + 1) * 8 : (size_t)(kRadPlanes + 1) * kRadLdsSlots * 8;
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            dispatch([&](auto p) {
+                hipLaunchKernelGGL((radial_deposit_kernel<decltype(p)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>),
+                                   dim3(rad_grid(c)), dim3(kBlock), lds, c->stream, pos, vel, mass, c->n, ctr, s.e2, (int)nb, ex, s.planes);
+            }, priv);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[3])) return rc;
+    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
+    return span_ms(c, s.ev[2], s.ev[3], &s.main_ms);
+}
+
+// one round: rad.hist[np][256][2] on the device and complete when this returns; timed between rad.ev[4 + 2 round] and the next
+int rad_select_round(bh_ctx *c, const char *who, const RadCentre &ctr, int32_t e0, int32_t round, const uint64_t *prefixes, int32_t np)
+{
+    RadState &s = c->rad;
+    if (int rc = rad_alloc(c)) return rc;
+    const int L = log2_ceil(c->n);
+    if (int rc = mark(c, s.ev[4 + 2 * round])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.hist, 0, (size_t)np * kRadDigits * 2 * sizeof(long long), c->stream));
+    BH_HIP(c, hipMemsetAsync(s.flags, 0, sizeof(unsigned long long), c->stream));
+    for (int32_t p0 = 0; p0 < np && c->n > 0; p0 += kRadSelChunk) {
+        RadSelect sel{};
+        sel.cx = ctr.cx; sel.cy = ctr.cy;
+        sel.m_limit = std::ldexp(1.0, 62 - L - e0);
+        sel.e0 = e0;
+        sel.hi_shift = 64 - kRadDigitBits * round;
+        sel.lo_shift = 64 - kRadDigitBits * (round + 1);
+        sel.np = std::min<int32_t>(kRadSelChunk, np - p0);
+        for (int k = 0; k < sel.np; ++k) sel.prefix[k] = prefixes[p0 + k];
+        state_ptrs(c, [&](auto pos, auto, auto mass) {
+            hipLaunchKernelGGL((radial_select_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(rad_grid(c)), dim3(kBlock), 0,
+                               c->stream, pos, mass, c->n, sel, s.hist + (size_t)p0 * kRadDigits * 2, s.flags);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[5 + 2 * round])) return rc;
+    unsigned long long flags = 0;
+    BH_HIP(c, hipMemcpyAsync(&flags, s.flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    if (int rc = span_ms(c, s.ev[4 + 2 * round], s.ev[5 + 2 * round], &s.round_ms[round])) return rc;
+    if (flags & kRadFlagBad) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position or mass (or a squared radius that overflows fp64)");
+    if (flags & kRadFlagNegative) return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a negative mass");
+    if (flags & kRadFlagLarge)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e0) + " is too large for this context's masses and body count");
+    return BH_OK;
+}
+
+// ---- the field at arbitrary points (bh_field.hpp)
+// The tree comes from a quiet build (quietly), with the walk counters of bh_stats copied aside and put back as in
+// check_walk (keys_kernel clears them).  The kernels read the tree and the call's own buffers and write the call's own buffers
+// only: force, body_counts, group_cost, phi, the event timings and walk_launches are not touched.
+int field_alloc(bh_ctx *c, int64_t want)
+{
+    FieldState &s = c->field;
+    if (want <= s.block.cap) return BH_OK;
+    const int64_t cap = grown_capacity(want);                  // (want <= kFieldChunk, a power of two)
+    const size_t n = (size_t)cap, nbl = blocks_for(cap, kBlock * kFieldSortItems);
+    return block_regrow(c, s.block, cap, {part(&s.points, n), part(&s.accel, n), part(&s.keys[0], n), part(&s.keys[1], n),
+                                          part(&s.phi, n), part(&s.order, n), part(&s.counts, n),
+                                          part(&s.radix, (size_t)kRadix * nbl), part(&s.rows, (size_t)kRadix)});
+}
+
+// one launch of k <= field.block.cap points: upload, keys, sort, walk; results at the points' places
+int enqueue_field(bh_ctx *c, const double *points, int64_t k)
+{
+    FieldState &s = c->field;
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(k, kBlock);
+    if (int rc = sorted_query_chunk(c, points, k, s.points, c->box, s.keys, s.order, s.radix, s.rows)) return rc;
+    if (c->tree64()) {
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, c->gd, c->ld, s.order, s.points, k, c->cfg.theta, c->cfg.G, c->eps2,
+                               c->ctr, s.accel, s.phi, s.counts);
+        };
+        if (c->mode == Mode::F64) go(field_f64_kernel<kAcceptThr>);
+        else if (c->exact_thresholds) go(field_f64_kernel<kAcceptExactThr>);
+        else go(field_f64_kernel<kAcceptSize>);
+    } else {
+        hipLaunchKernelGGL(field_f32_kernel, dim3(grid), dim3(kBlock), 0, st, c->qf, c->aux, c->spos, c->smass, s.order, s.points, k,
+                           c->cfg.G, c->eps2f, c->ctr, s.accel, s.phi, s.counts);
+    }
+    BH_HIP(c, hipGetLastError());
+    return BH_OK;
+}
+
+// ---- neighbour queries (bh_neighbours.hpp).  They read pos (and orig) as they lie in memory and write buffers of their own: no
+// force tree, no record of bh_run_state.hpp, no counter and no timing of the run, so a step before and after runs bit for bit as
+// it would have.
+constexpr int64_t kNbChunk = kFieldChunk;       // queries per launch: a point's index travels in its key word
+
+// the structure's block for n bodies and the launch block for `rows` queries of `entries` list entries in all
+int nb_alloc(bh_ctx *c, int64_t n, int64_t rows, int64_t entries)
+{
+    NbState &s = c->nb;
+    if (n > s.block.cap) {
+        const int64_t cap = grown_capacity(n);
+        int32_t off[kNbMaxLevels + 1];
+        nb_levels(cap, off);
+        const size_t nodes = (size_t)off[kNbMaxLevels] + kNbMaxLevels;            // (n <= cap has at most a node more per level)
+        const size_t b = (size_t)cap, nbl = blocks_for(std::max(cap, kNbChunk), kBlock * kFieldSortItems);
+        if (int rc = block_regrow(c, s.block, cap, {part(&s.spos, b), part(&s.boxes, nodes), part(&s.keys[0], b), part(&s.keys[1], b),
+                                                    part(&s.bounds, 1), part(&s.box, 4), part(&s.slot, b), part(&s.sidx, b),
+                                                    part(&s.radix, (size_t)kRadix * nbl), part(&s.rowsum, (size_t)kRadix),
+                                                    part(&s.off, (size_t)kNbMaxLevels + 1)}))
+            return rc;
+    }
+    if (rows > s.qblock.cap || entries > s.entries) {
+        const int64_t cap = grown_capacity(rows, std::max<int64_t>(s.qblock.cap, 1024)), ent = std::max(entries, s.entries);
+        const size_t q = (size_t)cap;
+        s.entries = 0;
+        if (int rc = block_regrow(c, s.qblock, cap, {part(&s.points, q), part(&s.pkeys[0], q), part(&s.pkeys[1], q),
+                                                     part(&s.idx, (size_t)ent), part(&s.d2, (size_t)ent), part(&s.order, q),
+                                                     part(&s.evals, q)}))
+            return rc;
+        s.entries = ent;
+    }
+    return BH_OK;
+}
+
+// bounds, keys, sort, sorted copies and boxes of the current state (n > 0), between the marks nb.ev[0] and nb.ev[1]; BH_ERR_ARG
+// when a position is not finite.  *levels: the levels of the hierarchy.
+int nb_build(bh_ctx *c, const char *who, int *levels)
+{
+    NbState &s = c->nb;
+    hipStream_t st = c->stream;
+    const int64_t n = c->n;
+    const unsigned grid = blocks_for(n, kBlock);
+    const NbBounds empty{~0ull, 0ull, ~0ull, 0ull, 0ull};
+    if (int rc = mark(c, s.ev[0])) return rc;
+    BH_HIP(c, hipMemcpyAsync(s.bounds, &empty, sizeof(empty), hipMemcpyHostToDevice, st));
+    BH_HIP(c, hipStreamSynchronize(st));                        // (`empty` lives on this stack)
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        hipLaunchKernelGGL((nb_bounds_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, static_cast<const Real2 *>(c->pos), n, s.bounds);
+    });
+    BH_HIP(c, hipGetLastError());
+    NbBounds got{};
+    BH_HIP(c, hipMemcpyAsync(&got, s.bounds, sizeof(got), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (got.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": a body of the state has a non-finite position (found by the bounds pass)");
+    hipLaunchKernelGGL(nb_setup_kernel, dim3(1), dim3(1), 0, st, s.bounds, n, s.box, s.off);
+    const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
+    static_assert(kFieldKeyBits % kSortBits == 0 && ((kFieldKeyBits / kSortBits) & 1) == 0, "the sorted keys end in the first array");
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        const Real2 *pos = static_cast<const Real2 *>(c->pos);
+        hipLaunchKernelGGL((nb_keys_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, n, s.box, s.keys[0]);
+        uint32_t *const slot[2] = {s.slot, s.slot};            // (packed: written by the last pass only)
+        enqueue_lsd_passes<kFieldSortItems>(st, s.keys, slot, s.radix, s.rowsum, n, kFieldKeyBits, true);
+        hipLaunchKernelGGL((nb_gather_kernel<Real2>), dim3(grid), dim3(kBlock), 0, st, pos, s.slot, orig, n, s.spos, s.sidx);
+    });
+    int32_t off[kNbMaxLevels + 1];
+    *levels = nb_levels(n, off);
+    hipLaunchKernelGGL(nb_leaf_kernel, dim3(blocks_for(off[1], kBlock)), dim3(kBlock), 0, st, s.spos, n, off[1], s.boxes);
+    for (int l = 1; l < *levels; ++l) {
+        const int32_t count = off[l + 1] - off[l], below = off[l] - off[l - 1];
+        hipLaunchKernelGGL(nb_level_kernel, dim3(blocks_for(count, kBlock)), dim3(kBlock), 0, st, s.boxes + off[l - 1], below,
+                           s.boxes + off[l], count);
+    }
+    BH_HIP(c, hipGetLastError());
+    return mark(c, s.ev[1]);
+}
+
+// a launch's queries, between the marks nb.ev[2] and nb.ev[3]: `rows` of the caller's points from `points` on, sorted, or
+// (points == nullptr) the bodies themselves; then search() enqueues the family's kernel
+template <typename Search>
+int nb_launch(bh_ctx *c, const double *points, int64_t rows, Search &&search)
+{
+    NbState &s = c->nb;
+    if (int rc = mark(c, s.ev[2])) return rc;
+    if (points) { if (int rc = sorted_query_chunk(c, points, rows, s.points, s.box, s.pkeys, s.order, s.radix, s.rowsum)) return rc; }
+    search();
+    BH_HIP(c, hipGetLastError());
+    return mark(c, s.ev[3]);
+}
+
+// Both queries.  k > 0: bh_neighbours; k == 0: bh_count_within at r2.  Rows come back in the launch's sorted order and are put
+// at their caller places here.
+int nb_query(bh_ctx *c, const char *who, const double *points, int64_t n_points, int32_t k, double r2, int64_t *idx, double *d2,
+             uint32_t *evals)
+{
+    NbState &s = c->nb;
+    const std::string w(who);
+    if (int rc = diag_check(c, who)) return rc;
+    if (!points && n_points != c->n) return fail(c, BH_ERR_ARG, w + ": without points, n_points must be the number of bodies");
+    if (int rc = points_finite(c, who, points, n_points)) return rc;
+    if (n_points == 0) return BH_OK;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, w + ": more than 2^24 bodies (their indices share a key word)");
+    const int64_t kk = std::max<int32_t>(k, 1);               // entries per row on the host side (counts: one)
+    if (n == 0) {                                              // no bodies: nobody is near
+        if (idx) std::fill(idx, idx + n_points * kk, (int64_t)-1);
+        if (d2) std::fill(d2, d2 + n_points * kk, (double)INFINITY);
+        if (evals) std::fill(evals, evals + n_points, 0u);
+        return BH_OK;
+    }
+    BH_HIP(c, hipSetDevice(c->device));
+    const int64_t rows_max = std::min(n_points, kNbChunk);
+    if (int rc = nb_alloc(c, n, rows_max, rows_max * k)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, who, &levels)) return rc;
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> dest((size_t)rows_max), hev((size_t)rows_max);
+    std::vector<int64_t> hidx(idx ? (size_t)(rows_max * k) : 0);
+    std::vector<double> hd2(d2 ? (size_t)(rows_max * k) : 0);
+    std::vector<uint32_t> sidx;
+    if (!points) {
+        sidx.resize((size_t)n);
+        BH_HIP(c, hipMemcpyAsync(sidx.data(), s.sidx, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    s.query_ms = 0.0;
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        auto search = [&](auto pts) {
+            constexpr bool PTS = decltype(pts)::value;
+            if (k > 0)
+                hipLaunchKernelGGL((nb_knn_kernel<PTS>), dim3(blocks_for(rows, kWave)), dim3(kWave), (size_t)k * kWave * 12, st, s.spos,
+                                   s.sidx, s.keys[0], s.boxes, s.off, levels, (int32_t)n, k, s.points, s.order, s.pkeys[0], t0, rows, s.idx,
+                                   s.d2, s.evals);
+            else
+                hipLaunchKernelGGL((nb_count_kernel<PTS>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, s.spos, s.boxes, s.off,
+                                   levels, (int32_t)n, s.points, s.order, t0, rows, r2, s.evals);
+        };
+        if (int rc = nb_launch(c, points ? points + 2 * t0 : nullptr, rows, [&] { dispatch(search, points != nullptr); })) return rc;
+        if (points) BH_HIP(c, hipMemcpyAsync(dest.data(), s.order, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (idx) BH_HIP(c, hipMemcpyAsync(hidx.data(), s.idx, (size_t)(rows * k) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (d2) BH_HIP(c, hipMemcpyAsync(hd2.data(), s.d2, (size_t)(rows * k) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (evals) BH_HIP(c, hipMemcpyAsync(hev.data(), s.evals, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+        if (int rc = span_ms(c, s.ev[2], s.ev[3], &s.query_ms, true)) return rc;
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t at = points ? t0 + (int64_t)dest[(size_t)r] : (int64_t)sidx[(size_t)(t0 + r)];
+            if (idx) std::copy(hidx.begin() + r * k, hidx.begin() + (r + 1) * k, idx + at * k);
+            if (d2) std::copy(hd2.begin() + r * k, hd2.begin() + (r + 1) * k, d2 + at * k);
+            if (evals) evals[at] = hev[(size_t)r];
+        }
+    }
+    return span_ms(c, s.ev[0], s.ev[1], &s.build_ms);
+}
+
+// ---- friends-of-friends groups (bh_groups.hpp) on the structure of the neighbour queries.  They read pos, vel, mass and orig as
+// they lie in memory and write buffers of their own: a step before and after runs bit for bit as it would have.
+int fof_alloc(bh_ctx *c, int64_t n)
+{
+    FofState &s = c->fof;
+    if (n <= s.block.cap) return BH_OK;
+    const size_t b = (size_t)grown_capacity(n);
+    return block_regrow(c, s.block, (int64_t)b, {part(&s.sums, b * kGrpPlanes), part(&s.label, b), part(&s.ctr, 1), part(&s.max, 1),
+                                                 part(&s.parent, b), part(&s.root, b), part(&s.minidx, b), part(&s.count, b),
+                                                 part(&s.rec_label, b), part(&s.rec_count, b)});
+}
+
+}  // namespace
+
+extern "C" {
+
+int bh_moment_map_max(bh_ctx *c, double *maxabs)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_moment_map_max: null output");
+    if (int rc = need_upload(c, "bh_moment_map_max before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kMapPlanes];
+    if (int rc = map_maxima(c, "bh_moment_map_max", m)) return rc;
+    std::copy(m, m + kMapPlanes, maxabs);
+    return BH_OK;
+}
+
+int bh_moment_map_deposit(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, const int32_t *exponents,
+                          void **planes_dev, int64_t *n_deposited)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!exponents || !planes_dev || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map_deposit: null argument");
+    int32_t e[kMapPlanes];
+    if (int rc = map_passes(c, "bh_moment_map_deposit", box, nx, ny, scheme, exponents, e, n_deposited)) return rc;
+    *planes_dev = c->map.planes;
+    return BH_OK;
+}
+
+int bh_moment_map(bh_ctx *c, const double *box, int32_t nx, int32_t ny, int32_t scheme, int64_t *planes, int32_t *exponents,
+                  int64_t *n_deposited)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents || !n_deposited) return fail(c, BH_ERR_ARG, "bh_moment_map: null argument");
+    int32_t e[kMapPlanes];
+    if (int rc = map_passes(c, "bh_moment_map", box, nx, ny, scheme, nullptr, e, n_deposited)) return rc;
+    BH_HIP(c, hipMemcpy(planes, c->map.planes, (size_t)kMapPlanes * nx * ny * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kMapPlanes, exponents);
+    return BH_OK;
+}
+
+int bh_radial_max(bh_ctx *c, const double *centre, const double *centre_vel, double *maxabs)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_radial_max: null output");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_radial_max", centre, centre_vel, &ctr)) return rc;
+    if (int rc = need_upload(c, "bh_radial_max before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_radial_max", ctr, true, false, m)) return rc;
+    std::copy(m, m + kRadPlanes, maxabs);
+    return BH_OK;
+}
+
+int bh_radial_deposit(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb,
+                      const int32_t *exponents, void **planes_dev)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!exponents || !planes_dev) return fail(c, BH_ERR_ARG, "bh_radial_deposit: null argument");
+    int32_t e[kRadPlanes];
+    if (int rc = rad_passes(c, "bh_radial_deposit", centre, centre_vel, edges, nb, exponents, e)) return rc;
+    *planes_dev = c->rad.planes;
+    return BH_OK;
+}
+
+int bh_radial_profile(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int64_t *planes,
+                      int32_t *exponents)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_radial_profile: null argument");
+    int32_t e[kRadPlanes];
+    if (int rc = rad_passes(c, "bh_radial_profile", centre, centre_vel, edges, nb, nullptr, e)) return rc;
+    BH_HIP(c, hipMemcpy(planes, c->rad.planes, (size_t)(kRadPlanes + 1) * (nb + 2) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kRadPlanes, exponents);
+    return BH_OK;
+}
+
+int bh_radial_select(bh_ctx *c, const double *centre, int32_t exponent, int32_t round, const uint64_t *prefixes, int32_t np,
+                     void **hist_dev)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!hist_dev) return fail(c, BH_ERR_ARG, "bh_radial_select: null output");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_radial_select", centre, nullptr, &ctr)) return rc;
+    if (const char *why = select_prefix_fault(round, prefixes, np)) return fail(c, BH_ERR_ARG, std::string("bh_radial_select: ") + why);
+    if (int rc = need_upload(c, "bh_radial_select before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    c->rad.max_ms = 0.0; c->rad.main_ms = 0.0;
+    for (double &v : c->rad.round_ms) v = 0.0;
+    if (int rc = rad_select_round(c, "bh_radial_select", ctr, exponent, round, prefixes, np)) return rc;
+    c->rad.main_ms = c->rad.round_ms[round];
+    *hist_dev = c->rad.hist;
+    return BH_OK;
+}
+
+int bh_lagrangian_radii(bh_ctx *c, const double *centre, const double *fractions, int32_t nf, double *r2, int64_t *count, int64_t *mass,
+                        int32_t *exponent)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!fractions || !r2 || !count || !mass || !exponent) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: null argument");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_lagrangian_radii", centre, nullptr, &ctr)) return rc;
+    if (nf < 1 || nf > kRadMaxFractions) return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: nf must be 1 .. BH_RADIAL_MAX_FRACTIONS = 32");
+    for (int32_t f = 0; f < nf; ++f)
+        if (!(std::isfinite(fractions[f]) && fractions[f] > 0.0 && fractions[f] <= 1.0))
+            return fail(c, BH_ERR_ARG, "bh_lagrangian_radii: a fraction must be finite, > 0 and <= 1");
+    if (int rc = need_upload(c, "bh_lagrangian_radii before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[kRadPlanes];
+    if (int rc = rad_maxima(c, "bh_lagrangian_radii", ctr, false, true, m)) return rc;
+    const int32_t e0 = plane_exponent(m[0], log2_ceil(c->n));
+    *exponent = e0;
+    c->rad.main_ms = 0.0;
+    for (double &v : c->rad.round_ms) v = 0.0;
+    // the decisions between the rounds are made here, on the host, from the downloaded histograms
+    LagrangianSelect sel(fractions, nf);
+    std::vector<int64_t> hist((size_t)kRadMaxFractions * kRadDigits * 2);
+    while (!sel.done()) {
+        const int32_t round = sel.round;
+        const uint64_t *distinct = nullptr;
+        const int32_t np = sel.prefixes(&distinct);
+        if (int rc = rad_select_round(c, "bh_lagrangian_radii", ctr, e0, round, distinct, np)) return rc;
+        c->rad.main_ms += c->rad.round_ms[round];
+        BH_HIP(c, hipMemcpy(hist.data(), c->rad.hist, (size_t)np * kRadDigits * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        sel.advance(hist.data());
+    }
+    sel.result(r2, count, mass);
+    return BH_OK;
+}
+
+int bh_radial_times(bh_ctx *c, double *max_ms, double *main_ms, double *rounds_ms)
+{
+    if (!c || !max_ms || !main_ms) return fail(c, BH_ERR_ARG, "bh_radial_times: null argument");
+    *max_ms = c->rad.max_ms;
+    *main_ms = c->rad.main_ms;
+    if (rounds_ms) std::copy(c->rad.round_ms, c->rad.round_ms + kRadRounds, rounds_ms);
+    return BH_OK;
+}
+
+int bh_field_at(bh_ctx *c, const double *points, int64_t n_points, double *accel, double *phi, uint32_t *counts)
+{
+    if (!c) return BH_ERR_ARG;
+    if (n_points < 0 || (n_points > 0 && !points) || (!accel && !phi && !counts))
+        return fail(c, BH_ERR_ARG, "bh_field_at: n_points < 0, null points or no output array");
+    if (int rc = diag_check(c, "bh_field_at")) return rc;
+    if (int rc = points_finite(c, "bh_field_at", points, n_points)) return rc;
+    if (n_points == 0) return BH_OK;
+    if (c->n == 0) {                                           // no bodies: no field, no terms
+        if (accel) std::fill(accel, accel + 2 * n_points, 0.0);
+        if (phi) std::fill(phi, phi + n_points, 0.0);
+        if (counts) std::fill(counts, counts + n_points, 0u);
+        return BH_OK;
+    }
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = field_alloc(c, std::min(n_points, kFieldChunk))) return rc;
+    int rc = quietly(c, kQuietCounters, [&] { return enqueue_build(c, false); });
+    if (!rc) rc = check_overflow(c);
+    if (rc) return rc;
+    const FieldState &s = c->field;
+    for (int64_t t0 = 0; t0 < n_points; t0 += kFieldChunk) {
+        const int64_t k = std::min(kFieldChunk, n_points - t0);
+        if ((rc = enqueue_field(c, points + 2 * t0, k))) return rc;
+        if (accel) BH_HIP(c, hipMemcpyAsync(accel + 2 * t0, s.accel, (size_t)k * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        if (phi) BH_HIP(c, hipMemcpyAsync(phi + t0, s.phi, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (counts) BH_HIP(c, hipMemcpyAsync(counts + t0, s.counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        BH_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return BH_OK;
+}
+
+int bh_neighbours(bh_ctx *c, const double *points, int64_t n_points, int32_t k, int64_t *idx, double *d2, uint32_t *evals)
+{
+    if (!c) return BH_ERR_ARG;
+    if (k < 1 || k > kNbMaxK) return fail(c, BH_ERR_ARG, "bh_neighbours: k must be 1 .. BH_NEIGHBOURS_MAX_K = 32");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_neighbours: n_points < 0");
+    if (!idx && !d2) return fail(c, BH_ERR_ARG, "bh_neighbours: no output array (idx and d2 are both null)");
+    return nb_query(c, "bh_neighbours", points, n_points, k, 0.0, idx, d2, evals);
+}
+
+int bh_count_within(bh_ctx *c, const double *points, int64_t n_points, double radius, uint32_t *counts)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(c, BH_ERR_ARG, "bh_count_within: the radius must be finite and >= 0");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_count_within: n_points < 0");
+    if (!counts) return fail(c, BH_ERR_ARG, "bh_count_within: null counts");
+    return nb_query(c, "bh_count_within", points, n_points, 0, radius * radius, nullptr, nullptr, counts);
+}
+
+int bh_neighbours_times(bh_ctx *c, double *build_ms, double *query_ms)
+{
+    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_neighbours_times: null argument");
+    *build_ms = c->nb.build_ms;
+    *query_ms = c->nb.query_ms;
+    return BH_OK;
+}
+
+// ---- pair counts (bh_pairs.hpp) on the structure of the neighbour queries.  They read pos as it lies in memory and write buffers
+// of their own: a step before and after runs bit for bit as it would have.  Allowed in LET mode and with world > 1: the
+// bodies are this context's own.
+int bh_pair_counts(bh_ctx *c, const double *points, int64_t n_points, const double *edges, int32_t nb, int64_t *counts, int64_t *evals)
+{
+    if (!c) return BH_ERR_ARG;
+    if (nb < 1 || nb > kPairMaxBins) return fail(c, BH_ERR_ARG, "bh_pair_counts: 1 .. BH_PAIR_MAX_BINS = 1024 bins");
+    if (!edges || !counts) return fail(c, BH_ERR_ARG, "bh_pair_counts: null edges or counts");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, "bh_pair_counts: n_points < 0");
+    std::vector<double> e2;
+    if (const unsigned why = squared_edges(edges, nb, kPairMaxBins, e2)) {
+        if (why & (kEdgeNotFinite | kEdgeNegative | kEdgeNotAscending))
+            return fail(c, BH_ERR_ARG, "bh_pair_counts: the edges must be finite, >= 0 and strictly ascending");
+        return fail(c, BH_ERR_ARG, "bh_pair_counts: the squared edges must be finite and strictly ascending");
+    }
+    if (int rc = need_upload(c, "bh_pair_counts before bh_upload/bh_initialize")) return rc;
+    const int64_t n = c->n;
+    if (!points && n_points != n) return fail(c, BH_ERR_ARG, "bh_pair_counts: without points, n_points must be the number of bodies");
+    if (int rc = points_finite(c, "bh_pair_counts", points, n_points)) return rc;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_pair_counts: more than 2^24 bodies (their indices share a key word)");
+    std::fill(counts, counts + nb + 2, (int64_t)0);
+    if (evals) *evals = 0;
+    NbState &s = c->nb;
+    PairState &pr = c->pair;
+    pr.build_ms = pr.query_ms = 0.0;
+    if (n == 0 || n_points == 0) return BH_OK;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, points ? std::min(n_points, kNbChunk) : 0, 0)) return rc;
+    if (!pr.e2) { if (int rc = alloc_all(c, {part(&pr.e2, (size_t)kPairMaxBins + 1), part(&pr.hist, (size_t)kPairMaxBins + 3)})) return rc; }
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_pair_counts", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const size_t words = (size_t)nb + 3;                       // the bins, then the evals word
+    BH_HIP(c, hipMemcpyAsync(pr.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    BH_HIP(c, hipMemsetAsync(pr.hist, 0, words * sizeof(unsigned long long), st));
+    const size_t lds = (2 * (size_t)nb + 4) * sizeof(unsigned long long);
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        auto search = [&](auto pts) {
+            hipLaunchKernelGGL((pair_count_kernel<decltype(pts)::value>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), lds, st, s.spos,
+                               s.boxes, s.off, levels, (int32_t)n, s.points, s.order, t0, rows, pr.e2, nb, pr.hist, pr.hist + nb + 2);
+        };
+        if (int rc = nb_launch(c, points ? points + 2 * t0 : nullptr, rows, [&] { dispatch(search, points != nullptr); })) return rc;
+        BH_HIP(c, hipStreamSynchronize(st));                    // (the next chunk overwrites the points; the events are read here)
+        if (int rc = span_ms(c, s.ev[2], s.ev[3], &pr.query_ms, true)) return rc;
+    }
+    std::vector<unsigned long long> got(words);
+    BH_HIP(c, hipMemcpyAsync(got.data(), pr.hist, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    for (int32_t k = 0; k < nb + 2; ++k) counts[k] = (int64_t)got[(size_t)k];
+    if (evals) *evals = (int64_t)got[(size_t)nb + 2];
+    return span_ms(c, s.ev[0], s.ev[1], &pr.build_ms);
+}
+
+int bh_pair_counts_times(bh_ctx *c, double *build_ms, double *query_ms)
+{
+    if (!c || !build_ms || !query_ms) return fail(c, BH_ERR_ARG, "bh_pair_counts_times: null argument");
+    *build_ms = c->pair.build_ms;
+    *query_ms = c->pair.query_ms;
+    return BH_OK;
+}
+
+int bh_groups(bh_ctx *c, double linking_length, int64_t min_members, int64_t *label, int64_t *n_groups, int64_t *n_catalogue,
+              uint64_t *stats)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(linking_length >= 0.0) || !std::isfinite(linking_length))
+        return fail(c, BH_ERR_ARG, "bh_groups: the linking length must be finite and >= 0");
+    if (min_members < 1) return fail(c, BH_ERR_ARG, "bh_groups: min_members must be at least 1");
+    if (!n_groups) return fail(c, BH_ERR_ARG, "bh_groups: null n_groups");
+    if (int rc = diag_check(c, "bh_groups")) return rc;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_groups: more than 2^24 bodies (their indices share a key word)");
+    NbState &nb = c->nb;
+    FofState &s = c->fof;
+    s.cat_labels.clear(); s.cat_counts.clear(); s.cat_sums.clear();
+    std::fill(s.cat_exp, s.cat_exp + kGrpPlanes, 0);
+    s.build_ms = s.link_ms = s.cat_ms = 0.0;
+    *n_groups = 0;
+    if (n_catalogue) *n_catalogue = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (n == 0) return BH_OK;
+    const double b2 = linking_length * linking_length;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, 0, 0)) return rc;
+    if (int rc = fof_alloc(c, n)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_groups", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(n, kBlock);
+    const int32_t n32 = (int32_t)n;
+    const uint32_t least = (uint32_t)std::min<int64_t>(min_members, (int64_t)UINT32_MAX);
+    BH_HIP(c, hipMemsetAsync(s.ctr, 0, sizeof(GrpCounters), st));
+    BH_HIP(c, hipMemsetAsync(s.minidx, 0xff, (size_t)n * sizeof(uint32_t), st));
+    BH_HIP(c, hipMemsetAsync(s.count, 0, (size_t)n * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(grp_init_kernel, dim3(grid), dim3(kBlock), 0, st, nb.boxes, nb.off, levels, n32, b2, s.parent, s.ctr);
+    hipLaunchKernelGGL(grp_link_kernel, dim3(grid), dim3(kBlock), 0, st, nb.spos, nb.boxes, nb.off, levels, n32, b2, s.parent, s.ctr);
+    hipLaunchKernelGGL(grp_flatten_kernel, dim3(grid), dim3(kBlock), 0, st, s.parent, nb.sidx, n32, s.root, s.minidx, s.count, s.ctr);
+    hipLaunchKernelGGL(grp_label_kernel, dim3(grid), dim3(kBlock), 0, st, s.root, s.minidx, nb.sidx, n32, s.label);
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[0])) return rc;
+    GrpExp ex{};
+    GrpCounters ctr{};
+    if (n_catalogue) {
+        BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(GrpMax), st));
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            hipLaunchKernelGGL((grp_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(grid), dim3(kBlock), 0, st, pos, vel,
+                               mass, n, s.max);
+        });
+        // (gid: the parents are not read any more)
+        hipLaunchKernelGGL(grp_compact_kernel, dim3(grid), dim3(kBlock), 0, st, s.root, s.minidx, s.count, n32, least, s.parent,
+                           s.rec_label, s.rec_count, s.ctr);
+        BH_HIP(c, hipGetLastError());
+        GrpMax mx{};
+        double m[kGrpPlanes];
+        if (int rc = read_maxima(c, s.max, &mx, m, &ctr, s.ctr, sizeof(ctr))) return rc;
+        if (mx.bad)
+            return fail(c, BH_ERR_ARG, "bh_groups: a body has a non-finite velocity or mass (or a moment m x, m v that overflows fp64)");
+        const int L = log2_ceil(n);
+        for (int p = 0; p < kGrpPlanes; ++p) ex.e[p] = plane_exponent(m[p], L);
+    } else {
+        BH_HIP(c, hipMemcpyAsync(&ctr, s.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+    }
+    const int64_t kept = (int64_t)ctr.kept;
+    if (n_catalogue && kept > 0) {
+        BH_HIP(c, hipMemsetAsync(s.sums, 0, (size_t)kept * kGrpPlanes * sizeof(unsigned long long), st));
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            hipLaunchKernelGGL((grp_sum_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(grid), dim3(kBlock), 0, st, pos, vel,
+                               mass, nb.slot, s.root, s.count, s.parent, n32, least, ex, s.sums);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[1])) return rc;
+    std::vector<uint32_t> rl((size_t)kept), rc_((size_t)kept);
+    std::vector<int64_t> sums((size_t)kept * kGrpPlanes);
+    if (kept > 0) {
+        BH_HIP(c, hipMemcpyAsync(rl.data(), s.rec_label, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(rc_.data(), s.rec_count, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(sums.data(), s.sums, sums.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (label) BH_HIP(c, hipMemcpyAsync(label, s.label, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (int rc = span_ms(c, nb.ev[0], nb.ev[1], &s.build_ms)) return rc;
+    if (int rc = span_ms(c, nb.ev[1], s.ev[0], &s.link_ms)) return rc;
+    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.cat_ms)) return rc;
+    catalogue_order(rl.data(), rc_.data(), sums.data(), kept, kGrpPlanes, s.cat_labels, s.cat_counts, s.cat_sums);
+    std::copy(ex.e, ex.e + kGrpPlanes, s.cat_exp);
+    *n_groups = (int64_t)ctr.roots;
+    if (n_catalogue) *n_catalogue = kept;
+    if (stats) { stats[0] = ctr.evals; stats[1] = ctr.pairs; stats[2] = ctr.hooks; }
+    return BH_OK;
+}
+
+int bh_groups_catalogue(bh_ctx *c, int64_t max_records, int64_t *labels, int64_t *counts, int64_t *sums, int32_t *exponents,
+                        int64_t *n_out)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!n_out || max_records < 0) return fail(c, BH_ERR_ARG, "bh_groups_catalogue: null n_out or max_records < 0");
+    const FofState &s = c->fof;
+    const int64_t g = (int64_t)s.cat_labels.size();
+    *n_out = g;
+    if (exponents) std::copy(s.cat_exp, s.cat_exp + kGrpPlanes, exponents);
+    if (g > max_records) return fail(c, BH_ERR_CAPACITY, "bh_groups_catalogue: the catalogue has " + std::to_string(g) + " records");
+    if (labels) std::copy(s.cat_labels.begin(), s.cat_labels.end(), labels);
+    if (counts) std::copy(s.cat_counts.begin(), s.cat_counts.end(), counts);
+    if (sums) std::copy(s.cat_sums.begin(), s.cat_sums.end(), sums);
+    return BH_OK;
+}
+
+int bh_groups_times(bh_ctx *c, double *build_ms, double *link_ms, double *catalogue_ms)
+{
+    if (!c || !build_ms || !link_ms || !catalogue_ms) return fail(c, BH_ERR_ARG, "bh_groups_times: null argument");
+    *build_ms = c->fof.build_ms;
+    *link_ms = c->fof.link_ms;
+    *catalogue_ms = c->fof.cat_ms;
+    return BH_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,88 @@
+// bh_queries_state.hpp -- what the context keeps for the analysis queries of bh_queries_host.hpp, one struct per family
+// (bh_ctx has one member of each).  Everything is allocated on first use and lives as long as the context.  Part of the
+// bh_engine.hip translation unit, included there after the kernels' headers and before bh_ctx -- bh_queries_host.hpp needs the
+// whole context and comes after it: hence a header of its own.
+#pragma once
+
+namespace bh {
+
+// a grow-only device allocation carved into arrays for up to `cap` items (block_regrow)
+struct DevBlock {
+    char *base = nullptr;
+    uint64_t bytes = 0;
+    int64_t cap = 0;
+};
+
+// moment maps (bh_moments.hpp): the first pass's record, the body counter, and the 4-plane int64 grid, which grows to the
+// largest map asked for (`cells` of them per plane)
+struct MapState {
+    MapMax *max = nullptr;
+    unsigned long long *count = nullptr;
+    long long *planes = nullptr;
+    int64_t cells = 0;
+};
+
+// radial profiles and Lagrangian radii (bh_radial.hpp): the first pass's record, the select's flags, the squared edges, the
+// 6-plane int64 profile of up to BH_RADIAL_MAX_BINS + 2 slots, a round's histograms
+struct RadState {
+    RadMax *max = nullptr;
+    unsigned long long *flags = nullptr;
+    double *e2 = nullptr;
+    long long *planes = nullptr, *hist = nullptr;
+    int blocks = 512;                  // BH_RADIAL_BLOCKS: most persistent workgroups of the radial kernels
+    hipEvent_t ev[4 + 2 * kRadRounds] = {};                 // around the first pass, the deposit, and every select round
+    double max_ms = 0.0, main_ms = 0.0, round_ms[kRadRounds] = {};     // of the last call (bh_radial_times)
+};
+
+// the field at arbitrary points (bh_field.hpp): one block for a launch of up to block.cap points -- the points, their results, two
+// key arrays and the sorted order, the sort's count matrix and row totals
+struct FieldState {
+    DevBlock block;
+    double2 *points = nullptr, *accel = nullptr;
+    uint64_t *keys[2] = {nullptr, nullptr};
+    double *phi = nullptr;
+    uint32_t *order = nullptr, *counts = nullptr, *radix = nullptr, *rows = nullptr;
+};
+
+// neighbour queries (bh_neighbours.hpp), grown as the field's block: one block for the search structure of up to block.cap
+// bodies, one for a launch of up to qblock.cap queries with `entries` list entries in all.  Pair counts and groups build and search the
+// same structure and mark the same events.
+struct NbState {
+    DevBlock block, qblock;
+    int64_t entries = 0;
+    uint64_t *keys[2] = {nullptr, nullptr}, *pkeys[2] = {nullptr, nullptr};
+    uint32_t *slot = nullptr, *sidx = nullptr, *radix = nullptr, *rowsum = nullptr, *order = nullptr, *evals = nullptr;
+    double2 *spos = nullptr, *points = nullptr;
+    NbBox *boxes = nullptr;
+    NbBounds *bounds = nullptr;
+    double *box = nullptr, *d2 = nullptr;
+    int32_t *off = nullptr;
+    int64_t *idx = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};    // around the build and around a launch's sort and search
+    double build_ms = 0.0, query_ms = 0.0;                      // of the last call (bh_neighbours_times)
+};
+
+// pair counts (bh_pairs.hpp): the squared edges, then the int64 histogram and the evals word
+struct PairState {
+    double *e2 = nullptr;
+    unsigned long long *hist = nullptr;
+    double build_ms = 0.0, query_ms = 0.0;                      // of the last call (bh_pair_counts_times)
+};
+
+// friends-of-friends groups (bh_groups.hpp): one block for up to block.cap bodies beside the neighbour structure's, and the
+// catalogue of the last bh_groups call on the host (no record of bh_run_state.hpp: it is that call's result, whatever the run
+// does afterwards)
+struct FofState {
+    DevBlock block;
+    uint32_t *parent = nullptr, *root = nullptr, *minidx = nullptr, *count = nullptr, *rec_label = nullptr, *rec_count = nullptr;
+    long long *label = nullptr;
+    unsigned long long *sums = nullptr;
+    GrpCounters *ctr = nullptr;
+    GrpMax *max = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};                      // after the labels, after the catalogue
+    double build_ms = 0.0, link_ms = 0.0, cat_ms = 0.0;         // of the last call (bh_groups_times)
+    std::vector<int64_t> cat_labels, cat_counts, cat_sums;
+    int32_t cat_exp[kGrpPlanes] = {0, 0, 0, 0, 0};
+};
+
+}  // namespace bh

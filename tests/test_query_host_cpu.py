@@ -1,0 +1,188 @@
+"""csrc/bh_query_host.hpp -- the host arithmetic of the analysis queries -- compiles with the plain host compiler, includes nothing
+of HIP, and agrees with the Python side of the project when tests/query_host_replay.cpp runs it on its own: the fixed-point
+exponent rule with engine.moment_exponents / radial_exponents, the squared edges with the conditions of the two callers (a reason
+per case, from reading them), the Lagrangian select with engine.LagrangianSelect round by round, the catalogue's order with
+sorted(), and the block layout with its own counting pass."""
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from gpu_nbody_simulation_amd import engine as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gpu-nbody-simulation_amd", "csrc")
+HEADER = os.path.join(CSRC, "bh_query_host.hpp")
+REPLAY = os.path.join(ROOT, "tests", "query_host_replay.cpp")
+
+FRACTIONS = (1e-9, 0.01, 0.5, 0.5, 1.0)
+# squared_edges' reasons (bh_query_host.hpp)
+COUNT, NOT_FINITE, SQ_NOT_FINITE, NEGATIVE, NOT_ASCENDING, SQ_NOT_ASCENDING = 1, 2, 4, 8, 16, 32
+
+
+def select_bodies():
+    """300 squared radii with exact duplicates, and integer weights; fixed seed"""
+    rng = np.random.default_rng(20)
+    r2 = rng.lognormal(0.0, 3.0, 300)
+    r2[50:80] = r2[10]                       # thirty bodies on one radius
+    r2[200:203] = r2[299]
+    r2[7] = 0.0
+    w = rng.integers(1, 1000, 300).astype(np.int64)
+    return r2.view(np.uint64).copy(), w
+
+
+@pytest.fixture(scope="module")
+def replay(tmp_path_factory):
+    """the program's lines, split into words, by their first word"""
+    tmp = tmp_path_factory.mktemp("query_host")
+    exe = tmp / "query_host_replay"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, "-o", str(exe), REPLAY])
+    bits, w = select_bodies()
+    bodies = tmp / "bodies.txt"
+    bodies.write_text("".join(f"{int(b):x} {int(m)}\n" for b, m in zip(bits, w)))
+    r = subprocess.run([str(exe), str(bodies)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = {}
+    for line in r.stdout.splitlines():
+        words = line.split()
+        lines.setdefault(words[0], []).append(words[1:])
+    return lines
+
+
+def test_header_is_hip_free():
+    src = open(HEADER).read()
+    assert not re.search(r'#\s*include\s*[<"]hip/|__global__|__device__|hipStream', src)
+    assert not re.search(r"\bhip[A-Z_]|bh_ctx", src)
+    assert re.findall(r'#\s*include\s*([<"][^>"]+[>"])', src) == ["<algorithm>", "<cmath>", "<cstddef>", "<cstdint>", "<cstring>",
+                                                                  "<initializer_list>", "<vector>"]
+    assert re.findall(r'#\s*include\s*([<"][^>"]+[>"])', open(REPLAY).read()) == ['"bh_query_host.hpp"', "<cinttypes>", "<cstdio>",
+                                                                                 "<limits>"]
+
+
+def test_exponent_rule(replay):
+    maxima = [0.0, 5e-324, 2.2250738585072014e-308, 1.0, np.nextafter(2.0, 0.0), 2.0, 1.7976931348623157e308]
+    counts = [0, 1, 2, 3, 2**24, 2**24 + 1]
+    rows = replay["exp"]
+    assert len(rows) == len(maxima) * len(counts)
+    for row, (m, n) in zip(rows, [(m, n) for m in maxima for n in counts]):
+        assert int(row[0], 16) == int(np.float64(m).view(np.uint64)) and int(row[1]) == n
+        L = 0 if n <= 1 else (n - 1).bit_length()
+        assert int(row[2]) == L
+        assert int(row[3]) == int(E.moment_exponents([m] * 4, n)[0]) == int(E.radial_exponents([m, 0.0, m], n)[2]), (m, n)
+        most = 62 - math.frexp(m)[1] - L
+        assert int(row[4]) == most, (m, n)
+        assert "at-most-differs" not in row
+        for word in row[5:]:
+            e, fits = (int(x) for x in word.split(":"))
+            assert fits == int(m == 0.0 or e <= most), (m, n, e)
+        assert [int(w.split(":")[0]) for w in row[5:]] == [most - 1, most, most + 1, -2000, 2000]
+
+
+def test_squared_edges(replay):
+    """The reason of every case, read off rad_edges and bh_pair_counts as they were before the two shared this routine: both stop
+    at the first edge k with any of the five conditions, and word that edge's conditions by their own priority."""
+    want = {
+        "unit": 0, "small_middle": 0,
+        # 1e-200 squared is 0, not above the square of the first edge, 0: rejected by both callers at k = 1 -- also when a
+        # third edge follows
+        "square_underflows_middle": SQ_NOT_ASCENDING, "square_underflows": SQ_NOT_ASCENDING,
+        "square_overflows": SQ_NOT_FINITE,
+        "negative": NEGATIVE, "negative_overflowing": NEGATIVE | SQ_NOT_FINITE,
+        "equal": NOT_ASCENDING | SQ_NOT_ASCENDING, "descending": NOT_ASCENDING | SQ_NOT_ASCENDING,
+        "nan": NOT_FINITE | SQ_NOT_FINITE | NOT_ASCENDING | SQ_NOT_ASCENDING,
+        "no_bins": COUNT, "too_many_bins": COUNT,
+    }
+    got = {row[0]: row[1:] for row in replay["edges"]}
+    assert {k: int(v[0]) for k, v in got.items()} == want
+    sq = lambda name: np.array([int(x, 16) for x in got[name][1:]], dtype=np.uint64).view(np.float64).tolist()
+    assert sq("unit") == [0.0, 1.0] and sq("small_middle") == [0.0, 1e-150 * 1e-150, 1.0]
+
+    # the two callers' wording of a reason, by their own priorities
+    def radial(why):
+        return ("count" if why & COUNT else "not finite" if why & (NOT_FINITE | SQ_NOT_FINITE) else "negative" if why & NEGATIVE
+                else "not ascending" if why else None)
+
+    def pairs(why):
+        return "edges" if why & (NOT_FINITE | NEGATIVE | NOT_ASCENDING) else "squared edges" if why else None
+
+    assert radial(want["negative_overflowing"]) == "not finite" and pairs(want["negative_overflowing"]) == "edges"
+    assert radial(want["square_underflows"]) == "not ascending" and pairs(want["square_underflows"]) == "squared edges"
+    assert radial(want["square_overflows"]) == "not finite" and pairs(want["square_overflows"]) == "squared edges"
+    assert radial(want["nan"]) == "not finite" and pairs(want["nan"]) == "edges"
+
+
+def test_points_and_select_arguments(replay):
+    assert [int(x) for x in replay["points"][0]] == [-1, 1, 0, -1, -1]
+    # the texts of bh_radial_select's refusals, in the order its rules are tested
+    rnd, null, count = "round must be 0 .. 7", "null prefixes", "np must be 1 .. BH_RADIAL_MAX_FRACTIONS"
+    zero, digits, distinct = "round 0 has the one prefix 0", "a prefix has more digits than the round", "the prefixes must be distinct"
+    assert [" ".join(r) for r in replay["select_args"]] == ["-", rnd, rnd, null, count, count, zero, zero, digits, "-", distinct, "-"]
+
+
+def select_histograms(bits, w, rnd, prefixes):
+    hist = np.zeros((len(prefixes), 256, 2), dtype=np.int64)
+    digit = ((bits >> np.uint64(64 - 8 * (rnd + 1))) & np.uint64(255)).astype(np.int64)
+    for k, p in enumerate(prefixes):
+        mine = np.ones(len(bits), dtype=bool) if rnd == 0 else (bits >> np.uint64(64 - 8 * rnd)) == np.uint64(p)
+        np.add.at(hist[k, :, 0], digit[mine], w[mine])
+        np.add.at(hist[k, :, 1], digit[mine], 1)
+    return hist
+
+
+@pytest.mark.parametrize("name", ["weighted", "massless"])
+def test_lagrangian_select(replay, name):
+    bits, w = select_bodies()
+    if name == "massless":
+        w = np.zeros_like(w)
+    rows = [r[1:] for r in replay["select"] if r[0] == name]
+    rounds = [r for r in rows if r[0] == "round"]
+    results = [r[1:] for r in rows if r[0] == "result"]
+    sel = E.LagrangianSelect(FRACTIONS)
+    k = 0
+    while not sel.done:
+        pre = sel.prefixes()
+        assert int(rounds[k][1]) == k and [int(x, 16) for x in rounds[k][2:]] == pre, k
+        sel.advance(select_histograms(bits, w, k, pre))
+        k += 1
+    assert len(rounds) == k == (8 if name == "weighted" else 1)
+    r2, count, mass = sel.result()
+    assert len(results) == len(FRACTIONS)
+    got_bits = np.array([int(r[0], 16) for r in results], dtype=np.uint64)
+    if name == "massless":
+        assert np.isnan(got_bits.view(np.float64)).all() and np.isnan(r2).all()
+    else:
+        assert np.array_equal(got_bits, r2.view(np.uint64))
+        # (and they are what a sort gives: the smallest radius whose bodies hold the fraction of the weight)
+        order = np.argsort(bits, kind="stable")
+        cum = np.cumsum(w[order])
+        for f, frac in enumerate(FRACTIONS):
+            target = min(int(cum[-1]), max(1, math.ceil(frac * float(cum[-1]))))
+            assert int(got_bits[f]) == int(bits[order][np.searchsorted(cum, target)])
+    assert [int(r[1]) for r in results] == count.tolist() and [int(r[2]) for r in results] == mass.tolist()
+
+
+def test_catalogue_order(replay):
+    rec = [tuple(int(x) for x in r) for r in replay["cat_in"]]
+    out = [tuple(int(x) for x in r) for r in replay["cat_out"]]
+    assert len(rec) == 7 and len({r[1] for r in rec}) < 7                   # tied counts
+    assert out == sorted(rec, key=lambda r: (-r[1], r[0]))
+    assert replay["cat_empty"] == [["0", "0", "0"]]
+
+
+def test_block_layout(replay):
+    assert replay["layout_before"] == [["1"]]                                # the counting pass sets no pointer
+    row = replay["layout"][0]
+    total, again, base_mod = int(row[0]), int(row[1]), int(row[2])
+    parts = [tuple(int(x) for x in w.split(":")) for w in row[3:]]
+    assert [b for _, b in parts] == [1, 3, 16, 17, 20, 0] and base_mod == 0 and total == again
+    end = 0
+    for at, nbytes in parts:
+        assert at % 16 == 0 and at >= end                                    # aligned, and past the part before
+        end = at + nbytes
+    last_at, last_bytes = parts[-1]
+    assert total == last_at + (last_bytes + 15) // 16 * 16
+    assert total == sum((b + 15) // 16 * 16 for _, b in parts)               # exact: no slack
+    assert [int(x) for x in replay["capacity"][0]] == [1024, 1024, 2048, 8192, 4096]
