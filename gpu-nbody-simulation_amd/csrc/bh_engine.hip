@@ -1,7 +1,7 @@
 // bh_engine.hip -- libbhgpu.so: the C-ABI of include/bhgpu.h.  In this file: the context and its helpers, the tree build, the
 // walks' launchers, the step and the split operators, the diagnostics, direct sums and force check, tree export, the
 // locally-essential trees and migration.  The analysis queries' host code -- moment maps, radial profiles, field at points,
-// neighbours, pair counts, groups -- is bh_queries_host.hpp, included below as part of this unit.
+// neighbours, pair counts, groups, spanning trees -- is bh_queries_host.hpp, included below as part of this unit.
 // Compiled with -ffp-contract=off (tree build + exact walk must not fuse multiply-adds; the fp32
 // walk lives in bh_walk_fast.hip, compiled separately).  gfx950 only, no CPU fallback.
 #include "../../include/bhgpu.h"
@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +33,7 @@
 #include "bh_neighbours.hpp"
 #include "bh_pairs.hpp"
 #include "bh_groups.hpp"
+#include "bh_mst.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
 #include "bh_queries_state.hpp"
@@ -168,6 +170,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     NbState nb;
     PairState pair;
     FofState fof;
+    MstState mst;
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -937,7 +940,7 @@ int quietly(bh_ctx *c, unsigned opts, Body body)
 
 }  // namespace
 
-// the analysis queries: moment maps, radial profiles, field at points, neighbours, pair counts, groups -- and the helpers they
+// the analysis queries: moment maps, radial profiles, field at points, neighbours, pair counts, groups, spanning trees -- and the helpers they
 // share, which the diagnostics below use as well
 #include "bh_queries_host.hpp"
 
@@ -1101,7 +1104,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
-    destroy(c->fof.ev); destroy(c->rad.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

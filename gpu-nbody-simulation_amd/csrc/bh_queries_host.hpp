@@ -1,9 +1,9 @@
 // bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, the field
-// at points, neighbour queries, pair counts and friends-of-friends groups, with their entry points of include/bhgpu.h.
-// Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers (fail, BH_HIP,
-// dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp, bh_radial.hpp,
-// bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp and bh_groups.hpp, the state in bh_queries_state.hpp, the arithmetic that
-// needs no device in bh_query_host.hpp.  What every family shares comes first.
+// at points, neighbour queries, pair counts, friends-of-friends groups and spanning trees, with their entry points of
+// include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
+// (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp,
+// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp, bh_groups.hpp and bh_mst.hpp, the state in bh_queries_state.hpp,
+// the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes first.
 #pragma once
 
 #include "bh_query_host.hpp"
@@ -550,6 +550,43 @@ int fof_alloc(bh_ctx *c, int64_t n)
                                                  part(&s.rec_label, b), part(&s.rec_count, b)});
 }
 
+// ---- spanning trees (bh_mst.hpp) on the structure of the neighbour queries, and of subsets on the state itself.  They read pos
+// and orig as they lie in memory and write buffers of their own: a step before and after runs bit for bit as it would have.
+int mst_alloc(bh_ctx *c, int64_t n)
+{
+    MstState &s = c->mst;
+    if (n <= s.block.cap) return BH_OK;
+    const int64_t cap = grown_capacity(n);
+    int32_t off[kNbMaxLevels + 1];
+    nb_levels(cap, off);
+    const size_t nodes = (size_t)off[kNbMaxLevels] + kNbMaxLevels, b = (size_t)cap;       // (as nb_alloc)
+    return block_regrow(c, s.block, cap, {part(&s.seedmin, b), part(&s.mind2, b), part(&s.minpair, b), part(&s.cand_d2, b), part(&s.cand_pair, b),
+                                          part(&s.edge_pair, b), part(&s.edge_d2, b), part(&s.ctr, 1), part(&s.parent, b),
+                                          part(&s.comp, b), part(&s.inv, b), part(&s.nodecomp, nodes)});
+}
+
+// an edge as the device leaves it, and the edge order
+struct MstEdge {
+    uint64_t d2, pair;
+    bool operator<(const MstEdge &o) const { return d2 < o.d2 || (d2 == o.d2 && pair < o.pair); }
+};
+
+// `count` edges in ascending edge order into lo / hi / d2
+void mst_sorted_out(MstEdge *e, int64_t count, int64_t *lo, int64_t *hi, double *d2)
+{
+    std::sort(e, e + count);
+    for (int64_t k = 0; k < count; ++k) {
+        lo[k] = (int64_t)(e[k].pair >> 24);
+        hi[k] = (int64_t)(e[k].pair & 0xffffffull);
+        std::memcpy(&d2[k], &e[k].d2, sizeof(double));
+    }
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 }  // namespace
 
 extern "C" {
@@ -921,6 +958,188 @@ int bh_groups_times(bh_ctx *c, double *build_ms, double *link_ms, double *catalo
     *build_ms = c->fof.build_ms;
     *link_ms = c->fof.link_ms;
     *catalogue_ms = c->fof.cat_ms;
+    return BH_OK;
+}
+
+int bh_spanning_tree(bh_ctx *c, int64_t *lo, int64_t *hi, double *d2, uint64_t *stats)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!lo || !hi || !d2) return fail(c, BH_ERR_ARG, "bh_spanning_tree: null output");
+    if (int rc = diag_check(c, "bh_spanning_tree")) return rc;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_spanning_tree: more than 2^24 bodies (their indices share a key word)");
+    NbState &nb = c->nb;
+    MstState &s = c->mst;
+    s.build_ms = s.rounds_ms = s.sort_ms = 0.0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (n == 0) return BH_OK;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, 0, 0)) return rc;
+    if (int rc = mst_alloc(c, n)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_spanning_tree", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(n, kBlock);
+    const int32_t n32 = (int32_t)n;
+    int32_t off[kNbMaxLevels + 1];
+    nb_levels(n, off);
+    BH_HIP(c, hipMemsetAsync(s.ctr, 0, sizeof(MstCounters), st));
+    hipLaunchKernelGGL(mst_init_kernel, dim3(grid), dim3(kBlock), 0, st, nb.sidx, n32, s.parent, s.comp, s.inv, s.seedmin, s.mind2,
+                       s.minpair);
+    // The rounds: the components at least halve in each, so kMstMaxRounds are never reached; a round that joins nothing ends the
+    // call as well.  One word comes back per round.
+    unsigned long long left = (unsigned long long)n;
+    int rounds = 0;
+    while (left > 1) {
+        if (rounds == kMstMaxRounds)
+            return fail(c, BH_ERR_DEVICE, "bh_spanning_tree: " + std::to_string(left) + " components left after " +
+                                          std::to_string(rounds) + " rounds");
+        for (int l = 0; l < levels; ++l) {
+            const int32_t count = off[l + 1] - off[l], below = l ? off[l] - off[l - 1] : 0;
+            hipLaunchKernelGGL(mst_nodecomp_kernel, dim3(blocks_for(count, kBlock)), dim3(kBlock), 0, st, s.comp,
+                               s.nodecomp + (l ? off[l - 1] : 0), l, below, n32, count, s.nodecomp + off[l]);
+        }
+        hipLaunchKernelGGL(mst_seed_kernel, dim3(grid), dim3(kBlock), 0, st, nb.spos, nb.sidx, s.comp, n32, s.seedmin, s.cand_d2,
+                           s.cand_pair, s.ctr);
+        hipLaunchKernelGGL(mst_nearest_kernel, dim3(grid), dim3(kBlock), 0, st, nb.spos, nb.sidx, s.comp, s.nodecomp, nb.boxes, nb.off,
+                           levels, n32, s.seedmin, s.mind2, s.cand_d2, s.cand_pair, s.ctr);
+        hipLaunchKernelGGL(mst_pick_kernel, dim3(grid), dim3(kBlock), 0, st, s.comp, s.mind2, s.cand_d2, s.cand_pair, n32, s.minpair);
+        hipLaunchKernelGGL(mst_hook_kernel, dim3(grid), dim3(kBlock), 0, st, s.comp, s.inv, s.mind2, s.minpair, n32, s.parent,
+                           s.edge_pair, s.edge_d2, s.ctr);
+        hipLaunchKernelGGL(mst_flatten_kernel, dim3(grid), dim3(kBlock), 0, st, s.parent, n32, s.comp, s.seedmin, s.mind2,
+                           s.minpair,
+                           &s.ctr->roots[rounds]);
+        BH_HIP(c, hipGetLastError());
+        unsigned long long got = 0;
+        BH_HIP(c, hipMemcpyAsync(&got, &s.ctr->roots[rounds], sizeof(got), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+        ++rounds;
+        if (got < 1 || got >= left)
+            return fail(c, BH_ERR_DEVICE, "bh_spanning_tree: round " + std::to_string(rounds) + " left " + std::to_string(got) +
+                                          " of " + std::to_string(left) + " components");
+        left = got;
+    }
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[0])) return rc;
+    // The final order, timed on its own: the records by the bits of d2 on the device -- the stable LSD passes over all 64 bits,
+    // an edge's place in the append order as the payload; the union-find and the candidates are not read any more and lend
+    // their arrays, the index its count matrix --, the pairs gathered into that order, then the host sorts the runs of equal d2.
+    const size_t edges = (size_t)(n - 1);
+    uint64_t *const keys[2] = {reinterpret_cast<uint64_t *>(s.edge_d2), reinterpret_cast<uint64_t *>(s.cand_d2)};
+    uint32_t *const vals[2] = {s.parent, s.comp};
+    int cur = 0;
+    if (edges) {
+        static_assert(kSortItems >= kFieldSortItems, "the index's count matrix holds this sort's tiles");
+        hipLaunchKernelGGL(mst_iota_kernel, dim3(blocks_for((int64_t)edges, kBlock)), dim3(kBlock), 0, st, (int32_t)edges, vals[0]);
+        cur = enqueue_lsd_passes<kSortItems>(st, keys, vals, nb.radix, nb.rowsum, (int64_t)edges, 64, false);
+        hipLaunchKernelGGL(mst_gather_kernel, dim3(blocks_for((int64_t)edges, kBlock)), dim3(kBlock), 0, st, vals[cur], s.edge_pair,
+                           (int32_t)edges, s.minpair);
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[1])) return rc;
+    MstCounters ctr{};
+    std::vector<uint64_t> pr(edges);
+    BH_HIP(c, hipMemcpyAsync(&ctr, s.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    if (edges) {
+        BH_HIP(c, hipMemcpyAsync(pr.data(), s.minpair, edges * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(d2, keys[cur], edges * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (int rc = span_ms(c, nb.ev[0], nb.ev[1], &s.build_ms)) return rc;
+    if (int rc = span_ms(c, nb.ev[1], s.ev[0], &s.rounds_ms)) return rc;
+    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.sort_ms)) return rc;
+    if (ctr.edges != (unsigned long long)edges)
+        return fail(c, BH_ERR_DEVICE, "bh_spanning_tree: " + std::to_string(ctr.edges) + " edges for " + std::to_string(n) + " bodies");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t k = 0; k < edges;) {
+        size_t end = k + 1;
+        while (end < edges && d2[end] == d2[k]) ++end;                 // (d2 >= +0 and never NaN: equal values, equal bits)
+        if (end - k > 1) std::sort(pr.begin() + (std::ptrdiff_t)k, pr.begin() + (std::ptrdiff_t)end);
+        k = end;
+    }
+    for (size_t k = 0; k < edges; ++k) {
+        lo[k] = (int64_t)(pr[k] >> 24);
+        hi[k] = (int64_t)(pr[k] & 0xffffffull);
+    }
+    s.sort_ms += ms_since(t0);
+    if (stats) { stats[0] = (uint64_t)rounds; stats[1] = ctr.evals; stats[2] = ctr.skips; stats[3] = ctr.edges; }
+    return BH_OK;
+}
+
+int bh_spanning_tree_subsets(bh_ctx *c, const int64_t *members, int64_t n_sets, int32_t k, int64_t *lo, int64_t *hi, double *d2)
+{
+    if (!c) return BH_ERR_ARG;
+    if (k < 2 || k > kMstSubsetMax) return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: k must be 2 .. BH_MST_SUBSET_MAX = 512");
+    if (n_sets < 0) return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: n_sets < 0");
+    if (n_sets > 0 && (!members || !lo || !hi || !d2)) return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: null argument");
+    if (int rc = diag_check(c, "bh_spanning_tree_subsets")) return rc;
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies)
+        return fail(c, BH_ERR_CAPACITY, "bh_spanning_tree_subsets: more than 2^24 bodies (the two indices of an edge share a word)");
+    MstState &s = c->mst;
+    s.build_ms = s.rounds_ms = s.sort_ms = 0.0;
+    // every index inside [0, n) and no index twice in a row, before anything is enqueued
+    std::vector<int64_t> seen((size_t)n, (int64_t)-1);
+    for (int64_t r = 0; r < n_sets; ++r)
+        for (int32_t t = 0; t < k; ++t) {
+            const int64_t m = members[r * k + t];
+            if (m < 0 || m >= n)
+                return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: set " + std::to_string(r) + " has index " + std::to_string(m) + " outside [0, n)");
+            if (seen[(size_t)m] == r)
+                return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: set " + std::to_string(r) + " has index " + std::to_string(m) + " twice");
+            seen[(size_t)m] = r;
+        }
+    if (n_sets == 0) return BH_OK;
+    BH_HIP(c, hipSetDevice(c->device));
+    const int64_t per = std::max<int64_t>(1, ((int64_t)1 << 22) / k);             // sets per launch
+    const int64_t want = std::min(n_sets, per) * k;
+    if (want > s.sblock.cap) {
+        const size_t b = (size_t)grown_capacity(want);
+        if (int rc = block_regrow(c, s.sblock, (int64_t)b, {part(&s.members, b), part(&s.set_pair, b), part(&s.set_d2, b), part(&s.bad, 1)}))
+            return rc;
+    }
+    hipStream_t st = c->stream;
+    const uint32_t *slot_of = nullptr;
+    if (!c->tree64() && !c->is.orig_identity) {            // (fp32 / mixed after a physical re-order: slots are not caller indices)
+        if (!c->slot_of) { if (int rc = dev_alloc(c, &c->slot_of, (size_t)std::max<int64_t>(c->cfg.capacity, 1))) return rc; }
+        hipLaunchKernelGGL(direct_slot_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, st, c->orig, n, c->slot_of);
+        slot_of = c->slot_of;
+    }
+    BH_HIP(c, hipMemsetAsync(s.bad, 0, sizeof(uint32_t), st));
+    const int64_t row = k - 1;
+    std::vector<MstEdge> e((size_t)(n_sets * row));
+    std::vector<uint64_t> pr((size_t)(std::min(n_sets, per) * row)), dd(pr.size());
+    for (int64_t r0 = 0; r0 < n_sets; r0 += per) {
+        const int64_t sets = std::min(per, n_sets - r0);
+        BH_HIP(c, hipMemcpyAsync(s.members, members + r0 * k, (size_t)(sets * k) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (int rc = mark(c, s.ev[0])) return rc;
+        state_ptrs(c, [&](auto pos, auto, auto) {
+            hipLaunchKernelGGL((mst_subset_kernel<Pointee<decltype(pos)>>), dim3((unsigned)sets), dim3(kWave), (size_t)k * 36, st, pos,
+                               slot_of, s.members, k, s.set_pair, s.set_d2, s.bad);
+        });
+        BH_HIP(c, hipGetLastError());
+        if (int rc = mark(c, s.ev[1])) return rc;
+        BH_HIP(c, hipMemcpyAsync(pr.data(), s.set_pair, (size_t)(sets * row) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(dd.data(), s.set_d2, (size_t)(sets * row) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));                    // (the next launch overwrites the members)
+        if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.rounds_ms, true)) return rc;
+        for (int64_t i = 0; i < sets * row; ++i) e[(size_t)(r0 * row + i)] = MstEdge{dd[(size_t)i], pr[(size_t)i]};
+    }
+    uint32_t bad = 0;
+    BH_HIP(c, hipMemcpy(&bad, s.bad, sizeof(bad), hipMemcpyDeviceToHost));
+    if (bad) return fail(c, BH_ERR_ARG, "bh_spanning_tree_subsets: a member has a non-finite position");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int64_t r = 0; r < n_sets; ++r) mst_sorted_out(e.data() + r * row, row, lo + r * row, hi + r * row, d2 + r * row);
+    s.sort_ms = ms_since(t0);
+    return BH_OK;
+}
+
+int bh_spanning_tree_times(bh_ctx *c, double *build_ms, double *rounds_ms, double *sort_ms)
+{
+    if (!c || !build_ms || !rounds_ms || !sort_ms) return fail(c, BH_ERR_ARG, "bh_spanning_tree_times: null argument");
+    *build_ms = c->mst.build_ms;
+    *rounds_ms = c->mst.rounds_ms;
+    *sort_ms = c->mst.sort_ms;
     return BH_OK;
 }
 

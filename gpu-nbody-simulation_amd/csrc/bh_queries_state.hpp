@@ -85,4 +85,19 @@ struct FofState {
     int32_t cat_exp[kGrpPlanes] = {0, 0, 0, 0, 0};
 };
 
+// spanning trees (bh_mst.hpp): one block for up to block.cap bodies beside the neighbour structure's -- the union-find, the
+// components of bodies and nodes, the per-component minima, the lanes' candidates and the edges as they were appended --, and
+// one for a launch of up to sblock.cap members of subsets with their edges
+struct MstState {
+    DevBlock block, sblock;
+    uint32_t *parent = nullptr, *comp = nullptr, *inv = nullptr, *nodecomp = nullptr, *bad = nullptr;
+    unsigned long long *seedmin = nullptr, *mind2 = nullptr, *minpair = nullptr, *cand_d2 = nullptr, *cand_pair = nullptr, *edge_pair = nullptr,
+                       *edge_d2 = nullptr, *set_pair = nullptr;
+    double *set_d2 = nullptr;
+    int64_t *members = nullptr;
+    MstCounters *ctr = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};                      // after the rounds, after the sort; subsets: around a launch
+    double build_ms = 0.0, rounds_ms = 0.0, sort_ms = 0.0;      // of the last call (bh_spanning_tree_times)
+};
+
 }  // namespace bh

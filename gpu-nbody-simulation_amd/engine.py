@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import math
 import os
 from dataclasses import dataclass
 
@@ -375,6 +376,92 @@ def groups_from_sums(label, n_groups: int, linking_length: float, min_members: i
     return BhGroups(np.asarray(label, dtype=np.int64), int(n_groups), float(linking_length), int(min_members),
                     np.asarray(ids, dtype=np.int64), np.asarray(counts, dtype=np.int64), val[0], com, vel,
                     sums if raw else None, exponents.copy() if raw else None, stats)
+
+
+MST_SUBSET_MAX = 512                    # BH_MST_SUBSET_MAX
+
+
+@dataclass
+class BhSpanningTree:
+    """The Euclidean minimum spanning tree of the current state (spanning_tree) under the edge order (d2, lo, hi), lo < hi the
+    caller indices of an edge's ends and d2 = dx * dx + dy * dy in fp64: unique, and ascending in that order.  It is the
+    friends-of-friends clustering at every linking length at once: the groups at b are the components of the edges with
+    d2 <= b * b."""
+    lo: np.ndarray               # (n - 1,) int64
+    hi: np.ndarray               # (n - 1,) int64
+    d2: np.ndarray               # (n - 1,) float64, ascending
+    length: np.ndarray           # sqrt(d2)
+    total_length: float          # math.fsum(length)
+    n: int
+    stats: tuple | None = None   # with_stats=True: (rounds, distances computed, nodes skipped as own-component, edges)
+
+    def _edges_within(self, lengths) -> np.ndarray:
+        b = np.asarray(lengths, dtype=np.float64)
+        if not (b >= 0.0).all():
+            raise ValueError("a linking length must be >= 0")
+        return np.searchsorted(self.d2, b * b, side="right")
+
+    def n_groups_at(self, lengths):
+        """the number of groups(b) at every linking length of `lengths` (any shape): n - the edges with d2 <= b * b"""
+        return self.n - self._edges_within(lengths)
+
+    def groups_at(self, b: float) -> np.ndarray:
+        """(n,) int64: the label groups(b) gives every body -- the smallest caller index of its component of the edges with
+        d2 <= b * b."""
+        m = int(self._edges_within(float(b)))
+        parent = list(range(self.n))
+        for a, c in zip(self.lo[:m].tolist(), self.hi[:m].tolist()):
+            while parent[a] != a:
+                parent[a] = a = parent[parent[a]]
+            while parent[c] != c:
+                parent[c] = c = parent[parent[c]]
+            if a < c:
+                parent[c] = a
+            else:
+                parent[a] = c
+        # (the larger root hangs under the smaller: parent[i] <= i, so one ascending pass resolves every body)
+        label = np.arange(self.n, dtype=np.int64)
+        for i in range(self.n):
+            label[i] = label[parent[i]]
+        return label
+
+
+def spanning_tree_from(lo, hi, d2, n: int, stats=None) -> BhSpanningTree:
+    """BhSpanningTree of the sorted edges of bh_spanning_tree."""
+    d2 = np.asarray(d2, dtype=np.float64).reshape(-1)
+    length = np.sqrt(d2)
+    return BhSpanningTree(np.asarray(lo, dtype=np.int64).reshape(-1), np.asarray(hi, dtype=np.int64).reshape(-1), d2, length,
+                          math.fsum(length.tolist()), int(n), stats)
+
+
+@dataclass
+class BhMassSegregation:
+    """The mass segregation ratio Lambda_MSR of Allison et al. (2009) (mass_segregation): the mean spanning-tree length of
+    random sets of n_massive bodies over the spanning-tree length of the n_massive most massive ones; above 1 when the massive
+    bodies lie closer together than bodies at random."""
+    ratio: float                 # mean(l_random) / l_massive
+    sigma: float                 # std(l_random) / l_massive
+    l_massive: float
+    l_random: np.ndarray         # (n_random,)
+    members: np.ndarray          # (1 + n_random, n_massive) int64: row 0 the massive set, then the random sets
+    n_massive: int
+
+
+def mass_segregation_from(d2, members) -> BhMassSegregation:
+    """BhMassSegregation from the squared edge lengths d2 (1 + n_random, k - 1) of the sets `members` (1 + n_random, k), row 0
+    the massive set: l = math.fsum(sqrt(d2)) per row, mean = fsum(l_random) / n_random, std^2 = fsum((l_random - mean)^2) /
+    n_random, both over l_massive (inf or NaN where that is 0)."""
+    d2 = np.asarray(d2, dtype=np.float64)
+    members = np.asarray(members, dtype=np.int64)
+    if d2.ndim != 2 or members.ndim != 2 or len(d2) != len(members) or len(d2) < 2 or d2.shape[1] != members.shape[1] - 1:
+        raise ValueError("d2 (1 + n_random, k - 1) and members (1 + n_random, k), n_random >= 1")
+    l = np.array([math.fsum(np.sqrt(row).tolist()) for row in d2])
+    l_massive, l_random = float(l[0]), l[1:].copy()
+    mean = math.fsum(l_random.tolist()) / len(l_random)
+    std = math.sqrt(math.fsum(((l_random - mean) * (l_random - mean)).tolist()) / len(l_random))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio, sigma = float(np.float64(mean) / np.float64(l_massive)), float(np.float64(std) / np.float64(l_massive))
+    return BhMassSegregation(ratio, sigma, l_massive, l_random, members, members.shape[1])
 
 
 PAIR_MAX_BINS = 1024                    # BH_PAIR_MAX_BINS
@@ -989,6 +1076,61 @@ class BarnesHutEngine:
         b, l, k = C.c_double(), C.c_double(), C.c_double()
         self._check(self._lib.bh_groups_times(self._h, C.byref(b), C.byref(l), C.byref(k)))
         return b.value, l.value, k.value
+
+    # -- spanning trees -------------------------------------------------------------------------
+    def spanning_tree(self, with_stats: bool = False) -> BhSpanningTree:
+        """The Euclidean minimum spanning tree of the current state under the edge order (d2, lo, hi) -- unique, the brute-force
+        tree bit for bit -- by Boruvka rounds on the index of the neighbour queries.  groups_at(b) of the result equals
+        groups(b).label at every b.  Reads the state only; the run is not perturbed."""
+        n = self.n
+        m = max(n - 1, 0)
+        lo, hi, d2 = np.zeros(max(m, 1), dtype=np.int64), np.zeros(max(m, 1), dtype=np.int64), np.zeros(max(m, 1))
+        st = (C.c_uint64 * 4)()
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.bh_spanning_tree(self._h, lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), _dptr(d2), st))
+        return spanning_tree_from(lo[:m], hi[:m], d2[:m], n, tuple(int(v) for v in st) if with_stats else None)
+
+    def spanning_tree_times(self):
+        """(build_ms, rounds_ms, sort_ms) of the last spanning_tree(): HIP events around the index's build, the rounds and the
+        sort of the edges (the host's ordering of equal d2 added); after subset_spanning_trees(): 0, the kernels, the host's sort of the rows."""
+        b, r, s = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.bh_spanning_tree_times(self._h, C.byref(b), C.byref(r), C.byref(s)))
+        return b.value, r.value, s.value
+
+    def subset_spanning_trees(self, members):
+        """(lo, hi, d2), each (n_sets, k - 1): the minimum spanning tree of every row of `members` (n_sets, k) caller indices,
+        of those k bodies alone, under the edge order of spanning_tree, each row ascending; 2 <= k <= MST_SUBSET_MAX, no
+        index twice in a row.  One wavefront per row."""
+        mem = np.ascontiguousarray(members, dtype=np.int64)
+        if mem.ndim != 2:
+            raise ValueError("members must be (n_sets, k)")
+        sets, k = mem.shape
+        m = max(k - 1, 1)
+        lo, hi, d2 = (np.zeros((max(sets, 1), m), dtype=np.int64), np.zeros((max(sets, 1), m), dtype=np.int64),
+                      np.zeros((max(sets, 1), m)))
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.bh_spanning_tree_subsets(self._h, mem.ctypes.data_as(i64) if mem.size else (C.c_int64 * 1)(), sets, k,
+                                                       lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), _dptr(d2)))
+        return lo[:sets], hi[:sets], d2[:sets]
+
+    def mass_segregation_sets(self, n_massive: int, n_random: int = 500, seed: int = 0, weights=None) -> np.ndarray:
+        """(1 + n_random, n_massive) int64: row 0 the n_massive bodies of largest `weights` (default: the masses; ties go to the
+        smaller index), row 1 + r the random set np.random.default_rng([seed, r]).choice(n, n_massive, replace=False)."""
+        n, k, R = self.n, int(n_massive), int(n_random)
+        if not (2 <= k <= min(n, MST_SUBSET_MAX)) or R < 1:
+            raise ValueError(f"n_massive must be 2 .. min(n, {MST_SUBSET_MAX}) and n_random >= 1")
+        w = self.masses() if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        if len(w) != n:
+            raise ValueError("one weight per body")
+        rows = [np.argsort(-w, kind="stable")[:k]]
+        rows += [np.random.default_rng([int(seed), r]).choice(n, k, replace=False) for r in range(R)]
+        return np.stack(rows).astype(np.int64)
+
+    def mass_segregation(self, n_massive: int, n_random: int = 500, seed: int = 0, weights=None) -> BhMassSegregation:
+        """The mass segregation ratio of the current state: the spanning trees of the massive set and of n_random random sets in
+        one subset_spanning_trees call -- see mass_segregation_sets and mass_segregation_from."""
+        members = self.mass_segregation_sets(n_massive, n_random, seed, weights)
+        return mass_segregation_from(self.subset_spanning_trees(members)[2], members)
 
     def local_density(self, k: int = 6):
         """(sigma (n,), r_k (n,)): Casertano and Hut's k-th-neighbour density estimate in two dimensions from one

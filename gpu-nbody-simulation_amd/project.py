@@ -17,6 +17,7 @@ lines of the scaling scripts translate one to one.)
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import time
@@ -82,7 +83,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      profile_spacing: str = "log", profile_centre="density", lagrange_file: str | None = None,
                      lagrange_fractions=(0.01, 0.1, 0.5, 0.9), lagrange_every: int = 0, lagrange_centre="density",
                      pairs_file: str | None = None, pairs_bins: int | None = None, pairs_range=None, pairs_spacing: str = "log",
-                     pairs_randoms: int | None = None, pairs_seed: int = 0):
+                     pairs_randoms: int | None = None, pairs_seed: int = 0, mst_file: str | None = None,
+                     segregation_file: str | None = None, segregation_massive: int | None = None, segregation_random: int = 500,
+                     segregation_seed: int = 0):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -125,6 +128,12 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     per bin.  With pairs_randoms = NR points drawn uniformly in the bounding box of the final positions from
     np.random.default_rng(pairs_seed), also their cross counts and the Davis-Peebles correlation
     (BarnesHutEngine.correlation): `# r_lo,r_hi,dd,dr,xi` (%.17g; nan where dr = 0).  Not part of gpu_parallel_duration_us.
+    mst_file: after the last step, also write the minimum spanning tree of the final state (BarnesHutEngine.spanning_tree): the
+    line `# i,j,length`, then one row per edge (%.17g), ascending in the edge order (d2, i, j).  Not part of
+    gpu_parallel_duration_us.
+    segregation_file: after the last step, also write the mass segregation ratio of the final state
+    (BarnesHutEngine.mass_segregation(segregation_massive, segregation_random, segregation_seed)): the line
+    `# k,ratio,sigma,l_massive,l_random_mean` and one row (%.17g).  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -132,6 +141,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     returned, has velocities and positions at the same time."""
     if groups_file is not None and linking_length is None:
         raise ValueError("groups_file needs a linking_length")
+    if (segregation_file is None) != (segregation_massive is None):
+        raise ValueError("segregation_file and segregation_massive go together")
     if integrator not in ("euler", "kdk"):
         raise ValueError("integrator must be 'euler' or 'kdk'")
     if (profile_file is None) != (profile_bins is None):
@@ -284,6 +295,17 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                     xi, dd, dr = eng.correlation(edges, pairs_random_points(pos, pairs_randoms, pairs_seed))
                     f.write("# r_lo,r_hi,dd,dr,xi\n")
                     f.write("".join("%.17g,%.17g,%d,%d,%.17g\n" % r for r in zip(dd.edges[:-1], dd.edges[1:], dd.counts, dr.counts, xi)))
+        if mst_file is not None:
+            t = eng.spanning_tree()
+            with open(os.path.join(out_dir, mst_file) if not os.path.isabs(mst_file) else mst_file, "w") as f:
+                f.write("# i,j,length\n")
+                f.write("".join("%d,%d,%.17g\n" % r for r in zip(t.lo, t.hi, t.length)))
+        if segregation_file is not None:
+            ms = eng.mass_segregation(segregation_massive, segregation_random, segregation_seed)
+            with open(os.path.join(out_dir, segregation_file) if not os.path.isabs(segregation_file) else segregation_file, "w") as f:
+                f.write("# k,ratio,sigma,l_massive,l_random_mean\n")
+                f.write("%d,%.17g,%.17g,%.17g,%.17g\n" % (ms.n_massive, ms.ratio, ms.sigma, ms.l_massive,
+                                                          math.fsum(ms.l_random.tolist()) / len(ms.l_random)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr, lagrange):
@@ -425,6 +447,14 @@ def _parse(argv):
     ap.add_argument("--pairs-randoms", type=int, default=None, metavar="NR",
                     help="random points, uniform in the bounding box of the final positions, for dr and xi")
     ap.add_argument("--pairs-seed", type=int, default=None, metavar="S", help="seed of --pairs-randoms (default 0)")
+    ap.add_argument("--mst-file", default=None, metavar="PATH",
+                    help="after the last step, also write i,j,length of every edge of the minimum spanning tree of the final state")
+    ap.add_argument("--segregation-file", default=None, metavar="PATH",
+                    help="after the last step, also write k,ratio,sigma,l_massive,l_random_mean: the mass segregation ratio of the "
+                         "final state (needs --segregation-massive)")
+    ap.add_argument("--segregation-massive", type=int, default=None, metavar="K", help="the K most massive bodies (2 .. 512)")
+    ap.add_argument("--segregation-random", type=int, default=None, metavar="R", help="random sets of K bodies (default 500)")
+    ap.add_argument("--segregation-seed", type=int, default=None, metavar="S", help="seed of the random sets (default 0)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -484,6 +514,14 @@ def _parse(argv):
         ap.error("--pairs-range: log spacing needs RMIN > 0")
     if a.pairs_randoms is not None and a.pairs_randoms < 1:
         ap.error("--pairs-randoms: at least 1")
+    if (a.segregation_file is None) != (a.segregation_massive is None):
+        ap.error("--segregation-file and --segregation-massive go together")
+    if a.segregation_file is None and (a.segregation_random is not None or a.segregation_seed is not None):
+        ap.error("--segregation-random and --segregation-seed need --segregation-file")
+    if a.segregation_massive is not None and not 2 <= a.segregation_massive <= 512:
+        ap.error("--segregation-massive: 2 .. 512")
+    if a.segregation_random is not None and a.segregation_random < 1:
+        ap.error("--segregation-random: at least 1")
     a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     if a.groups_min is not None and a.groups_min < 1:
@@ -560,7 +598,9 @@ def main(argv=None) -> int:
         lagrange_fractions=(0.01, 0.1, 0.5, 0.9) if a.lagrange_fractions is None else tuple(a.lagrange_fractions),
         lagrange_every=a.lagrange_every, lagrange_centre=a.lagrange_centre, pairs_file=a.pairs_file, pairs_bins=a.pairs_bins,
         pairs_range=a.pairs_range, pairs_spacing=a.pairs_spacing or "log", pairs_randoms=a.pairs_randoms,
-        pairs_seed=a.pairs_seed or 0)
+        pairs_seed=a.pairs_seed or 0, mst_file=a.mst_file, segregation_file=a.segregation_file,
+        segregation_massive=a.segregation_massive, segregation_random=500 if a.segregation_random is None else a.segregation_random,
+        segregation_seed=a.segregation_seed or 0)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -597,6 +597,38 @@ int bh_groups_catalogue(bh_ctx *ctx, int64_t max_records, int64_t *labels, int64
                         int64_t *n_out);
 int bh_groups_times(bh_ctx *ctx, double *build_ms, double *link_ms, double *catalogue_ms);
 
+/* --- spanning trees: the clustering at every linking length at once, and the trees of small subsets ------------------------------
+ * Distance.  d2(i, j) is the d2 of bh_count_within and bh_groups: dx = x_j - x_i; dy = y_j - y_i; d2 = dx * dx + dy * dy, in fp64
+ *   with nothing fused, in every precision (an fp32 state is widened first, exactly).  It is symmetric in (i, j), bit for bit.
+ * Edge order.  The edges of the complete graph over the bodies are ordered by the triple (d2, lo, hi), lo < hi the CALLER indices
+ *   of the two ends.  That is a strict total order, so the minimum spanning tree is UNIQUE -- with coincident bodies and on a
+ *   lattice too: there is exactly one right answer, and no launch shape, traversal order or race decides any of it.
+ * bh_spanning_tree: the n - 1 edges of that tree over all bodies of the current state (none for n <= 1) as lo[], hi[], d2[], each
+ *   with room for n - 1 entries, ASCENDING in the edge order.  The friends-of-friends groups of bh_groups at linking length b are
+ *   the connected components of the edges with d2 <= b * b, and their number is n minus the number of such edges.  It builds the
+ *   index of the neighbour queries, runs Boruvka rounds on it (at most ceil(log2 n); BH_ERR_DEVICE with a message should 25 not
+ *   do) and sorts the edges by d2 on the device (the host orders edges of equal d2); it waits for the stream.
+ *   stats (may be NULL) = {rounds, distances computed, nodes skipped because all their bodies lay in the lane's own component,
+ *   edges (= n - 1)}: deterministic for a given state; a measure of the work and no part of the answer.
+ * bh_spanning_tree_subsets: for each of n_sets rows of k caller indices in members[n_sets][k], the k - 1 edges of the minimum
+ *   spanning tree of THOSE k BODIES ALONE under the same edge order, into row r of lo, hi, d2 ([n_sets][k - 1]), each row
+ *   ascending.  2 <= k <= BH_MST_SUBSET_MAX, n_sets >= 0.  One wavefront per row (Prim's algorithm in LDS); rows may share
+ *   bodies.  It reads the positions of the members only.
+ * bh_spanning_tree_times: of the last of the two calls.  bh_spanning_tree: HIP-event times of the index's build, of the rounds
+ *   and of the final sort (the host's ordering of equal d2 added).  bh_spanning_tree_subsets: 0, the HIP-event time of the
+ *   kernels, and the host's time for sorting the rows.
+ * They read the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.
+ * Errors: BH_ERR_ARG for a null lo, hi or d2 (bh_spanning_tree_subsets: with n_sets > 0, members too), for k or n_sets outside
+ *   the rules above, for an index outside [0, n) or an index twice in one row (checked on the host before anything is
+ *   enqueued), and for a non-finite body position (bh_spanning_tree: found by the bounds pass, with a message that says so;
+ *   bh_spanning_tree_subsets: of a member).  BH_ERR_CAPACITY for more than 2^24 bodies.  BH_ERR_STATE before any upload, in LET
+ *   mode and with world > 1 (the tree spans ranks). */
+#define BH_MST_SUBSET_MAX 512
+int bh_spanning_tree(bh_ctx *ctx, int64_t *lo, int64_t *hi, double *d2, uint64_t stats[4]);
+int bh_spanning_tree_subsets(bh_ctx *ctx, const int64_t *members, int64_t n_sets, int32_t k, int64_t *lo, int64_t *hi, double *d2);
+int bh_spanning_tree_times(bh_ctx *ctx, double *build_ms, double *rounds_ms, double *sort_ms);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
