@@ -18,10 +18,9 @@
 // highest node (else to s): the bodies of a dense core are one tree before a single distance is computed, and nobody pays a
 // union per friend pair there.
 //
-// Link kernel (grp_link_kernel): launch shape and traversal of nb_count_kernel -- one lane per body in sorted order, boxes,
-// offsets and leaf bodies at wave-uniform addresses in the constant address space, one LaneStack per wave, a lane takes part
-// in a node only if it took part in the parent and lb <= b2.  The lane at s links to positions j < s only and leaves out a
-// node whose first position is >= s, so every unordered pair is looked at once, by its later member.  A clique node
+// Link kernel (grp_link_kernel): nb_walk (bh_neighbours.hpp), one lane per body in sorted order; a lane takes part in a node
+// only if lb <= b2.  The lane at s links to positions j < s only and leaves out a node whose first position is >= s, so every
+// unordered pair is looked at once, by its later member.  A clique node
 //   * that holds s: left out (its bodies are one tree since grp_init_kernel);
 //   * whole (ub <= b2): one union with its first body, not opened;
 //   * else: opened, and the lane links to its first friend in it only -- `done`, the end of the highest clique node of the
@@ -156,8 +155,9 @@ __global__ __launch_bounds__(kBlock) void grp_init_kernel(const NbBox *__restric
         }
         uint32_t p = (uint32_t)s;
         if (top >= 0) {
-            const int64_t span = (int64_t)kNbLeaf << (2 * top);
-            p = (uint32_t)(s / span * span);
+            int64_t first, last;
+            nb_range(top, leaf >> (2 * top), n, first, last);
+            p = (uint32_t)first;
         }
         parent[s] = p;
         linked = p != (uint32_t)s;
@@ -179,13 +179,6 @@ __global__ __launch_bounds__(kBlock) void grp_link_kernel(const double2 *__restr
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = r < n;
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
-    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
-    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
-#pragma clang diagnostic pop
-
     const int32_t s = valid ? (int32_t)r : 0;
     double2 q{0.0, 0.0};
     if (valid) q = spos[s];
@@ -193,41 +186,27 @@ __global__ __launch_bounds__(kBlock) void grp_link_kernel(const double2 *__restr
     uint32_t evals = 0, pairs = 0, hooks = 0;
     int32_t done = 0;                      // the lane has nothing more to find below this position ...
     int64_t cend = 0;                      // ... the end of the highest clique node of the path (wave-uniform)
-    LaneStack st;
-    const uint64_t all = __ballot(valid);
-    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
-    while (st.sp > 0) {
-        int32_t entry;
-        uint64_t mask;
-        st.pop(entry, mask);
-        const int level = entry >> 24;
-        const int32_t node = entry & 0xffffff;
-        const int32_t at = co[level] + node;
-        NbBox b;
-        b.lox = cb[at].lox; b.hix = cb[at].hix; b.loy = cb[at].loy; b.hiy = cb[at].hiy;
-        double ub;
-        const double lb = nb_bound<true>(b, q, ub);
-        const int64_t span = (int64_t)kNbLeaf << (2 * level);
-        const int64_t first = (int64_t)node * span;
-        const int64_t last = (first + span < n) ? first + span : (int64_t)n;
-        const double ex = b.hix - b.lox, ey = b.hiy - b.loy;
-        const bool clique = ex * ex + ey * ey <= b2;               // (wave-uniform)
-        if (clique && first >= cend) cend = last;
-        const bool inside = first < cend;                          // in a clique node (this one or one above)
-        bool in = (((mask >> lane) & 1ull) != 0ull) && lb <= b2 && first < s && first >= done;
-        if (clique && s < last) in = false;                        // (the lane's own clique node)
-        const bool whole = in && clique && ub <= b2;
-        if (whole) {
-            mine = grp_union(parent, mine, (uint32_t)first, hooks);
-            ++pairs;
-            done = (int32_t)cend;
-        }
-        const bool rest = in && !whole;
-        const uint64_t open = __ballot(rest);
-        if (open == 0ull) continue;
-        if (level == 0) {
-            for (int32_t j = (int32_t)first; j < (int32_t)last; ++j) {
-                const double dx = cpos[j].x - q.x, dy = cpos[j].y - q.y;
+    bool inside = false;                   // the node last visited lies in a clique node (itself or one above; wave-uniform)
+    nb_walk(boxes, off, spos, levels, n, valid,
+            [&](const bool took, const NbNode &nd) {
+                double ub;
+                const double lb = nb_bound<true>(nd.box, q, ub);
+                const double ex = nd.box.hix - nd.box.lox, ey = nd.box.hiy - nd.box.loy;
+                const bool clique = ex * ex + ey * ey <= b2;               // (wave-uniform)
+                if (clique && nd.first >= cend) cend = nd.last;
+                inside = nd.first < cend;
+                bool in = took && lb <= b2 && nd.first < s && nd.first >= done;
+                if (clique && s < nd.last) in = false;                     // (the lane's own clique node)
+                const bool whole = in && clique && ub <= b2;
+                if (whole) {
+                    mine = grp_union(parent, mine, (uint32_t)nd.first, hooks);
+                    ++pairs;
+                    done = (int32_t)cend;
+                }
+                return in && !whole;
+            },
+            [&](const bool rest, const int32_t j, const double px, const double py) {
+                const double dx = px - q.x, dy = py - q.y;
                 if (rest && j < s && j >= done) {
                     ++evals;
                     if (dx * dx + dy * dy <= b2) {
@@ -236,13 +215,7 @@ __global__ __launch_bounds__(kBlock) void grp_link_kernel(const double2 *__restr
                         if (inside) done = (int32_t)cend;
                     }
                 }
-            }
-        } else {
-            const int32_t below = co[level] - co[level - 1];
-            for (int c = 3; c >= 0; --c)
-                if (4 * node + c < below) st.push(nb_entry(level - 1, 4 * node + c), open);
-        }
-    }
+            });
     if (valid && mine != (uint32_t)s) atomicMin(parent + s, mine);
     const unsigned long long e = grp_wave_sum(evals), p = grp_wave_sum(pairs), h = grp_wave_sum(hooks);
     if (lane == 0) {

@@ -17,10 +17,9 @@
 //   mst_seed_kernel      every lane looks at the sorted positions s +- kMstSeed for bodies of other components: its seed, the
 //                        smallest such edge, goes to cand[], and its d2 to seedmin[comp] with a 64-bit atomicMin.  Every
 //                        component has a seed (where its run of sorted positions ends, another begins).
-//   mst_nearest_kernel   launch shape and traversal of grp_link_kernel / nb_count_kernel: one lane per sorted body, one
-//                        LaneStack per wave, boxes, offsets, node components, leaf bodies and their comp / sidx at
-//                        wave-uniform addresses in the constant address space, a lane takes part in a node only if it took
-//                        part in the parent.  The lane finds its smallest edge, in the edge order, to a body of another
+//   mst_nearest_kernel   nb_walk (bh_neighbours.hpp), one lane per sorted body; the node components and the leaf bodies'
+//                        comp / sidx are read at the walker's wave-uniform addresses, in the constant address space too.
+//                        The lane finds its smallest edge, in the edge order, to a body of another
 //                        component: `best`, which starts from the lane's seed (the traversal skips the seeds' positions).  A
 //                        node is dropped when its component is the lane's, or when lb > bound = min(best.d2, the smallest seed
 //                        of the lane's component) -- STRICTLY: at equality an edge with smaller indices can still win (as in
@@ -218,9 +217,6 @@ __global__ __launch_bounds__(kBlock) void mst_nearest_kernel(const double2 *__re
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
-    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
-    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
-    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
     const uint32_t BH64_CONSTANT *ccomp = (const uint32_t BH64_CONSTANT *)comp;
     const uint32_t BH64_CONSTANT *cidx = (const uint32_t BH64_CONSTANT *)sidx;
     const uint32_t BH64_CONSTANT *cnode = (const uint32_t BH64_CONSTANT *)nodecomp;
@@ -241,32 +237,16 @@ __global__ __launch_bounds__(kBlock) void mst_nearest_kernel(const double2 *__re
     }
     uint32_t evals = 0, skips = 0;
     const int32_t slo = s - kMstSeed, shi = s + kMstSeed;
-    LaneStack st;
-    const uint64_t all = __ballot(valid);
-    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
-    while (st.sp > 0) {
-        int32_t entry;
-        uint64_t mask;
-        st.pop(entry, mask);
-        const int level = entry >> 24;
-        const int32_t node = entry & 0xffffff;
-        const int32_t at = co[level] + node;
-        NbBox b;
-        b.lox = cb[at].lox; b.hix = cb[at].hix; b.loy = cb[at].loy; b.hiy = cb[at].hiy;
-        const uint32_t nc = cnode[at];
-        bool in = ((mask >> lane) & 1ull) != 0ull;
-        double unused;
-        const double lb = nb_bound<false>(b, q, unused);
-        const bool own = in && nc == mine;
-        skips += own ? 1u : 0u;
-        in = in && !own && !(lb > bound);
-        const uint64_t open = __ballot(in);
-        if (open == 0ull) continue;
-        if (level == 0) {
-            const int32_t first = node * kNbLeaf;
-            const int32_t last = (first + kNbLeaf < n) ? first + kNbLeaf : n;
-            for (int32_t j = first; j < last; ++j) {
-                const double px = cpos[j].x, py = cpos[j].y;
+    nb_walk(boxes, off, spos, levels, n, valid,
+            [&](const bool took, const NbNode &nd) {
+                const uint32_t nc = cnode[nd.at];
+                double unused;
+                const double lb = nb_bound<false>(nd.box, q, unused);
+                const bool own = took && nc == mine;
+                skips += own ? 1u : 0u;
+                return took && !own && !(lb > bound);
+            },
+            [&](const bool in, const int32_t j, const double px, const double py) {
                 const uint32_t cj = ccomp[j], ij = cidx[j];
                 const double dx = px - q.x, dy = py - q.y;
                 if (in && cj != mine && (j < slo || j > shi)) {
@@ -275,14 +255,8 @@ __global__ __launch_bounds__(kBlock) void mst_nearest_kernel(const double2 *__re
                     ++evals;
                     if (mst_before(d, pr, bd, bp)) { bd = d; bp = pr; }
                 }
-            }
-            bound = (bd < bound) ? bd : bound;
-        } else {
-            const int32_t below = co[level] - co[level - 1];
-            for (int c = 3; c >= 0; --c)                       // (pushed last first: child 0 is opened first)
-                if (4 * node + c < below) st.push(nb_entry(level - 1, 4 * node + c), open);
-        }
-    }
+            },
+            [&] { bound = (bd < bound) ? bd : bound; });
 
     const bool have = valid && bp != kMstNone;
     const unsigned long long bits = have ? (unsigned long long)__double_as_longlong(bd) : kMstNone;

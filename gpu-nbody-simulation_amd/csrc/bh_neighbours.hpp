@@ -15,22 +15,14 @@
 //            (index arithmetic, no links); every node holds the tight bounding box of the positions it covers.  The levels lie
 //            one after the other in one array, off[l] is the first node of level l, off[levels] the total.
 //
-// Why pruning on the boxes is exact.  For a box and a query, bx = max(lox - q.x, q.x - hix, 0), by likewise and
-// lb = bx * bx + by * by, in the operations of d2.  Rounded subtraction, multiplication and addition are monotone, and
-// rounding is symmetric in the sign: for a body in the box with q.x < lox, dx = x_j - q.x >= lox - q.x = bx as computed; with
-// q.x > hix, dx <= hix - q.x = -bx; so |dx| >= bx, dx * dx >= bx * bx, and the computed d2 >= lb.  The k nearest search drops a
-// node only when the lane's list is full and lb > the list's k-th d2 -- strictly: at equality a body with a smaller caller
-// index can still enter.  The count drops a node when lb > r2, and takes a node whole, without opening it, when
-// ub = fx * fx + fy * fy <= r2 with fx = max(q.x - lox, hix - q.x): the same argument gives |dx| <= fx, so every body of the
-// node has d2 <= ub.  The number of bodies of a node follows from its index.  Neither kNbLeaf, the key resolution nor the
-// order of the traversal can therefore change a result: they decide only how many distances are computed.
+// Pruning is exact (the argument stands with nb_walk below: lb <= d2 <= ub for every body of a box, as computed).  The k
+// nearest search drops a node only when the lane's list is full and lb > the list's k-th d2 -- strictly: at equality a body
+// with a smaller caller index can still enter.  The count drops a node when lb > r2, and takes a node whole, without opening
+// it, when ub <= r2; the number of bodies of a node follows from its index.  Neither kNbLeaf, the key resolution nor the order
+// of the traversal can therefore change a result: they decide only how many distances are computed.
 //
-// Launch shape: that of the side walks (bh_treewalk.hpp).  One wavefront per 64 queries that are consecutive in the sorted
-// order -- body queries in the sorted order itself, points Morton-sorted in the same box by field_keys_kernel -- the boxes and
-// the leaf bodies read at wave-uniform addresses in the constant address space (scalar loads), one LaneStack of
-// {level, node, lane mask} per wave (12 levels at most: 3 * 12 + 4 entries).  A lane takes part in a node only if its own
-// bound passes and it took part in the parent: its evaluations are those of a solo search in the same fixed order, whoever
-// shares the wave.  Every loop is bounded by k, kNbLeaf or the depth; no workgroup waits for another.
+// Launch shape and traversal: nb_walk's.  Body queries run in the sorted order itself, points Morton-sorted in the same box by
+// field_keys_kernel.
 //
 // Seeding.  Before the traversal a lane inserts the bodies at the sorted positions [s - k, s + k] around its own place s (a
 // body query: its sorted position, itself left out; a point: the lower bound of its key among the sorted body keys), and the
@@ -222,9 +214,6 @@ __device__ __forceinline__ int32_t nb_lower_bound(const uint64_t *__restrict__ k
     return lo;
 }
 
-// stack entries: level in the bits above 24, node below (a level has at most 2^21 nodes)
-__device__ __forceinline__ int32_t nb_entry(int level, int32_t node) { return (level << 24) | node; }
-
 // a lane's list in LDS: D and I point at the lane's entry 0, entry e is kWave further
 struct NbList {
     double *D;
@@ -252,6 +241,103 @@ struct NbList {
     }
 };
 
+// ---- the one traversal of the index: nb_knn_kernel, nb_count_kernel, pair_count_kernel (bh_pairs.hpp), grp_link_kernel
+// (bh_groups.hpp) and mst_nearest_kernel (bh_mst.hpp) ----------------------------------------------------------------------------
+//
+// Why pruning on the boxes is exact.  For a box and a query, bx = max(lox - q.x, q.x - hix, 0), by likewise and
+// lb = bx * bx + by * by, in the operations of d2.  Rounded subtraction, multiplication and addition are monotone, and
+// rounding is symmetric in the sign: for a body in the box with q.x < lox, dx = x_j - q.x >= lox - q.x = bx as computed; with
+// q.x > hix, dx <= hix - q.x = -bx; so |dx| >= bx, dx * dx >= bx * bx, and the computed d2 >= lb.  With
+// ub = fx * fx + fy * fy, fx = max(q.x - lox, hix - q.x), the same argument gives |dx| <= fx, so every body of the box has
+// d2 <= ub.  A caller drops a node on lb, takes it whole on ub (its bodies are counted by nb_range, never read) or opens it:
+// whatever it decides on these two bounds changes how many distances are computed and no result.
+//
+// Launch shape: that of the side walks (bh_treewalk.hpp), whatever the workgroup -- nb_walk knows the wave only.  One lane per
+// query, the 64 queries of a wavefront consecutive in the sorted order; the boxes, the level offsets and the leaf bodies read
+// at wave-uniform addresses in the constant address space (scalar loads); one LaneStack of {level, node, lane mask} per wave.
+// 2^24 bodies make 12 levels, and depth-first pushing of four children needs at most 3 * 12 + 4 entries.  The children are
+// pushed last first: child 0 is opened first, so the traversal meets the sorted positions in ascending order.  A lane takes
+// part in a node only if it took part in the parent and its own visit() says so: its nodes and bodies are those of a solo
+// search in the same fixed order, whoever shares the wave.  Every loop is bounded by kNbLeaf or the depth; nobody waits.
+//
+//   visit(mine, node) -> bool   every lane of the wave, for every node popped.  mine: the lane took part in the parent.
+//                               Whole-node work is done in here; true: the lane opens the node (false where !mine).
+//   body(rest, j, px, py)       every lane, for every body j of a leaf that some lane opened; rest: this lane did.  (px, py) =
+//                               spos[j], loaded once by the walker.
+//   leaf_end()                  after the last body of such a leaf (optional).
+
+// a node's bodies: the sorted positions [first, last) of node `node` of level `level` over n bodies
+__host__ __device__ __forceinline__ void nb_range(int level, int64_t node, int64_t n, int64_t &first, int64_t &last)
+{
+    const int64_t span = (int64_t)kNbLeaf << (2 * level);
+    first = node * span;
+    last = (first + span < n) ? first + span : n;
+}
+
+struct NbNode {
+    int level;
+    int32_t node, at;              // index in its level, and in boxes[] (= off[level] + node)
+    NbBox box;
+    int64_t first, last;           // nb_range
+};
+
+template <typename Visit, typename Body, typename LeafEnd>
+__device__ __forceinline__ void nb_walk(const NbBox *__restrict__ boxes, const int32_t *__restrict__ off,
+                                        const double2 *__restrict__ spos, const int32_t levels, const int32_t n, const bool valid,
+                                        Visit visit, Body body, LeafEnd leaf_end)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
+    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
+    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
+#pragma clang diagnostic pop
+
+    // stack entries: level in the bits above 24, node below (a level has at most 2^21 nodes)
+    auto nb_entry = [](int level, int32_t node) -> int32_t { return (level << 24) | node; };
+    LaneStack st;
+    const uint64_t all = __ballot(valid);
+    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
+    while (st.sp > 0) {
+        int32_t entry;
+        uint64_t mask;
+        st.pop(entry, mask);
+        const int level = entry >> 24;
+        const int32_t node = entry & 0xffffff;
+        NbNode nd;
+        nd.level = level;
+        nd.node = node;
+        nd.at = co[level] + node;
+        nd.box.lox = cb[nd.at].lox; nd.box.hix = cb[nd.at].hix; nd.box.loy = cb[nd.at].loy; nd.box.hiy = cb[nd.at].hiy;
+        nb_range(level, node, n, nd.first, nd.last);
+        // (the mask is wave-uniform: it becomes the lanes' condition as it is, no lane forms 1 << lane)
+        const bool rest = visit(__builtin_amdgcn_inverse_ballot_w64(mask), nd);
+        const uint64_t open = __ballot(rest);
+        if (open == 0ull) continue;
+        if (level == 0) {
+            int64_t first, last;                               // (nd's, with the level a constant: the span folds)
+            nb_range(0, node, n, first, last);
+            for (int32_t j = (int32_t)first; j < (int32_t)last; ++j) {
+                const double px = cpos[j].x, py = cpos[j].y;
+                body(rest, j, px, py);
+            }
+            leaf_end();
+        } else {
+            const int32_t below = co[level] - co[level - 1];
+            for (int c = 3; c >= 0; --c)                       // (pushed last first: child 0 is opened first)
+                if (4 * node + c < below) st.push(nb_entry(level - 1, 4 * node + c), open);
+        }
+    }
+}
+
+template <typename Visit, typename Body>
+__device__ __forceinline__ void nb_walk(const NbBox *__restrict__ boxes, const int32_t *__restrict__ off,
+                                        const double2 *__restrict__ spos, const int32_t levels, const int32_t n, const bool valid,
+                                        Visit visit, Body body)
+{
+    nb_walk(boxes, off, spos, levels, n, valid, visit, body, [] {});
+}
+
 // k nearest bodies of the queries of rows [0, nq) of this launch: row r is the body at sorted position s0 + r (POINTS false), or
 // the point points[order[r]], whose sorted key is pkeys[r] (POINTS true).  Row r of the outputs: k entries, padded with
 // -1 / +inf; evals[r]: the bodies whose d2 the lane computed.  Dynamic LDS: k * kWave * 12 bytes.
@@ -271,9 +357,6 @@ __global__ __launch_bounds__(kWave) void nb_knn_kernel(const double2 *__restrict
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
-    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
-    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
-    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
     const uint32_t BH64_CONSTANT *cidx = (const uint32_t BH64_CONSTANT *)sidx;
 #pragma clang diagnostic pop
 
@@ -307,41 +390,20 @@ __global__ __launch_bounds__(kWave) void nb_knn_kernel(const double2 *__restrict
         }
     }
 
-    LaneStack st;
-    const uint64_t all = __ballot(valid);
-    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
-    while (st.sp > 0) {
-        int32_t entry;
-        uint64_t mask;
-        st.pop(entry, mask);
-        const int level = entry >> 24;
-        const int32_t node = entry & 0xffffff;
-        const int32_t at = co[level] + node;
-        NbBox b;
-        b.lox = cb[at].lox; b.hix = cb[at].hix; b.loy = cb[at].loy; b.hiy = cb[at].hiy;
-        double unused;
-        const double lb = nb_bound<false>(b, q, unused);
-        const bool in = (((mask >> lane) & 1ull) != 0ull) && list.wants(lb);
-        const uint64_t open = __ballot(in);
-        if (open == 0ull) continue;
-        if (level == 0) {
-            const int32_t first = node * kNbLeaf;
-            const int32_t last = (first + kNbLeaf < n) ? first + kNbLeaf : n;
-            for (int32_t j = first; j < last; ++j) {
-                const double px = cpos[j].x, py = cpos[j].y;
+    nb_walk(boxes, off, spos, levels, n, valid,
+            [&](const bool mine, const NbNode &nd) {
+                double unused;
+                const double lb = nb_bound<false>(nd.box, q, unused);
+                return mine && list.wants(lb);
+            },
+            [&](const bool in, const int32_t j, const double px, const double py) {
                 const uint32_t id = cidx[j];
                 const double dx = px - q.x, dy = py - q.y;
                 if (in && (j < lo || j > hi)) {
                     ++ev;
                     list.insert(dx * dx + dy * dy, id);
                 }
-            }
-        } else {
-            const int32_t below = co[level] - co[level - 1];
-            for (int c = 3; c >= 0; --c)                       // (pushed last first: child 0 is opened first)
-                if (4 * node + c < below) st.push(nb_entry(level - 1, 4 * node + c), open);
-        }
-    }
+            });
 
     if (valid) {
         for (int e = 0; e < k; ++e) {
@@ -360,16 +422,8 @@ __global__ __launch_bounds__(kBlock) void nb_count_kernel(const double2 *__restr
                                                           const double2 *__restrict__ points, const uint32_t *__restrict__ order,
                                                           int64_t s0, int64_t nq, double r2, uint32_t *__restrict__ counts)
 {
-    const int lane = lane_id();
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = r < nq;
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
-    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
-    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
-#pragma clang diagnostic pop
 
     double2 q{0.0, 0.0};
     int32_t self = -1;
@@ -378,41 +432,19 @@ __global__ __launch_bounds__(kBlock) void nb_count_kernel(const double2 *__restr
         else { self = (int32_t)(s0 + r); q = spos[self]; }
     }
     uint32_t cnt = 0;
-    LaneStack st;
-    const uint64_t all = __ballot(valid);
-    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
-    while (st.sp > 0) {
-        int32_t entry;
-        uint64_t mask;
-        st.pop(entry, mask);
-        const int level = entry >> 24;
-        const int32_t node = entry & 0xffffff;
-        const int32_t at = co[level] + node;
-        NbBox b;
-        b.lox = cb[at].lox; b.hix = cb[at].hix; b.loy = cb[at].loy; b.hiy = cb[at].hiy;
-        double ub;
-        const double lb = nb_bound<true>(b, q, ub);
-        const bool in = (((mask >> lane) & 1ull) != 0ull) && lb <= r2;
-        const bool whole = in && ub <= r2;
-        // the bodies of the node: sorted positions [first, last)
-        const int64_t span = (int64_t)kNbLeaf << (2 * level);
-        const int64_t first = (int64_t)node * span;
-        const int64_t last = (first + span < n) ? first + span : (int64_t)n;
-        if (whole) cnt += (uint32_t)(last - first) - ((self >= first && self < last) ? 1u : 0u);
-        const bool rest = in && !whole;
-        const uint64_t open = __ballot(rest);
-        if (open == 0ull) continue;
-        if (level == 0) {
-            for (int32_t j = (int32_t)first; j < (int32_t)last; ++j) {
-                const double dx = cpos[j].x - q.x, dy = cpos[j].y - q.y;
+    nb_walk(boxes, off, spos, levels, n, valid,
+            [&](const bool mine, const NbNode &nd) {
+                double ub;
+                const double lb = nb_bound<true>(nd.box, q, ub);
+                const bool in = mine && lb <= r2;
+                const bool whole = in && ub <= r2;
+                if (whole) cnt += (uint32_t)(nd.last - nd.first) - ((self >= nd.first && self < nd.last) ? 1u : 0u);
+                return in && !whole;
+            },
+            [&](const bool rest, const int32_t j, const double px, const double py) {
+                const double dx = px - q.x, dy = py - q.y;
                 if (rest && j != self && dx * dx + dy * dy <= r2) ++cnt;
-            }
-        } else {
-            const int32_t below = co[level] - co[level - 1];
-            for (int c = 3; c >= 0; --c)
-                if (4 * node + c < below) st.push(nb_entry(level - 1, 4 * node + c), open);
-        }
-    }
+            });
     if (valid) counts[r] = cnt;
 }
 

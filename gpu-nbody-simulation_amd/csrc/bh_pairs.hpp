@@ -7,12 +7,10 @@
 // Bins: nb + 2 of them on the squared edges e2[0 .. nb]: bin(d2) = the number of edges with e2[k] < d2 -- 0: d2 <= e2[0];
 // k + 1: e2[k] < d2 <= e2[k + 1]; nb + 1: d2 > e2[nb].  The upper edge is inclusive, as in bh_count_within and bh_groups.
 //
-// Structure and traversal: those of nb_count_kernel -- the Morton-sorted copies and the box hierarchy of nb_build, one lane
-// per query in sorted order, the boxes and leaf bodies read at wave-uniform addresses in the constant address space, one
-// LaneStack per wave.
+// Structure and traversal: the index of nb_build and nb_walk (bh_neighbours.hpp), one lane per query in sorted order.
 //
-// Why taking a node whole is exact.  bh_neighbours.hpp shows that every body of a node has a computed d2 with lb <= d2 <= ub,
-// lb and ub the two bounds of nb_bound<true>.  bin() is non-decreasing in d2.  So with bin(lb) == bin(ub) every body of the
+// Why taking a node whole is exact.  Every body of a node has a computed d2 with lb <= d2 <= ub, lb and ub the two bounds of
+// nb_bound<true> (the argument stands with nb_walk).  bin() is non-decreasing in d2.  So with bin(lb) == bin(ub) every body of the
 // node falls in that bin, and the node's body count is added to it without opening the node.  Otherwise the node is opened;
 // a leaf's bodies are binned one by one, searching upward from bin(lb), never past bin(ub).  Nodes wholly below e2[0] or wholly
 // beyond e2[nb] are taken whole into the two outer counters like any other.
@@ -61,7 +59,6 @@ __global__ __launch_bounds__(kBlock) void pair_count_kernel(const double2 *__res
     for (int k = threadIdx.x; k < nb + 3; k += kBlock) h[k] = 0ull;
     __syncthreads();
 
-    const int lane = lane_id();
 #ifdef BHGPU_PAIR_FORWARD                                       // A/B builds only: workgroup b takes group b
     const int64_t group = blockIdx.x;
 #else
@@ -69,13 +66,6 @@ __global__ __launch_bounds__(kBlock) void pair_count_kernel(const double2 *__res
 #endif
     const int64_t r = group * kBlock + threadIdx.x;
     const bool valid = r < nq;
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    const NbBox BH64_CONSTANT *cb = (const NbBox BH64_CONSTANT *)boxes;
-    const int32_t BH64_CONSTANT *co = (const int32_t BH64_CONSTANT *)off;
-    const double2 BH64_CONSTANT *cpos = (const double2 BH64_CONSTANT *)spos;
-#pragma clang diagnostic pop
 
     double2 q{0.0, 0.0};
     int64_t s = n;                                             // bodies before the query: a point counts them all
@@ -85,46 +75,33 @@ __global__ __launch_bounds__(kBlock) void pair_count_kernel(const double2 *__res
     }
     const double e2_first = e2[0], e2_last = e2[nb];
     uint32_t below = 0, beyond = 0, ev = 0;                    // (a lane meets fewer than 2^24 bodies)
-    LaneStack st;
-    const uint64_t all = __ballot(valid);
-    if (all != 0ull) st.push(nb_entry(levels - 1, 0), all);
-    while (st.sp > 0) {
-        int32_t entry;
-        uint64_t mask;
-        st.pop(entry, mask);
-        const int level = entry >> 24;
-        const int32_t node = entry & 0xffffff;
-        const int32_t at = co[level] + node;
-        NbBox b;
-        b.lox = cb[at].lox; b.hix = cb[at].hix; b.loy = cb[at].loy; b.hiy = cb[at].hiy;
-        double ub;
-        const double lb = nb_bound<true>(b, q, ub);
-        // the bodies of the node: sorted positions [first, last), m of them before the query
-        const int64_t span = (int64_t)kNbLeaf << (2 * level);
-        const int64_t first = (int64_t)node * span;
-        const int64_t last = (first + span < n) ? first + span : (int64_t)n;
-        const int64_t upto = (s < last) ? s : last;
-        const uint32_t m = (upto > first) ? (uint32_t)(upto - first) : 0u;
-        const bool in = (((mask >> lane) & 1ull) != 0ull) && m != 0u;
-        int kl = 0, ku = 0;
-        bool rest = false;
-        if (in) {
-            if (ub <= e2_first) below += m;
-            else if (lb > e2_last) beyond += m;
-            else {
-                kl = pair_bin(e2, 0, nb + 1, lb);
-                ku = pair_bin(e2, kl, nb + 1, ub);
-                if (kl == ku) atomicAdd(&h[kl], (unsigned long long)m);
-                else rest = true;
-            }
-        }
-        const uint64_t open = __ballot(rest);
-        if (open == 0ull) continue;
-        if (level == 0) {
-            const double edge = rest ? e2[kl] : 0.0;
-            uint32_t c0 = 0, c1 = 0;                           // of the bins kl and kl + 1
-            for (int32_t j = (int32_t)first; j < (int32_t)last; ++j) {
-                const double dx = cpos[j].x - q.x, dy = cpos[j].y - q.y;
+    int kl = 0, ku = 0;                                        // of the node last visited: bin(lb), bin(ub) ...
+    double edge = 0.0;                                         // ... e2[kl] of an opened leaf ...
+    uint32_t c0 = 0, c1 = 0;                                   // ... and what it adds to the bins kl and kl + 1
+    nb_walk(boxes, off, spos, levels, n, valid,
+            [&](const bool mine, const NbNode &nd) {
+                double ub;
+                const double lb = nb_bound<true>(nd.box, q, ub);
+                // m of the node's bodies lie before the query
+                const int64_t upto = (s < nd.last) ? s : nd.last;
+                const uint32_t m = (upto > nd.first) ? (uint32_t)(upto - nd.first) : 0u;
+                bool rest = false;
+                kl = ku = 0;
+                if (mine && m != 0u) {
+                    if (ub <= e2_first) below += m;
+                    else if (lb > e2_last) beyond += m;
+                    else {
+                        kl = pair_bin(e2, 0, nb + 1, lb);
+                        ku = pair_bin(e2, kl, nb + 1, ub);
+                        if (kl == ku) atomicAdd(&h[kl], (unsigned long long)m);
+                        else rest = true;
+                    }
+                }
+                if (nd.level == 0) edge = rest ? e2[kl] : 0.0;
+                return rest;
+            },
+            [&](const bool rest, const int32_t j, const double px, const double py) {
+                const double dx = px - q.x, dy = py - q.y;
                 const double d2 = dx * dx + dy * dy;
                 if (rest && j < s) {
                     ++ev;
@@ -132,15 +109,12 @@ __global__ __launch_bounds__(kBlock) void pair_count_kernel(const double2 *__res
                     else if (ku == kl + 1 || !(e2[kl + 1] < d2)) ++c1;
                     else atomicAdd(&h[pair_bin(e2, kl + 2, ku, d2)], 1ull);
                 }
-            }
-            if (c0) atomicAdd(&h[kl], (unsigned long long)c0);
-            if (c1) atomicAdd(&h[kl + 1], (unsigned long long)c1);
-        } else {
-            const int32_t nbelow = co[level] - co[level - 1];
-            for (int c = 3; c >= 0; --c)                       // (pushed last first: child 0 is opened first)
-                if (4 * node + c < nbelow) st.push(nb_entry(level - 1, 4 * node + c), open);
-        }
-    }
+            },
+            [&] {
+                if (c0) atomicAdd(&h[kl], (unsigned long long)c0);
+                if (c1) atomicAdd(&h[kl + 1], (unsigned long long)c1);
+                c0 = c1 = 0;
+            });
     if (below) atomicAdd(&h[0], (unsigned long long)below);
     if (beyond) atomicAdd(&h[nb + 1], (unsigned long long)beyond);
     if (ev) atomicAdd(&h[nb + 2], (unsigned long long)ev);
