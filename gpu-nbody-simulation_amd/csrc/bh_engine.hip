@@ -34,6 +34,7 @@
 #include "bh_pairs.hpp"
 #include "bh_groups.hpp"
 #include "bh_mst.hpp"
+#include "bh_binaries.hpp"
 #include "bh_walk_fast.h"
 #include "bh_run_state.hpp"
 #include "bh_queries_state.hpp"
@@ -171,6 +172,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     PairState pair;
     FofState fof;
     MstState mst;
+    BinState bin;
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -1104,7 +1106,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
-    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev); destroy(c->bin.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -1,8 +1,9 @@
 // bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, the field
-// at points, neighbour queries, pair counts, friends-of-friends groups and spanning trees, with their entry points of
-// include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
+// at points, neighbour queries, pair counts, friends-of-friends groups, spanning trees and bound pairs, with their entry points
+// of include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
 // (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp,
-// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp, bh_groups.hpp and bh_mst.hpp, the state in bh_queries_state.hpp,
+// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
+// bh_queries_state.hpp,
 // the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes first.
 #pragma once
 
@@ -587,6 +588,22 @@ double ms_since(std::chrono::steady_clock::time_point t0)
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// ---- bound pairs (bh_binaries.hpp) on the structure of the neighbour queries.  They read pos, vel, mass and orig as they lie in
+// memory and write buffers of their own -- no force tree, no build, so there is nothing for a quiet scope to put back: a step
+// before and after runs bit for bit as it would have.
+int bin_alloc(bh_ctx *c, int64_t n)
+{
+    BinState &s = c->bin;
+    if (n <= s.block.cap) return BH_OK;
+    const int64_t cap = grown_capacity(n);
+    int32_t off[kNbMaxLevels + 1];
+    nb_levels(cap, off);
+    const size_t nodes = (size_t)off[kNbMaxLevels] + kNbMaxLevels, b = (size_t)cap, room = b / 2 + 1;       // (nodes: as nb_alloc)
+    return block_regrow(c, s.block, cap, {part(&s.svel, b), part(&s.smass, b), part(&s.nodemass, nodes), part(&s.eps, b),
+                                          part(&s.rec, room * kBinRecord), part(&s.partner, b), part(&s.ctr, 1), part(&s.psort, b),
+                                          part(&s.rec_lo, room), part(&s.rec_hi, room)});
+}
+
 }  // namespace
 
 extern "C" {
@@ -1140,6 +1157,122 @@ int bh_spanning_tree_times(bh_ctx *c, double *build_ms, double *rounds_ms, doubl
     *build_ms = c->mst.build_ms;
     *rounds_ms = c->mst.rounds_ms;
     *sort_ms = c->mst.sort_ms;
+    return BH_OK;
+}
+
+int bh_binaries(bh_ctx *c, double max_separation, int64_t *partner, double *eps, int64_t *n_pairs, uint64_t *stats)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!(max_separation > 0.0)) return fail(c, BH_ERR_ARG, "bh_binaries: max_separation must be > 0 (+inf: no cut) and not NaN");
+    if (!n_pairs) return fail(c, BH_ERR_ARG, "bh_binaries: null n_pairs");
+    if (int rc = diag_check(c, "bh_binaries")) return rc;
+    if (!(c->cfg.G > 0.0)) return fail(c, BH_ERR_ARG, "bh_binaries: G must be > 0 (the energy bound of the search rests on it)");
+    const int64_t n = c->n;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, "bh_binaries: more than 2^24 bodies (their indices share a key word)");
+    NbState &nb = c->nb;
+    BinState &s = c->bin;
+    s.cat_lo.clear(); s.cat_hi.clear(); s.cat_rec.clear();
+    s.build_ms = s.search_ms = s.cat_ms = 0.0;
+    *n_pairs = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (n == 0) return BH_OK;
+    const double R2 = max_separation * max_separation;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = nb_alloc(c, n, 0, 0)) return rc;
+    if (int rc = bin_alloc(c, n)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_binaries", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const unsigned grid = blocks_for(n, kBlock);
+    const int32_t n32 = (int32_t)n;
+    const int64_t room = s.block.cap / 2 + 1;
+    int32_t off[kNbMaxLevels + 1];
+    nb_levels(n, off);
+    BH_HIP(c, hipMemsetAsync(s.ctr, 0, sizeof(BinCounters), st));
+    state_ptrs(c, [&](auto, auto vel, auto mass) {
+        hipLaunchKernelGGL((bin_gather_kernel<Pointee<decltype(vel)>, Pointee<decltype(mass)>>), dim3(grid), dim3(kBlock), 0, st, vel, mass,
+                           nb.slot, n, s.svel, s.smass);
+    });
+    for (int l = 0; l < levels; ++l) {
+        const int32_t count = off[l + 1] - off[l], below = l ? off[l] - off[l - 1] : 0;
+        hipLaunchKernelGGL(bin_nodemass_kernel, dim3(blocks_for(count, kBlock)), dim3(kBlock), 0, st, s.smass,
+                           s.nodemass + (l ? off[l - 1] : 0), l, below, n32, count, s.nodemass + off[l]);
+    }
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[0])) return rc;
+    hipLaunchKernelGGL(bin_search_kernel, dim3(grid), dim3(kBlock), 0, st, nb.spos, s.svel, s.smass, nb.sidx, s.nodemass, nb.boxes, nb.off,
+                       levels, n32, R2, c->cfg.G, s.partner, s.eps, s.psort, s.ctr);
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[1])) return rc;
+    hipLaunchKernelGGL(bin_pairs_kernel, dim3(grid), dim3(kBlock), 0, st, nb.spos, s.svel, s.smass, nb.sidx, s.psort, n32, c->cfg.G, room,
+                       s.rec_lo, s.rec_hi, s.rec, s.ctr);
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[2])) return rc;
+    BinCounters ctr{};
+    BH_HIP(c, hipMemcpyAsync(&ctr, s.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    if (partner) BH_HIP(c, hipMemcpyAsync(partner, s.partner, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (eps) BH_HIP(c, hipMemcpyAsync(eps, s.eps, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (int rc = span_ms(c, nb.ev[0], s.ev[0], &s.build_ms)) return rc;
+    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.search_ms)) return rc;
+    if (int rc = span_ms(c, s.ev[1], s.ev[2], &s.cat_ms)) return rc;
+    const int64_t pairs = (int64_t)ctr.pairs;
+    if (pairs > room || 2 * pairs > n)
+        return fail(c, BH_ERR_DEVICE, "bh_binaries: " + std::to_string(pairs) + " mutual pairs for " + std::to_string(n) + " bodies");
+    // the records as the atomics placed them; the catalogue is ascending in lo (a body is in one pair at most: no ties)
+    std::vector<uint32_t> lo((size_t)pairs), hi((size_t)pairs);
+    std::vector<double> rec((size_t)pairs * kBinRecord);
+    if (pairs > 0) {
+        BH_HIP(c, hipMemcpyAsync(lo.data(), s.rec_lo, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(hi.data(), s.rec_hi, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipMemcpyAsync(rec.data(), s.rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> place((size_t)n, -1);                 // body -> its record where it is a lo: one pass over the bodies orders them
+    for (int64_t k = 0; k < pairs; ++k) {
+        if (lo[(size_t)k] >= (uint32_t)n || place[lo[(size_t)k]] >= 0)
+            return fail(c, BH_ERR_DEVICE, "bh_binaries: record " + std::to_string(k) + " names body " + std::to_string(lo[(size_t)k]) +
+                                          " a second time, or outside the state");
+        place[lo[(size_t)k]] = (int32_t)k;
+    }
+    std::vector<int64_t> order;
+    order.reserve((size_t)pairs);
+    for (int64_t i = 0; i < n; ++i)
+        if (place[(size_t)i] >= 0) order.push_back(place[(size_t)i]);
+    s.cat_lo.resize((size_t)pairs); s.cat_hi.resize((size_t)pairs); s.cat_rec.resize(rec.size());
+    for (int64_t k = 0; k < pairs; ++k) {
+        const size_t g = (size_t)order[(size_t)k];
+        s.cat_lo[(size_t)k] = (int64_t)lo[g];
+        s.cat_hi[(size_t)k] = (int64_t)hi[g];
+        std::copy(rec.begin() + (std::ptrdiff_t)(g * kBinRecord), rec.begin() + (std::ptrdiff_t)((g + 1) * kBinRecord),
+                  s.cat_rec.begin() + (std::ptrdiff_t)((size_t)k * kBinRecord));
+    }
+    s.cat_ms += ms_since(t0);
+    *n_pairs = pairs;
+    if (stats) { stats[0] = ctr.evals; stats[1] = ctr.max_evals; stats[2] = ctr.opened; stats[3] = ctr.pairs; }
+    return BH_OK;
+}
+
+int bh_binaries_catalogue(bh_ctx *c, int64_t max_records, int64_t *lo, int64_t *hi, double *records)
+{
+    if (!c) return BH_ERR_ARG;
+    if (max_records < 0) return fail(c, BH_ERR_ARG, "bh_binaries_catalogue: max_records < 0");
+    const BinState &s = c->bin;
+    const int64_t g = (int64_t)s.cat_lo.size();
+    if (g > max_records) return fail(c, BH_ERR_CAPACITY, "bh_binaries_catalogue: the catalogue has " + std::to_string(g) + " records");
+    if (lo) std::copy(s.cat_lo.begin(), s.cat_lo.end(), lo);
+    if (hi) std::copy(s.cat_hi.begin(), s.cat_hi.end(), hi);
+    if (records) std::copy(s.cat_rec.begin(), s.cat_rec.end(), records);
+    return BH_OK;
+}
+
+int bh_binaries_times(bh_ctx *c, double *build_ms, double *search_ms, double *catalogue_ms)
+{
+    if (!c || !build_ms || !search_ms || !catalogue_ms) return fail(c, BH_ERR_ARG, "bh_binaries_times: null argument");
+    *build_ms = c->bin.build_ms;
+    *search_ms = c->bin.search_ms;
+    *catalogue_ms = c->bin.cat_ms;
     return BH_OK;
 }
 

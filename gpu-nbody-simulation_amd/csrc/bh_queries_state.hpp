@@ -100,4 +100,22 @@ struct MstState {
     double build_ms = 0.0, rounds_ms = 0.0, sort_ms = 0.0;      // of the last call (bh_spanning_tree_times)
 };
 
+// bound pairs (bh_binaries.hpp): one block for up to block.cap bodies beside the neighbour structure's -- the sorted velocities
+// and masses, the nodes' mass bounds, the partners in caller order and as sorted positions, room for block.cap / 2 + 1 records --,
+// and the catalogue of the last bh_binaries call on the host, ascending in lo (as FofState's: that call's result, whatever the
+// run does afterwards)
+struct BinState {
+    DevBlock block;
+    double2 *svel = nullptr;
+    double *smass = nullptr, *nodemass = nullptr, *eps = nullptr, *rec = nullptr;
+    int64_t *partner = nullptr;
+    int32_t *psort = nullptr;
+    uint32_t *rec_lo = nullptr, *rec_hi = nullptr;
+    BinCounters *ctr = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};             // after the sorted copies and mass bounds, the search, the records
+    double build_ms = 0.0, search_ms = 0.0, cat_ms = 0.0;       // of the last call (bh_binaries_times)
+    std::vector<int64_t> cat_lo, cat_hi;
+    std::vector<double> cat_rec;                                // kBinRecord doubles a record
+};
+
 }  // namespace bh

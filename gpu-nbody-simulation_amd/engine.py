@@ -9,7 +9,7 @@ import ctypes as C
 import enum
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -376,6 +376,71 @@ def groups_from_sums(label, n_groups: int, linking_length: float, min_members: i
     return BhGroups(np.asarray(label, dtype=np.int64), int(n_groups), float(linking_length), int(min_members),
                     np.asarray(ids, dtype=np.int64), np.asarray(counts, dtype=np.int64), val[0], com, vel,
                     sums if raw else None, exponents.copy() if raw else None, stats)
+
+
+@dataclass
+class BhBinaries:
+    """Bound pairs of the current state (binaries): every body's partner -- among the bodies j within max_separation with
+    two-body energy eps_ij = 0.5 * |v_j - v_i|^2 - G (m_i + m_j) / |x_j - x_i| < 0, the one first in the order (eps_ij, j) --
+    and the catalogue of the mutual pairs lo < hi, ascending in lo, with their Keplerian elements as the device computed them
+    (include/bhgpu.h).  The engine's softening does not enter.  The state is read as it is: after step() the velocities lie half
+    a step from the positions; synchronised elements want a step_kdk state."""
+    n: int
+    max_separation: float
+    partner: np.ndarray          # (n,) int64: caller index of the partner, -1: none
+    eps: np.ndarray              # (n,): eps of (body, partner), +inf: none
+    lo: np.ndarray               # (p,) int64
+    hi: np.ndarray               # (p,) int64
+    separation: np.ndarray       # (p,): r = sqrt(d2)
+    energy: np.ndarray           # (p,): eps, per unit reduced mass
+    semi_major_axis: np.ndarray  # (p,)
+    eccentricity: np.ndarray     # (p,)
+    period: np.ndarray           # (p,)
+    binding_energy: np.ndarray   # (p,): -(m_lo m_hi / M) eps > 0
+    mass: np.ndarray             # (p,): M = m_lo + m_hi
+    com: np.ndarray              # (p, 2)
+    velocity: np.ndarray         # (p, 2)
+    stats: tuple | None = None   # with_stats=True: (energies computed, the most by one body, nodes opened, pairs)
+    mean_kinetic: object = None  # what hardness() divides by without an argument: a float, or a callable that gives it
+
+    @property
+    def total_binding_energy(self) -> float:
+        return math.fsum(self.binding_energy.tolist())
+
+    @property
+    def fraction(self) -> float:
+        """the fraction of bodies in a catalogued pair: 2 pairs / n"""
+        return 2.0 * len(self.lo) / self.n if self.n else 0.0
+
+    def hardness(self, mean_kinetic=None) -> np.ndarray:
+        """binding_energy / mean_kinetic; by default the mean kinetic energy of a body, the engine's energy().kinetic / n, taken
+        at the first such call (so call it before the run goes on) and kept"""
+        if mean_kinetic is None:
+            if callable(self.mean_kinetic):
+                self.mean_kinetic = float(self.mean_kinetic())
+            mean_kinetic = self.mean_kinetic
+        if mean_kinetic is None:
+            raise ValueError("hardness needs a mean kinetic energy")
+        return self.binding_energy / float(mean_kinetic)
+
+    def within(self, a_max: float) -> "BhBinaries":
+        """the catalogue's pairs with semi_major_axis <= a_max (partner and eps stay whole)"""
+        keep = self.semi_major_axis <= float(a_max)
+        return replace(self, **{f: getattr(self, f)[keep] for f in BINARIES_COLUMNS})
+
+
+BINARIES_COLUMNS = ("lo", "hi", "separation", "energy", "semi_major_axis", "eccentricity", "period", "binding_energy", "mass", "com",
+                    "velocity")
+
+
+def binaries_from_records(partner, eps, lo, hi, records, max_separation: float, stats=None, mean_kinetic=None) -> BhBinaries:
+    """BhBinaries of the partners and the catalogue's records (p, 11) of bh_binaries_catalogue."""
+    rec = np.asarray(records, dtype=np.float64).reshape(-1, 11)
+    partner = np.asarray(partner, dtype=np.int64).reshape(-1)
+    return BhBinaries(len(partner), float(max_separation), partner, np.asarray(eps, dtype=np.float64).reshape(-1),
+                      np.asarray(lo, dtype=np.int64).reshape(-1), np.asarray(hi, dtype=np.int64).reshape(-1),
+                      rec[:, 0].copy(), rec[:, 1].copy(), rec[:, 2].copy(), rec[:, 3].copy(), rec[:, 4].copy(), rec[:, 5].copy(),
+                      rec[:, 6].copy(), rec[:, 7:9].copy(), rec[:, 9:11].copy(), stats, mean_kinetic)
 
 
 MST_SUBSET_MAX = 512                    # BH_MST_SUBSET_MAX
@@ -1131,6 +1196,33 @@ class BarnesHutEngine:
         one subset_spanning_trees call -- see mass_segregation_sets and mass_segregation_from."""
         members = self.mass_segregation_sets(n_massive, n_random, seed, weights)
         return mass_segregation_from(self.subset_spanning_trees(members)[2], members)
+
+    # -- binaries -------------------------------------------------------------------------------
+    def binaries(self, max_separation: float, with_stats: bool = False) -> BhBinaries:
+        """Bound pairs of the current state: every body's partner among the bodies within max_separation (inclusive; inf: no
+        cut, and a body bound to nobody then searches everything) that are bound to it, eps_ij < 0, first in the order
+        (eps_ij, caller index) -- the brute-force definition bit for bit --, and the catalogue of the mutual pairs with their
+        Keplerian elements; see BhBinaries.  The softening does not enter.  Reads the state as it is (synchronised elements want
+        a step_kdk state); the run is not perturbed."""
+        n = self.n
+        partner, eps = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1))
+        npairs = C.c_int64()
+        st = (C.c_uint64 * 4)()
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.bh_binaries(self._h, float(max_separation), partner.ctypes.data_as(i64), _dptr(eps), C.byref(npairs), st))
+        p = npairs.value
+        lo, hi, rec = np.zeros(max(p, 1), dtype=np.int64), np.zeros(max(p, 1), dtype=np.int64), np.zeros((max(p, 1), 11))
+        self._check(self._lib.bh_binaries_catalogue(self._h, p, lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), _dptr(rec)))
+        return binaries_from_records(partner[:n], eps[:n], lo[:p], hi[:p], rec[:p], max_separation,
+                                     tuple(int(v) for v in st) if with_stats else None,
+                                     (lambda: self.energy().kinetic / n) if n else None)
+
+    def binaries_times(self):
+        """(build_ms, search_ms, catalogue_ms) of the last binaries(): HIP events around the index's build with the sorted
+        velocities, masses and mass bounds, the partner search, and the pairs with their elements (the host's ordering added)."""
+        b, s, k = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.bh_binaries_times(self._h, C.byref(b), C.byref(s), C.byref(k)))
+        return b.value, s.value, k.value
 
     def local_density(self, k: int = 6):
         """(sigma (n,), r_k (n,)): Casertano and Hut's k-th-neighbour density estimate in two dimensions from one

@@ -85,7 +85,7 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      pairs_file: str | None = None, pairs_bins: int | None = None, pairs_range=None, pairs_spacing: str = "log",
                      pairs_randoms: int | None = None, pairs_seed: int = 0, mst_file: str | None = None,
                      segregation_file: str | None = None, segregation_massive: int | None = None, segregation_random: int = 500,
-                     segregation_seed: int = 0):
+                     segregation_seed: int = 0, binaries_file: str | None = None, binaries_separation: float | None = None):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -134,6 +134,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     segregation_file: after the last step, also write the mass segregation ratio of the final state
     (BarnesHutEngine.mass_segregation(segregation_massive, segregation_random, segregation_seed)): the line
     `# k,ratio,sigma,l_massive,l_random_mean` and one row (%.17g).  Not part of gpu_parallel_duration_us.
+    binaries_file: after the last step, also write the bound pairs of the final state
+    (BarnesHutEngine.binaries(binaries_separation)): the line `# i,j,r,a,e,period,binding_energy`, then one row per mutual pair
+    (%.17g), ascending in i: the two body indices, their separation, the semi-major axis, the eccentricity, the period and the
+    binding energy -- Keplerian, whatever the softening, of the state as it is (with integrator "kdk" velocities and positions
+    are at the same time).  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -143,6 +148,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("groups_file needs a linking_length")
     if (segregation_file is None) != (segregation_massive is None):
         raise ValueError("segregation_file and segregation_massive go together")
+    if (binaries_file is None) != (binaries_separation is None):
+        raise ValueError("binaries_file and binaries_separation go together")
     if integrator not in ("euler", "kdk"):
         raise ValueError("integrator must be 'euler' or 'kdk'")
     if (profile_file is None) != (profile_bins is None):
@@ -306,6 +313,12 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 f.write("# k,ratio,sigma,l_massive,l_random_mean\n")
                 f.write("%d,%.17g,%.17g,%.17g,%.17g\n" % (ms.n_massive, ms.ratio, ms.sigma, ms.l_massive,
                                                           math.fsum(ms.l_random.tolist()) / len(ms.l_random)))
+        if binaries_file is not None:
+            b = eng.binaries(binaries_separation)
+            with open(os.path.join(out_dir, binaries_file) if not os.path.isabs(binaries_file) else binaries_file, "w") as f:
+                f.write("# i,j,r,a,e,period,binding_energy\n")
+                f.write("".join("%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(b.lo, b.hi, b.separation, b.semi_major_axis,
+                                                                                    b.eccentricity, b.period, b.binding_energy)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr, lagrange):
@@ -455,6 +468,11 @@ def _parse(argv):
     ap.add_argument("--segregation-massive", type=int, default=None, metavar="K", help="the K most massive bodies (2 .. 512)")
     ap.add_argument("--segregation-random", type=int, default=None, metavar="R", help="random sets of K bodies (default 500)")
     ap.add_argument("--segregation-seed", type=int, default=None, metavar="S", help="seed of the random sets (default 0)")
+    ap.add_argument("--binaries-file", default=None, metavar="PATH",
+                    help="after the last step, also write i,j,r,a,e,period,binding_energy of every bound pair of the final state "
+                         "(needs --binaries-separation)")
+    ap.add_argument("--binaries-separation", type=float, default=None, metavar="R",
+                    help="largest separation of a pair's two bodies (> 0; inf: no cut)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -522,6 +540,10 @@ def _parse(argv):
         ap.error("--segregation-massive: 2 .. 512")
     if a.segregation_random is not None and a.segregation_random < 1:
         ap.error("--segregation-random: at least 1")
+    if (a.binaries_file is None) != (a.binaries_separation is None):
+        ap.error("--binaries-file and --binaries-separation go together")
+    if a.binaries_separation is not None and not a.binaries_separation > 0.0:
+        ap.error("--binaries-separation: > 0")
     a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     if a.groups_min is not None and a.groups_min < 1:
@@ -600,7 +622,7 @@ def main(argv=None) -> int:
         pairs_range=a.pairs_range, pairs_spacing=a.pairs_spacing or "log", pairs_randoms=a.pairs_randoms,
         pairs_seed=a.pairs_seed or 0, mst_file=a.mst_file, segregation_file=a.segregation_file,
         segregation_massive=a.segregation_massive, segregation_random=500 if a.segregation_random is None else a.segregation_random,
-        segregation_seed=a.segregation_seed or 0)
+        segregation_seed=a.segregation_seed or 0, binaries_file=a.binaries_file, binaries_separation=a.binaries_separation)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -629,6 +629,51 @@ int bh_spanning_tree(bh_ctx *ctx, int64_t *lo, int64_t *hi, double *d2, uint64_t
 int bh_spanning_tree_subsets(bh_ctx *ctx, const int64_t *members, int64_t n_sets, int32_t k, int64_t *lo, int64_t *hi, double *d2);
 int bh_spanning_tree_times(bh_ctx *ctx, double *build_ms, double *rounds_ms, double *sort_ms);
 
+/* --- binaries: which bodies are bound pairs, and a catalogue of their Keplerian elements -----------------------------------------
+ * Energy.  For bodies i != j of the CURRENT state, in fp64 with nothing fused, sqrt and / correctly rounded, in every precision
+ *   (an fp32 state is widened first, exactly), G the context's:
+ *     dx = x_j - x_i; dy = y_j - y_i; d2 = dx * dx + dy * dy                     (the d2 of bh_count_within)
+ *     ux = vx_j - vx_i; uy = vy_j - vy_i; v2 = ux * ux + uy * uy
+ *     M = m_i + m_j;  eps_ij = 0.5 * v2 - (G * M) / sqrt(d2)                     (two-body energy per unit reduced mass)
+ *   eps_ij and eps_ji are the same bits.  The softening of the configuration does NOT enter: the elements are Keplerian.  The
+ *   state is read as it is: after bh_step the velocities lie half a step from the positions; synchronised elements want the
+ *   state of bh_step_kdk.
+ * Candidates of i, for max_separation R (R2 = R * R, formed once on the host): all j != i with 0 < d2 <= R2 and eps_ij < 0.  The
+ *   upper edge is inclusive, as in bh_count_within; coincident bodies are never candidates of each other.  A NaN velocity or
+ *   mass follows the formulas: every comparison is false, such a body is nobody's candidate and has none.
+ * Partner.  partner[i] (n of them, caller order; may be NULL) is the candidate first in the strict total order (eps_ij, caller
+ *   index j), with eps[i] = that eps_ij (may be NULL); -1 with eps = +inf when there is no candidate.  A pure function of the
+ *   state and R: no launch shape, traversal order or race decides any of it.
+ * Binary.  A pair lo < hi (caller indices) with partner[lo] == hi and partner[hi] == lo.  The catalogue lists them ASCENDING in lo;
+ *   record k is lo[k], hi[k] and records[k][11], computed on the device in this order with i = lo, j = hi:
+ *     mu = G * M;  r = sqrt(d2);  eps as above
+ *     a = mu / (-2.0 * eps)                                                       semi-major axis
+ *     h = dx * uy - dy * ux
+ *     e = sqrt(max(1.0 + ((2.0 * eps) * (h * h)) / (mu * mu), 0.0))               eccentricity (max(x, 0) is x > 0 ? x : 0)
+ *     period = 6.283185307179586 * sqrt(((a * a) * a) / mu)
+ *     binding = -(((m_i * m_j) / M) * eps)                                        > 0
+ *     com = ((m_i * x_i + m_j * x_j) / M, same in y);  velocity likewise
+ *   records[k] = {r, eps, a, e, period, binding, M, com x, com y, velocity x, velocity y}.
+ * bh_binaries: builds the index of the neighbour queries and, beside it, the sorted velocities and masses and the largest mass
+ *   under every node; searches (a lane drops a node only on a lower bound of its distances or of its energies that rounding
+ *   cannot invert: DESIGN.md section 27); finds the mutual pairs and their elements; waits for the stream.  R must be > 0 and not
+ *   NaN; +inf means no cut -- a body that is bound to nobody then searches every body.  *n_pairs: the records of the catalogue.
+ *   stats (may be NULL) = {energies computed, the most by one body, nodes opened, pairs}: deterministic for a given state and
+ *   call; a measure of the work and no part of the answer.
+ * bh_binaries_catalogue: copies out the catalogue of the last bh_binaries call -- that call's result, valid until the next
+ *   bh_binaries or bh_destroy whatever the run does in between.  lo[g], hi[g], records[g][11]; any of them may be NULL.  With
+ *   max_records below the *n_pairs of that call: BH_ERR_CAPACITY and nothing is copied.
+ * bh_binaries_times: HIP-event times of the last bh_binaries: the index's build with the sorted copies and mass bounds; the
+ *   search; the pairs and their elements (the host's ordering of the records added).
+ * They read the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.
+ * Errors: BH_ERR_ARG for R <= 0 or NaN, G <= 0, a null n_pairs, max_records < 0 and -- found by the bounds pass, with a message
+ *   that says so -- a non-finite body position.  BH_ERR_CAPACITY for more than 2^24 bodies.  BH_ERR_STATE before any upload, in LET
+ *   mode and with world > 1 (a pair can span ranks).  Without bodies *n_pairs = 0 and the catalogue is empty. */
+int bh_binaries(bh_ctx *ctx, double max_separation, int64_t *partner, double *eps, int64_t *n_pairs, uint64_t stats[4]);
+int bh_binaries_catalogue(bh_ctx *ctx, int64_t max_records, int64_t *lo, int64_t *hi, double *records /* n x 11 */);
+int bh_binaries_times(bh_ctx *ctx, double *build_ms, double *search_ms, double *catalogue_ms);
+
 /* --- tree output ------------------------------------------------------------------------
  * bh_export_tree: the tree of the last bh_build_tree/bh_compute_forces/bh_step in DFS
  * pre-order with children in index order -- the visiting order of TraverseTreeToFile
