@@ -24,6 +24,7 @@ from gpu_nbody_simulation_amd.project import runSimulationGpu  # noqa: E402
 from potential_ref import potential_walk  # noqa: E402
 import field_ref as FR  # noqa: E402
 import quiet_case as QC  # noqa: E402
+from reduction_ref import quotient_tolerance, sum2_tolerance  # noqa: E402
 
 P = G.Precision
 F64_TOL = 1e-12
@@ -162,11 +163,18 @@ def test_energy_reductions_against_fsum(prec):
         "L": mm * (x[:, 0] * u[:, 1] - x[:, 1] * u[:, 0]), "kin": 0.5 * mm * (u ** 2).sum(axis=1),
         "pot": 0.5 * mm * phi,
     }
-    got = {"mass": a.mass, "com0": a.com[0] * a.mass, "com1": a.com[1] * a.mass, "px": a.momentum[0],
-           "py": a.momentum[1], "L": a.angular_momentum, "kin": a.kinetic, "pot": a.potential}
+    got = {"mass": a.mass, "px": a.momentum[0], "py": a.momentum[1], "L": a.angular_momentum, "kin": a.kinetic,
+           "pot": a.potential}
+    n, ref, tol = len(mm), {}, {}
     for k, t in terms.items():
-        ref, scale = math.fsum(t), math.fsum(np.abs(t))
-        assert abs(got[k] - ref) <= 1e-13 * scale, (k, got[k], ref)
+        ref[k], scale = math.fsum(t), math.fsum(np.abs(t))
+        tol[k] = sum2_tolerance(ref[k], scale, n)
+        if k in got:
+            assert abs(got[k] - ref[k]) <= tol[k], (k, got[k], ref[k], tol[k])
+    for i, k in enumerate(("com0", "com1")):                 # the host's quotient of two sums
+        want = ref[k] / ref["mass"]
+        bound = quotient_tolerance(ref[k], ref["mass"], tol[k], tol["mass"])
+        assert abs(a.com[i] - want) <= bound, (k, a.com[i], want, bound)
     assert a.total == a.kinetic + a.potential and a.n_bodies == len(m)
 
 
