@@ -1351,7 +1351,7 @@ __global__ __launch_bounds__(kBlock, 5) void nodes_fast_kernel(
 // ---- exact bottom-up pass: ComputeMass, project.cu:473-502, ONE launch (small trees) -------------------
 // The reference recurses (children before parents).  Round 1 ran one launch per depth (9 at the
 // reference's cap, 31 at cap 32), each ~5 us of launch floor -- most of the build at N = 1,024.  Here every thread starts at one subdivided
-// cell; a cell whose four children are all leaves (pending == 0 after the node kernel) is summed at once,
+// cell; a cell whose four children are all leaves (no link with a child: what the node kernel counted as pending == 0) is summed at once,
 // and the thread then climbs: it decrements its parent's count of unfinished subdivided children and
 // whoever brings it to zero sums the parent.  Each cell is summed by exactly ONE thread, from the stored
 // values of its children in child order 0..3 starting from 0.0 -- the reference's order (project.cu:483-495)
@@ -1366,7 +1366,10 @@ __global__ __launch_bounds__(kBlock) void com_up_kernel(NodeD *__restrict__ gd, 
     const int64_t r0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint32_t total = ctr->n_internal;
     if (r0 >= (int64_t)total || (int64_t)total > internal_cap) return;
-    if (pending[r0] != 0) return;                     // a descendant's thread will come by
+    // a cell with a subdivided child is left to that child's thread: read from the links, which nothing writes in this launch --
+    // pending[r0] counts down during it, and a thread that starts late may find it at zero
+    const int32_t q0 = 1 + 4 * (int32_t)r0;
+    if (ld[q0].child >= 0 || ld[q0 + 1].child >= 0 || ld[q0 + 2].child >= 0 || ld[q0 + 3].child >= 0) return;
     uint32_t r = (uint32_t)r0;
     for (;;) {
         const int32_t node = self_node[r];
