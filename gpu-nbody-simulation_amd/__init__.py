@@ -9,7 +9,8 @@ library and a GPU, every compute entry point raises.
 from .engine import (BarnesHutEngine, BhConfig, BhError, BhForceError, BhGroups, BhLagrangian, BhMomentMap, BhPairCounts, BhRadialProfile, BhSortSnapshot,  # noqa: F401
                      BhTimestep, LagrangianSelect, Precision, correlation_from, density_centre_from, force_error_stats, lagrangian_from,
                      local_density_from, radial_edges, radial_exponents, radial_profile_from_planes,
-                     BhMassSegregation, BhSpanningTree, mass_segregation_from, spanning_tree_from, BhBinaries, binaries_from_records)
+                     BhMassSegregation, BhSpanningTree, mass_segregation_from, spanning_tree_from, BhBinaries, binaries_from_records,
+                     BhNeighbourLists, neighbour_lists_from)
 from .textio import loadSimulationDataFromText, save_init_files  # noqa: F401
 
 __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups", "BhMomentMap", "BhTimestep", "Precision",
@@ -17,4 +18,4 @@ __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups",
            "BhRadialProfile", "BhLagrangian", "LagrangianSelect", "radial_edges", "radial_exponents",
            "radial_profile_from_planes", "lagrangian_from", "BhPairCounts", "correlation_from", "BhSortSnapshot",
            "BhSpanningTree", "BhMassSegregation", "mass_segregation_from", "spanning_tree_from",
-           "BhBinaries", "binaries_from_records"]
+           "BhBinaries", "binaries_from_records", "BhNeighbourLists", "neighbour_lists_from"]

@@ -147,6 +147,10 @@ SIGNATURES = {
     "bh_binaries": (C.c_int, [_ctx, C.c_double, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "bh_binaries_catalogue": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
     "bh_binaries_times": (C.c_int, [_ctx, _dp, _dp, _dp]),
+    "bh_neighbour_lists": (C.c_int, [_ctx, _dp, C.c_int64, _dp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
+    "bh_neighbour_lists_times": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
+    "bh_neighbour_lists_evals": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_uint32)]),
     "bh_export_tree": (C.c_int, [_ctx, _vp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
     "bh_write_quadtree_file": (C.c_int, [_ctx, C.c_char_p]),
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),

@@ -31,6 +31,7 @@
 #include "bh_moments.hpp"
 #include "bh_radial.hpp"
 #include "bh_neighbours.hpp"
+#include "bh_neighbour_lists.hpp"
 #include "bh_pairs.hpp"
 #include "bh_groups.hpp"
 #include "bh_mst.hpp"
@@ -173,6 +174,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     FofState fof;
     MstState mst;
     BinState bin;
+    NblState nbl;
     // the quiet scope's device-side copies (quietly), allocated on first use; perm_save: the last force walk's permutation
     double *slots_save = nullptr;
     TreeCounters *ctr_save = nullptr;
@@ -1001,6 +1003,8 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_CHAIN_COLLAPSE")) c->chain_collapse = std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_RADIAL_BLOCKS")) { const int b = std::atoi(e); if (b >= 1 && b <= 65536) c->rad.blocks = b; }
+    if (const char *e = std::getenv("BH_LISTS_ENTRIES")) { const long long b = std::atoll(e); if (b >= 1) c->nbl.budget = b; }
+    if (const char *e = std::getenv("BH_LISTS_SORT_LDS")) { const int b = std::atoi(e); if (b >= 2 && b <= kNblMaxLds) c->nbl.sort_lds = b; }
     auto bail = [&](int rc) { g_create_error = c->err; bh_destroy(c); return rc; };
 
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(BH_ERR_DEVICE); }
@@ -1106,7 +1110,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
-    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev); destroy(c->bin.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev); destroy(c->bin.ev); destroy(c->nbl.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

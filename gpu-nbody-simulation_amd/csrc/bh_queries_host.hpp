@@ -1,8 +1,8 @@
 // bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, the field
-// at points, neighbour queries, pair counts, friends-of-friends groups, spanning trees and bound pairs, with their entry points
+// at points, neighbour queries and lists, pair counts, friends-of-friends groups, spanning trees and bound pairs, with their entry points
 // of include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
 // (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp,
-// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
+// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_neighbour_lists.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
 // bh_queries_state.hpp,
 // the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes first.
 #pragma once
@@ -603,6 +603,31 @@ int bin_alloc(bh_ctx *c, int64_t n)
                                           part(&s.rec, room * kBinRecord), part(&s.partner, b), part(&s.ctr, 1), part(&s.psort, b),
                                           part(&s.rec_lo, room), part(&s.rec_hi, room)});
 }
+
+// ---- neighbour lists (bh_neighbour_lists.hpp) on the structure of the neighbour queries.  As those: they read pos (and orig) as
+// they lie in memory and write buffers of their own, so a step before and after runs bit for bit as it would have.
+int nbl_alloc(bh_ctx *c, int64_t rows, int64_t entries, bool merge)
+{
+    NblState &s = c->nbl;
+    if (rows > s.block.cap) {
+        const int64_t cap = grown_capacity(rows);
+        const size_t q = (size_t)cap;
+        if (int rc = block_regrow(c, s.block, cap, {part(&s.counts, q), part(&s.evals, q), part(&s.rows_lds, q), part(&s.rows_merge, q),
+                                                    part(&s.cursors, q), part(&s.rad2, q),
+                                                    part(&s.tiles, (size_t)blocks_for(cap, kNblScanTile) + 1), part(&s.ctr, 1)}))
+            return rc;
+    }
+    if (entries > s.eblock.cap) {
+        if (int rc = block_regrow(c, s.eblock, entries, {part(&s.ent_d2, (size_t)entries), part(&s.ent_idx, (size_t)entries)})) return rc;
+    }
+    if (merge && s.eblock.cap > s.ablock.cap) {
+        const size_t e = (size_t)s.eblock.cap;
+        if (int rc = block_regrow(c, s.ablock, s.eblock.cap, {part(&s.alt_d2, e), part(&s.alt_idx, e)})) return rc;
+    }
+    return BH_OK;
+}
+
+int32_t pow2_at_least(int64_t v) { int32_t t = 2; while (t < v) t <<= 1; return t; }
 
 }  // namespace
 
@@ -1273,6 +1298,197 @@ int bh_binaries_times(bh_ctx *c, double *build_ms, double *search_ms, double *ca
     *build_ms = c->bin.build_ms;
     *search_ms = c->bin.search_ms;
     *catalogue_ms = c->bin.cat_ms;
+    return BH_OK;
+}
+
+int bh_neighbour_lists(bh_ctx *c, const double *points, int64_t n_points, const double *radii, int64_t n_radii, int64_t max_entries,
+                       int64_t *offsets, int64_t *idx, double *d2, int64_t *n_entries, uint64_t *stats)
+{
+    if (!c) return BH_ERR_ARG;
+    const std::string w("bh_neighbour_lists");
+    if (!offsets || !n_entries || !radii) return fail(c, BH_ERR_ARG, w + ": null offsets, n_entries or radii");
+    if (n_points < 0) return fail(c, BH_ERR_ARG, w + ": n_points < 0");
+    if (n_radii != 1 && n_radii != n_points) return fail(c, BH_ERR_ARG, w + ": n_radii must be 1 or n_points");
+    if ((idx == nullptr) != (d2 == nullptr)) return fail(c, BH_ERR_ARG, w + ": idx and d2 come together or not at all");
+    if (max_entries < 0) return fail(c, BH_ERR_ARG, w + ": max_entries < 0");
+    for (int64_t i = 0; i < n_radii; ++i)
+        if (!(radii[i] >= 0.0) || !std::isfinite(radii[i]))
+            return fail(c, BH_ERR_ARG, w + ": radius " + std::to_string(i) + " must be finite and >= 0");
+    if (int rc = diag_check(c, "bh_neighbour_lists")) return rc;
+    const int64_t n = c->n;
+    if (!points && n_points != n) return fail(c, BH_ERR_ARG, w + ": without points, n_points must be the number of bodies");
+    if (int rc = points_finite(c, "bh_neighbour_lists", points, n_points)) return rc;
+    NbState &nb = c->nb;
+    NblState &s = c->nbl;
+    std::fill(offsets, offsets + n_points + 1, (int64_t)0);
+    *n_entries = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    s.build_ms = s.count_ms = s.fill_ms = s.sort_ms = 0.0;
+    s.evals_host.assign((size_t)n_points, 0u);
+    if (n_points == 0) return BH_OK;
+    if (n > kNbMaxBodies) return fail(c, BH_ERR_CAPACITY, w + ": more than 2^24 bodies (their indices share a key word)");
+    if (n == 0) return BH_OK;                                  // no bodies: every row is empty
+
+    // the squared radii, each product formed once in fp64
+    const bool each = n_radii != 1;                            // (one query with its one radius: the same thing)
+    const double r2_all = radii[0] * radii[0];
+    std::vector<double> r2host(each ? (size_t)n_points : 0);
+    for (size_t i = 0; i < r2host.size(); ++i) r2host[i] = radii[i] * radii[i];
+
+    BH_HIP(c, hipSetDevice(c->device));
+    const int64_t rows_max = std::min(n_points, kNbChunk);
+    if (int rc = nb_alloc(c, n, points ? rows_max : 0, 0)) return rc;
+    if (int rc = nbl_alloc(c, (each && !points) ? std::max(rows_max, n) : rows_max, 0, false)) return rc;
+    int levels = 0;
+    if (int rc = nb_build(c, "bh_neighbour_lists", &levels)) return rc;
+    hipStream_t st = c->stream;
+    const int32_t n32 = (int32_t)n;
+    const bool many = n_points > kNbChunk;                     // more than one chunk: a chunk's order and counts are made again to fill it
+
+    // ---- the count pass: row lengths in launch order, and where every launch row belongs
+    std::vector<uint32_t> hcount((size_t)n_points), hdest((size_t)n_points);
+    if (!points) BH_HIP(c, hipMemcpyAsync(hdest.data(), nb.sidx, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (each && !points) BH_HIP(c, hipMemcpyAsync(s.rad2, r2host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    const double *rad2 = each ? s.rad2 : nullptr;
+    auto chunk_radii = [&](int64_t t0, int64_t rows) -> int {
+        if (!each || !points) return BH_OK;
+        BH_HIP(c, hipMemcpyAsync(s.rad2, r2host.data() + t0, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, st));
+        return BH_OK;
+    };
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        if (int rc = chunk_radii(t0, rows)) return rc;
+        auto search = [&](auto pts) {
+            hipLaunchKernelGGL((nbl_count_kernel<decltype(pts)::value>), dim3(blocks_for(rows, kBlock)), dim3(kBlock), 0, st, nb.spos, nb.sidx,
+                               nb.boxes, nb.off, levels, n32, nb.points, nb.order, t0, rows, rad2, r2_all, s.counts);
+        };
+        if (int rc = nb_launch(c, points ? points + 2 * t0 : nullptr, rows, [&] { dispatch(search, points != nullptr); })) return rc;
+        BH_HIP(c, hipMemcpyAsync(hcount.data() + t0, s.counts, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (points) BH_HIP(c, hipMemcpyAsync(hdest.data() + t0, nb.order, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BH_HIP(c, hipStreamSynchronize(st));
+        if (int rc = span_ms(c, nb.ev[2], nb.ev[3], &s.count_ms, true)) return rc;
+        if (points) for (int64_t r = 0; r < rows; ++r) hdest[(size_t)(t0 + r)] += (uint32_t)t0;
+    }
+    if (int rc = span_ms(c, nb.ev[0], nb.ev[1], &s.build_ms)) return rc;
+    int64_t longest = 0;
+    for (int64_t g = 0; g < n_points; ++g) {
+        offsets[(int64_t)hdest[(size_t)g] + 1] = (int64_t)hcount[(size_t)g];
+        longest = std::max<int64_t>(longest, hcount[(size_t)g]);
+    }
+    for (int64_t r = 0; r < n_points; ++r) offsets[r + 1] += offsets[r];
+    const int64_t total = offsets[n_points];
+    *n_entries = total;
+    if (stats) { stats[2] = (uint64_t)total; stats[3] = (uint64_t)longest; }
+    if (!idx) return BH_OK;
+    if (total > max_entries)
+        return fail(c, BH_ERR_CAPACITY, w + ": the lists hold " + std::to_string(total) + " entries, max_entries is " + std::to_string(max_entries));
+
+    // ---- the fill pass, launch by launch: consecutive rows whose lengths sum to at most the budget (at least the longest row)
+    const int64_t budget = std::max(s.budget, longest), room = std::max<int64_t>(std::min(budget, total), 1);
+    const int64_t lds_most = std::max<int64_t>(s.sort_lds, kNblSmall);
+    if (int rc = nbl_alloc(c, 0, room, longest > lds_most)) return rc;
+    std::vector<unsigned long long> hd2((size_t)room);
+    std::vector<uint32_t> hidx((size_t)room), hev((size_t)rows_max), rows_lds[3], rows_merge;
+    // (rows_lds: the in-LDS tier by length, up to 128, up to 256, longer: a network of T entries keeps T / 2 threads busy, so short
+    // rows get workgroups of one or two waves)
+    BH_HIP(c, hipMemsetAsync(s.ctr, 0, sizeof(NblCounters), st));
+    for (int64_t t0 = 0; t0 < n_points; t0 += kNbChunk) {
+        const int64_t rows = std::min(kNbChunk, n_points - t0);
+        if (many) {
+            if (int rc = chunk_radii(t0, rows)) return rc;
+            if (points) { if (int rc = sorted_query_chunk(c, points + 2 * t0, rows, nb.points, nb.box, nb.pkeys, nb.order, nb.radix, nb.rowsum)) return rc; }
+            BH_HIP(c, hipMemcpyAsync(s.counts, hcount.data() + t0, (size_t)rows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
+        for (int64_t a = 0, b = 0; a < rows; a = b) {
+            int64_t sum = 0, small_most = 1, lds_len[3] = {0, 0, 0};
+            for (auto &v : rows_lds) v.clear();
+            rows_merge.clear();
+            for (b = a; b < rows && sum + (int64_t)hcount[(size_t)(t0 + b)] <= budget; ++b) {
+                const int64_t len = (int64_t)hcount[(size_t)(t0 + b)];
+                sum += len;
+                if (len <= kNblSmall) small_most = std::max(small_most, len);
+                else if (len <= lds_most) {
+                    const int g = len <= 2 * kWave ? 0 : len <= 4 * kWave ? 1 : 2;
+                    rows_lds[g].push_back((uint32_t)(b - a));
+                    lds_len[g] = std::max(lds_len[g], len);
+                }
+                else rows_merge.push_back((uint32_t)(b - a));
+            }
+            const int64_t nq = b - a;
+            const unsigned nt = blocks_for(nq, kNblScanTile);
+            if (int rc = mark(c, s.ev[0])) return rc;
+            hipLaunchKernelGGL(nbl_scan_totals_kernel, dim3(nt), dim3(kBlock), 0, st, s.counts + a, nq, s.tiles);
+            hipLaunchKernelGGL(nbl_scan_bases_kernel, dim3(1), dim3(kBlock), 0, st, s.tiles, (int32_t)nt);
+            hipLaunchKernelGGL(nbl_scan_apply_kernel, dim3(nt), dim3(kBlock), 0, st, s.counts + a, nq, s.tiles, s.cursors);
+            dispatch([&](auto pts) {
+                hipLaunchKernelGGL((nbl_fill_kernel<decltype(pts)::value>), dim3(blocks_for(nq, kWave)), dim3(kWave),
+                                   (size_t)small_most * kWave * 12, st, nb.spos, nb.sidx, nb.boxes, nb.off, levels, n32, (int32_t)small_most,
+                                   nb.points, nb.order + (points ? a : 0), t0 + a, nq, rad2, r2_all, s.counts + a, s.cursors, s.ent_d2, s.ent_idx,
+                                   s.evals, s.ctr);
+            }, points != nullptr);
+            BH_HIP(c, hipGetLastError());
+            if (int rc = mark(c, s.ev[1])) return rc;
+            size_t at = 0;
+            for (int g = 0; g < 3; ++g) {
+                if (rows_lds[g].empty()) continue;
+                const int32_t T = pow2_at_least(lds_len[g]);
+                BH_HIP(c, hipMemcpyAsync(s.rows_lds + at, rows_lds[g].data(), rows_lds[g].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL((nbl_sort_kernel<false>), dim3((unsigned)rows_lds[g].size()), dim3(std::min(kBlock, std::max(kWave, T / 2))),
+                                   (size_t)T * 12, st, s.rows_lds + at, s.counts + a, s.cursors, T, s.ent_d2, s.ent_idx, s.alt_d2, s.alt_idx);
+                at += rows_lds[g].size();
+            }
+            if (!rows_merge.empty()) {
+                const int32_t T = pow2_at_least(s.sort_lds);
+                BH_HIP(c, hipMemcpyAsync(s.rows_merge, rows_merge.data(), rows_merge.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL((nbl_sort_kernel<true>), dim3((unsigned)rows_merge.size()), dim3(kBlock), (size_t)T * 12, st, s.rows_merge,
+                                   s.counts + a, s.cursors, T, s.ent_d2, s.ent_idx, s.alt_d2, s.alt_idx);
+            }
+            BH_HIP(c, hipGetLastError());
+            if (int rc = mark(c, s.ev[2])) return rc;
+            if (sum > 0) {
+                BH_HIP(c, hipMemcpyAsync(hd2.data(), s.ent_d2, (size_t)sum * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+                BH_HIP(c, hipMemcpyAsync(hidx.data(), s.ent_idx, (size_t)sum * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            }
+            BH_HIP(c, hipMemcpyAsync(hev.data(), s.evals, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            BH_HIP(c, hipStreamSynchronize(st));                // (the row lists live in this scope; the next launch reuses the entries)
+            if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.fill_ms, true)) return rc;
+            if (int rc = span_ms(c, s.ev[1], s.ev[2], &s.sort_ms, true)) return rc;
+            int64_t from = 0;                                  // (the device's cursors are this prefix)
+            for (int64_t r = a; r < b; ++r) {
+                const int64_t at = (int64_t)hdest[(size_t)(t0 + r)], len = (int64_t)hcount[(size_t)(t0 + r)];
+                std::memcpy(d2 + offsets[at], hd2.data() + from, (size_t)len * sizeof(double));
+                for (int64_t e = 0; e < len; ++e) idx[offsets[at] + e] = (int64_t)hidx[(size_t)(from + e)];
+                s.evals_host[(size_t)at] = hev[(size_t)(r - a)];
+                from += len;
+            }
+        }
+    }
+    NblCounters ctr{};
+    BH_HIP(c, hipMemcpyAsync(&ctr, s.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    BH_HIP(c, hipStreamSynchronize(st));
+    if (ctr.refused || ctr.cut)
+        return fail(c, BH_ERR_DEVICE, w + ": the fill pass disagrees with the count pass: " + std::to_string(ctr.refused) +
+                                      " stores past a row's end were refused, " + std::to_string(ctr.cut) + " rows ended short");
+    if (stats) { stats[0] = ctr.evals; stats[1] = ctr.opened; }
+    return BH_OK;
+}
+
+int bh_neighbour_lists_times(bh_ctx *c, double *build_ms, double *count_ms, double *fill_ms, double *sort_ms)
+{
+    if (!c || !build_ms || !count_ms || !fill_ms || !sort_ms) return fail(c, BH_ERR_ARG, "bh_neighbour_lists_times: null argument");
+    *build_ms = c->nbl.build_ms;
+    *count_ms = c->nbl.count_ms;
+    *fill_ms = c->nbl.fill_ms;
+    *sort_ms = c->nbl.sort_ms;
+    return BH_OK;
+}
+
+int bh_neighbour_lists_evals(bh_ctx *c, int64_t n_points, uint32_t *evals)
+{
+    if (!c || !evals) return fail(c, BH_ERR_ARG, "bh_neighbour_lists_evals: null argument");
+    if (n_points != (int64_t)c->nbl.evals_host.size())
+        return fail(c, BH_ERR_ARG, "bh_neighbour_lists_evals: the last bh_neighbour_lists call had " + std::to_string(c->nbl.evals_host.size()) + " queries");
+    std::copy(c->nbl.evals_host.begin(), c->nbl.evals_host.end(), evals);
     return BH_OK;
 }
 

@@ -118,4 +118,22 @@ struct BinState {
     std::vector<double> cat_rec;                                // kBinRecord doubles a record
 };
 
+// neighbour lists (bh_neighbour_lists.hpp) beside the neighbour structure's blocks: one block for a launch of up to block.cap
+// queries (row lengths, cursors, evals, the per-query r2, the rows of the two sort kernels, the scan's tile totals), one for
+// up to eblock.cap entries, and a second of that size once a row is sorted through global memory
+struct NblState {
+    DevBlock block, eblock, ablock;
+    uint32_t *counts = nullptr, *evals = nullptr, *rows_lds = nullptr, *rows_merge = nullptr, *ent_idx = nullptr, *alt_idx = nullptr;
+    int64_t *cursors = nullptr;
+    double *rad2 = nullptr;
+    uint64_t *tiles = nullptr;
+    unsigned long long *ent_d2 = nullptr, *alt_d2 = nullptr;
+    NblCounters *ctr = nullptr;
+    int64_t budget = (int64_t)1 << 24;  // BH_LISTS_ENTRIES: most entries of a launch
+    int sort_lds = 512;                 // BH_LISTS_SORT_LDS: the longest row the in-LDS sort takes
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};             // around a launch's scan and fill, and after its sorts
+    double build_ms = 0.0, count_ms = 0.0, fill_ms = 0.0, sort_ms = 0.0;       // of the last call (bh_neighbour_lists_times)
+    std::vector<uint32_t> evals_host;                           // per query, caller order: of the last filling call
+};
+
 }  // namespace bh

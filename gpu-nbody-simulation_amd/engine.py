@@ -443,6 +443,64 @@ def binaries_from_records(partner, eps, lo, hi, records, max_separation: float, 
                       rec[:, 6].copy(), rec[:, 7:9].copy(), rec[:, 9:11].copy(), stats, mean_kinetic)
 
 
+@dataclass
+class BhNeighbourLists:
+    """Fixed-radius neighbour lists (neighbours_within): row r holds the bodies with d2 <= radius_r * radius_r of query r --
+    a body (itself left out by index) or a point (nobody left out) --, ascending in (d2, caller index), with
+    d2 = dx * dx + dy * dy in fp64.  Row r is idx[offsets[r]:offsets[r + 1]] with the matching d2."""
+    offsets: np.ndarray          # (q + 1,) int64: the exclusive prefix of the row lengths
+    idx: np.ndarray              # (entries,) int64: caller indices
+    d2: np.ndarray               # (entries,) float64
+    radius: np.ndarray           # () or (q,) float64: as it was asked
+    body_queries: bool           # the queries are the bodies themselves
+    stats: tuple | None = None   # with_stats=True: (distances the fill pass computed, nodes it opened, entries, longest row)
+    evals: np.ndarray | None = None   # with_stats=True: (q,) uint32, the distances the fill pass computed per query
+
+    @property
+    def counts(self) -> np.ndarray:
+        """(q,) int64: the row lengths"""
+        return np.diff(self.offsets)
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def row(self, r: int):
+        """(idx, d2) of row r, as views"""
+        a, b = int(self.offsets[r]), int(self.offsets[r + 1])
+        return self.idx[a:b], self.d2[a:b]
+
+    def nearest(self):
+        """(idx (q,) int64, d2 (q,)): the first entry of every row; -1 / inf for an empty row"""
+        q = len(self)
+        idx, d2 = np.full(q, -1, dtype=np.int64), np.full(q, np.inf)
+        have = self.counts > 0
+        idx[have], d2[have] = self.idx[self.offsets[:-1][have]], self.d2[self.offsets[:-1][have]]
+        return idx, d2
+
+    def pairs(self):
+        """(lo, hi, d2): every unordered pair of bodies within the radius once, lo < hi, ascending in (lo, hi).  For body
+        queries with one radius only: with per-query radii the relation is one-sided, and a point is nobody's partner."""
+        if not self.body_queries or np.ndim(self.radius) != 0:
+            raise ValueError("pairs() needs body queries and one radius: otherwise the relation is one-sided")
+        lo = np.repeat(np.arange(len(self), dtype=np.int64), self.counts)
+        keep = lo < self.idx
+        lo, hi, d2 = lo[keep], self.idx[keep], self.d2[keep]
+        order = np.lexsort((hi, lo))
+        return lo[order], hi[order], d2[order]
+
+
+def neighbour_lists_from(offsets, idx, d2, radius, body_queries: bool, stats=None, evals=None) -> BhNeighbourLists:
+    """BhNeighbourLists of the arrays of bh_neighbour_lists (or of a twin's)."""
+    radius = np.asarray(radius, dtype=np.float64)
+    if radius.ndim > 1:
+        raise ValueError("radius is a scalar or an array of shape (q,)")
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    idx, d2 = np.asarray(idx, dtype=np.int64).reshape(-1), np.asarray(d2, dtype=np.float64).reshape(-1)
+    if len(offsets) < 1 or len(idx) != offsets[-1] or len(d2) != offsets[-1] or (radius.ndim == 1 and len(radius) != len(offsets) - 1):
+        raise ValueError("offsets, idx, d2 and radius do not belong together")
+    return BhNeighbourLists(offsets, idx, d2, radius, bool(body_queries), stats, evals)
+
+
 MST_SUBSET_MAX = 512                    # BH_MST_SUBSET_MAX
 
 
@@ -1079,6 +1137,42 @@ class BarnesHutEngine:
         b, q = C.c_double(), C.c_double()
         self._check(self._lib.bh_neighbours_times(self._h, C.byref(b), C.byref(q)))
         return b.value, q.value
+
+    # -- neighbour lists ------------------------------------------------------------------------
+    def neighbours_within(self, radius, points=None, max_entries=None, with_stats: bool = False) -> BhNeighbourLists:
+        """Every body within `radius` (a scalar, or one radius per query, shape (q,)) of every body (points None; itself left
+        out by index) or of the coordinates `points` (q, 2): see BhNeighbourLists.  Two calls: one that counts (about the cost
+        of a count_within), then, with the arrays allocated, one that fills.  More than max_entries entries in all (None: no
+        limit) raise BhError with BH_ERR_CAPACITY, and the message carries the number needed.  Reads the state only; the run is
+        not perturbed."""
+        p, q, pp = self._query_points(points)
+        rad = np.asarray(radius, dtype=np.float64)
+        if rad.ndim > 1:
+            raise ValueError("radius is a scalar or an array of shape (q,)")
+        flat = np.ascontiguousarray(rad).reshape(-1)
+        i64 = C.POINTER(C.c_int64)
+        off = np.zeros(q + 1, dtype=np.int64)
+        total = C.c_int64()
+        rp = _dptr(flat) if len(flat) else (C.c_double * 1)()
+        call = self._lib.bh_neighbour_lists
+        self._check(call(self._h, pp, q, rp, len(flat), 0, off.ctypes.data_as(i64), None, None, C.byref(total), None))
+        room = total.value if max_entries is None else int(max_entries)
+        idx, d2 = np.zeros(max(room, 1), dtype=np.int64), np.zeros(max(room, 1))
+        st = (C.c_uint64 * 4)()
+        self._check(call(self._h, pp, q, rp, len(flat), room, off.ctypes.data_as(i64), idx.ctypes.data_as(i64), _dptr(d2), C.byref(total), st))
+        ev = None
+        if with_stats:
+            ev = np.zeros(max(q, 1), dtype=np.uint32)
+            self._check(self._lib.bh_neighbour_lists_evals(self._h, q, ev.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return neighbour_lists_from(off, idx[:total.value], d2[:total.value], rad, points is None,
+                                    tuple(int(v) for v in st) if with_stats else None, ev[:q] if with_stats else None)
+
+    def neighbour_lists_times(self):
+        """(build_ms, count_ms, fill_ms, sort_ms) of the last bh_neighbour_lists call (neighbours_within makes two; this is the
+        filling one): HIP events around the index's build, the count pass, scan and fill, and the row sorts."""
+        t = [C.c_double() for _ in range(4)]
+        self._check(self._lib.bh_neighbour_lists_times(self._h, *[C.byref(v) for v in t]))
+        return tuple(v.value for v in t)
 
     # -- pair counts ----------------------------------------------------------------------------
     def pair_counts_raw(self, edges, points=None):

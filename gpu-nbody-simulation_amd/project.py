@@ -85,7 +85,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      pairs_file: str | None = None, pairs_bins: int | None = None, pairs_range=None, pairs_spacing: str = "log",
                      pairs_randoms: int | None = None, pairs_seed: int = 0, mst_file: str | None = None,
                      segregation_file: str | None = None, segregation_massive: int | None = None, segregation_random: int = 500,
-                     segregation_seed: int = 0, binaries_file: str | None = None, binaries_separation: float | None = None):
+                     segregation_seed: int = 0, binaries_file: str | None = None, binaries_separation: float | None = None,
+                     encounters_file: str | None = None, encounters_radius: float | None = None):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -139,6 +140,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     (%.17g), ascending in i: the two body indices, their separation, the semi-major axis, the eccentricity, the period and the
     binding energy -- Keplerian, whatever the softening, of the state as it is (with integrator "kdk" velocities and positions
     are at the same time).  Not part of gpu_parallel_duration_us.
+    encounters_file: after the last step, also write the close pairs of the final state
+    (BarnesHutEngine.neighbours_within(encounters_radius).pairs()): the line `# i,j,r`, then one row per pair of bodies no
+    farther apart than encounters_radius (%.17g), i < j, ascending in (i, j): the two body indices and their separation
+    sqrt(d2).  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -150,6 +155,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("segregation_file and segregation_massive go together")
     if (binaries_file is None) != (binaries_separation is None):
         raise ValueError("binaries_file and binaries_separation go together")
+    if (encounters_file is None) != (encounters_radius is None):
+        raise ValueError("encounters_file and encounters_radius go together")
     if integrator not in ("euler", "kdk"):
         raise ValueError("integrator must be 'euler' or 'kdk'")
     if (profile_file is None) != (profile_bins is None):
@@ -319,6 +326,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 f.write("# i,j,r,a,e,period,binding_energy\n")
                 f.write("".join("%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(b.lo, b.hi, b.separation, b.semi_major_axis,
                                                                                     b.eccentricity, b.period, b.binding_energy)))
+        if encounters_file is not None:
+            lo, hi, d2 = eng.neighbours_within(encounters_radius).pairs()
+            with open(os.path.join(out_dir, encounters_file) if not os.path.isabs(encounters_file) else encounters_file, "w") as f:
+                f.write("# i,j,r\n")
+                f.write("".join("%d,%d,%.17g\n" % r for r in zip(lo, hi, np.sqrt(d2))))
         if traj is not None:
             traj.close()
         for f in (energy, ferr, lagrange):
@@ -473,6 +485,10 @@ def _parse(argv):
                          "(needs --binaries-separation)")
     ap.add_argument("--binaries-separation", type=float, default=None, metavar="R",
                     help="largest separation of a pair's two bodies (> 0; inf: no cut)")
+    ap.add_argument("--encounters-file", default=None, metavar="PATH",
+                    help="after the last step, also write i,j,r of every pair of bodies of the final state no farther apart than "
+                         "--encounters-radius")
+    ap.add_argument("--encounters-radius", type=float, default=None, metavar="R", help="largest separation of a close pair (>= 0)")
     ap.add_argument("--save-init", action="store_true", help="write the three init files after initialisation")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
@@ -544,6 +560,10 @@ def _parse(argv):
         ap.error("--binaries-file and --binaries-separation go together")
     if a.binaries_separation is not None and not a.binaries_separation > 0.0:
         ap.error("--binaries-separation: > 0")
+    if (a.encounters_file is None) != (a.encounters_radius is None):
+        ap.error("--encounters-file and --encounters-radius go together")
+    if a.encounters_radius is not None and not (0.0 <= a.encounters_radius < math.inf):
+        ap.error("--encounters-radius: finite and >= 0")
     a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     if a.groups_min is not None and a.groups_min < 1:
@@ -622,7 +642,8 @@ def main(argv=None) -> int:
         pairs_range=a.pairs_range, pairs_spacing=a.pairs_spacing or "log", pairs_randoms=a.pairs_randoms,
         pairs_seed=a.pairs_seed or 0, mst_file=a.mst_file, segregation_file=a.segregation_file,
         segregation_massive=a.segregation_massive, segregation_random=500 if a.segregation_random is None else a.segregation_random,
-        segregation_seed=a.segregation_seed or 0, binaries_file=a.binaries_file, binaries_separation=a.binaries_separation)
+        segregation_seed=a.segregation_seed or 0, binaries_file=a.binaries_file, binaries_separation=a.binaries_separation,
+        encounters_file=a.encounters_file, encounters_radius=a.encounters_radius)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -529,6 +529,45 @@ int bh_neighbours(bh_ctx *ctx, const double *points, int64_t n_points, int32_t k
 int bh_count_within(bh_ctx *ctx, const double *points, int64_t n_points, double radius, uint32_t *counts);
 int bh_neighbours_times(bh_ctx *ctx, double *build_ms, double *query_ms);
 
+/* --- neighbour lists: WHICH bodies lie within a radius of a body or a point, every one of them ---------------------------------
+ * Queries, distance and self-exclusion: those of bh_count_within above.  points == NULL: the queries are the n bodies in caller
+ *   order, n_points must be n, and body i is left out of its own row by index only.  Otherwise points[n_points][2], nobody is
+ *   left out, and a point that lies on a body lists that body with d2 = 0.
+ * Row r holds the bodies j with d2 <= radius_r * radius_r (the product formed once in fp64 on the host; the edge inclusive),
+ *   ascending in the order (d2, caller index j).  radius_r is radii[0] when n_radii == 1, else radii[r]; every radius is finite
+ *   and >= 0.
+ * Outputs.  offsets[n_points + 1]: the exclusive prefix of the row lengths in caller order, offsets[n_points] = *n_entries.
+ *   Row r is idx[offsets[r] .. offsets[r + 1]) -- caller indices -- with the matching d2.  idx and d2 hold max_entries each.
+ * Count-only call: idx == NULL and d2 == NULL.  offsets and *n_entries are written and the call returns BH_OK whatever
+ *   max_entries is; it costs about a bh_count_within.
+ * Too little room: with idx and d2 given and *n_entries > max_entries the call returns BH_ERR_CAPACITY; offsets and *n_entries
+ *   are still written (the message carries the number too) and nothing is written to idx or d2.
+ * A row depends on its own query only -- not on the other queries of the call, their order or their number -- and equals the
+ *   brute-force definition bit for bit in all four precisions (an fp32 state is widened first, exactly).
+ * stats (may be NULL): {distances computed by the fill pass, nodes opened by it (summed over the queries), entries, longest
+ *   row} -- deterministic for a given state and call, a measure of the work and no part of the answer.  A count-only or refused
+ *   call leaves the first two 0.  bh_neighbour_lists_evals: the distances the fill pass of the last call computed, per query.
+ * How.  Two traversals of the neighbours' search structure: one counts (taking whole nodes where it can), the row lengths are
+ *   scanned to write cursors on the device, one fills; rows are sorted on the device.  The entries of a launch are bounded by
+ *   BH_LISTS_ENTRIES (environment, read at bh_create; at least the longest row), BH_LISTS_SORT_LDS is the longest row sorted in
+ *   LDS alone.  Should the two traversals ever disagree, the call fails with BH_ERR_DEVICE and says how; it never writes past a row.
+ * bh_neighbour_lists_times: HIP-event times of the last call: the structure's build, the count pass (a point launch's own sort
+ *   included), scan and fill, and the row sorts; downloads excluded.
+ * It reads the state only: no force tree is built, nothing a step, bh_stats or another diagnostic reads is touched, and a
+ * following bh_step is bit for bit what it would have been.  It waits for the stream.  Its buffers only grow; bh_destroy frees them.
+ * Errors: BH_ERR_ARG for a negative or non-finite radius (checked before anything is enqueued), n_radii not 1 or n_points,
+ *   n_points < 0, null offsets, n_entries or radii, exactly one of idx and d2 null, max_entries < 0, points == NULL with
+ *   n_points != n, a non-finite point, and -- found by the bounds pass, with a message that says so -- a non-finite body
+ *   position.  BH_ERR_CAPACITY for more than 2^24 bodies.  BH_ERR_STATE before any upload, in LET mode and with world > 1.
+ *   n_points = 0 gives offsets[0] = 0 and *n_entries = 0; without bodies every row is empty. */
+int bh_neighbour_lists(bh_ctx *ctx, const double *points, int64_t n_points,
+                       const double *radii, int64_t n_radii,          /* 1, or n_points */
+                       int64_t max_entries, int64_t *offsets /* n_points + 1 */,
+                       int64_t *idx, double *d2,                      /* max_entries each, or both NULL */
+                       int64_t *n_entries, uint64_t stats[4]);
+int bh_neighbour_lists_times(bh_ctx *ctx, double *build_ms, double *count_ms, double *fill_ms, double *sort_ms);
+int bh_neighbour_lists_evals(bh_ctx *ctx, int64_t n_points, uint32_t *evals);
+
 /* --- pair counts: how many pairs lie at each separation (DD(r), the raw material of the two-point correlation) ----------------
  * Distance.  For a body j and a query q of the CURRENT state: dx = x_j - q.x; dy = y_j - q.y; d2 = dx * dx + dy * dy, in fp64
  *   with nothing fused, in every precision (an fp32 state is widened first, exactly): the d2 of bh_count_within.  It is
