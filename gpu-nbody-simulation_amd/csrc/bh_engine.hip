@@ -1207,6 +1207,13 @@ int bh_initialize(bh_ctx *c, int64_t n, uint64_t seed, int32_t kind, double lowe
     if (n < 0 || n > c->cfg.capacity)
         return fail(c, BH_ERR_ARG, "Requested number of bodies exceeds N_BODIES.");
     if (kind != 0 && kind != 1) return fail(c, BH_ERR_ARG, "bh_initialize: kind must be 0 (box) or 1 (plummer)");
+    if (kind == 1) {               // kind 0 stays as permissive as generateRandomGpu; a Plummer sphere of these is NaN or garbage
+        if (!(std::isfinite(lower_p) && lower_p > 0))
+            return fail(c, BH_ERR_ARG, "bh_initialize: plummer scale lower_p must be finite and > 0");
+        if (!(higher_p > 0))       // +inf: untruncated
+            return fail(c, BH_ERR_ARG, "bh_initialize: plummer truncation radius higher_p must be > 0 (+inf: none)");
+        if (!std::isfinite(higher_m)) return fail(c, BH_ERR_ARG, "bh_initialize: plummer mass higher_m must be finite");
+    }
     BH_HIP(c, hipSetDevice(c->device));
     if (n > 0) {
         const unsigned g = blocks_for(n, kBlock);

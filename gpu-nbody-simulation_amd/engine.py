@@ -799,7 +799,12 @@ class BarnesHutEngine:
                    lower_p=-1e-1, higher_p=1e-1, lower_v=-1e-4, higher_v=1e-4) -> None:
         """On-device initial conditions (initializeGpu, project.cu:304-341; defaults = its
         constants, project.cu:30-35).  kind "plummer": scale lower_p, truncation higher_p, equal
-        masses higher_m, zero velocities."""
+        masses higher_m, zero velocities.  Body i is a function of (seed, i) alone.
+
+        The Plummer radius is drawn again while it lies beyond higher_p, up to 64 draws; after that the last
+        one stands, with probability (1 - M(higher_p))^64 per body, M(r) = r^3 / (r^2 + a^2)^(3/2): below 1e-12
+        for higher_p >= a, about 0.2 at higher_p = 0.3 a.  BhError -1 unless lower_p is finite and > 0, higher_p
+        is > 0 (inf: untruncated) and higher_m is finite."""
         k = {"box": 0, "plummer": 1}[kind]
         self._check(self._lib.bh_initialize(self._h, n, seed, k, lower_m, higher_m, lower_p, higher_p,
                                             lower_v, higher_v))

@@ -207,6 +207,18 @@ int bh_download(bh_ctx *ctx, double *pos, double *vel);
  * [lower_v, higher_v]^2, each range log-uniform when both bounds are positive and linear otherwise
  * (generateRandomGpu, project.cu:84-97).  kind 1 = projected Plummer sphere (BASELINE config 3):
  * scale lower_p, truncation radius higher_p, equal masses higher_m, zero velocities.
+ *
+ * The generator is Philox-4x32-10 with the counter [i_lo, i_hi, stream, 0x9E3779B9] and the key [seed_lo, seed_hi]: body i is
+ * a function of (seed, i) alone -- not of n, the capacity or the launch.  kind 0 takes the mass and x from stream 0, y and vx
+ * from stream 1, vy from stream 2 (53 bits each); a linear range is u * (upper - lower) + lower in two roundings.
+ *
+ * kind 1, the rejection rule: the THREE-dimensional radius is drawn by inverting M(r) = r^3 / (r^2 + a^2)^(3/2) and drawn
+ * again, from stream 16 + t for try t, while it lies beyond higher_p.  Up to 64 draws are made; AFTER THE 64TH THE LAST ONE
+ * STANDS, beyond higher_p though it is.  A body ends that way with probability (1 - M(higher_p))^64: below 1e-12 for
+ * higher_p >= a, about 0.2 at higher_p = 0.3 a.  (The truncation is of the sphere: the projected radius of every other
+ * body is <= higher_p, with the law 1 - a^2 / (R^2 + a^2) (1 - R^2 / higher_p^2)^(3/2).)
+ * kind 1 returns BH_ERR_ARG unless lower_p is finite and > 0, higher_p is > 0 (+inf: no truncation) and higher_m is finite;
+ * lower_m, lower_v and higher_v are ignored.  kind 0 takes any ranges, as the reference does.
  * bh_download_masses returns the masses (the caller supplied them in bh_upload otherwise). */
 int bh_initialize(bh_ctx *ctx, int64_t n, uint64_t seed, int32_t kind, double lower_m, double higher_m,
                   double lower_p, double higher_p, double lower_v, double higher_v);
