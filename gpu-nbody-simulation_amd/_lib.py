@@ -156,6 +156,7 @@ SIGNATURES = {
     "bh_stats": (C.c_int, [_ctx, C.POINTER(bh_stats_t)]),
     "bh_sort_snapshot": (C.c_int, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "bh_sort_paths": (C.c_int, [_ctx, C.POINTER(C.c_uint64)]),
     "bh_set_owned_fraction": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "bh_device_state": (C.c_int, [_ctx, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

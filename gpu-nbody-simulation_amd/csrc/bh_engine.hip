@@ -97,6 +97,8 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     uint32_t direct_cap = 0, direct_subcap = 0;
     int direct_nsub = 1;
     int direct_slot = 0;                  // the counter the next build counts into (zero by then)
+    bool sort_place = true;               // bucket_sort_kernel finishes a nearly ordered bucket by placement (BH_SORT_PLACE=0 disables, A/B)
+    uint32_t *sort_paths = nullptr;       // [2][kBucketsBig] per bucket number: times placed, times through the passes (bh_sort_paths)
     // what the last build's sort was given (bh_sort_snapshot): direct_slot has been flipped by the time anybody asks.
     // offered: direct input was offered, and `count` is the block that build counted into; the output is keys_sorted / perm
     struct SortRecord {
@@ -444,7 +446,8 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
         int cur = 0;
         if (single) {
             hipLaunchKernelGGL(bucket_sort_kernel, dim3(1), dim3(kBsThreads), 0, st, c->keys[0], c->keys[1], c->vals[1],
-                               nullptr, nullptr, &c->ctr->sort_spills, &c->ctr->sort_reruns, (int)n, BucketDirect{});
+                               nullptr, nullptr, &c->ctr->sort_spills, &c->ctr->sort_reruns, (int)n, BucketDirect{}, c->sort_paths,
+                               c->sort_place ? 1 : 0);
             cur = 1;
         } else if (bucket) {
             constexpr int SI = (ITEMS == kItems ? kSortItems : ITEMS);
@@ -470,12 +473,13 @@ int enqueue_build_t(bh_ctx *c, bool may_reorder, bool time_groups)
             if (nb == kBuckets) pass(std::integral_constant<int, 8>{}); else pass(std::integral_constant<int, 10>{});
             if (direct) {
                 hipLaunchKernelGGL(bucket_sort_kernel, dim3(nb), dim3(kBsThreads), 0, st, c->keys_scatter, c->keys[1], c->vals[1],
-                                   c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0, bd);
+                                   c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0, bd,
+                                   c->sort_paths, c->sort_place ? 1 : 0);
                 cur = 1;
             } else {
                 hipLaunchKernelGGL(bucket_sort_kernel, dim3(nb), dim3(kBsThreads), 0, st, c->keys[1], c->keys[0], c->vals[0],
                                    c->bsum_sort, c->bsum_sort + kBucketStartOffset, &c->ctr->sort_spills, &c->ctr->sort_reruns, 0,
-                                   BucketDirect{});
+                                   BucketDirect{}, c->sort_paths, c->sort_place ? 1 : 0);
                 cur = 0;
             }
         } else {
@@ -1002,6 +1006,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     c->hilbert = !c->tree64();
     if (const char *e = std::getenv("BH_HILBERT")) c->hilbert = !c->tree64() && std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_CHAIN_COLLAPSE")) c->chain_collapse = std::atoi(e) != 0;
+    if (const char *e = std::getenv("BH_SORT_PLACE")) c->sort_place = std::atoi(e) != 0;
     if (const char *e = std::getenv("BH_RADIAL_BLOCKS")) { const int b = std::atoi(e); if (b >= 1 && b <= 65536) c->rad.blocks = b; }
     if (const char *e = std::getenv("BH_LISTS_ENTRIES")) { const long long b = std::atoll(e); if (b >= 1) c->nbl.budget = b; }
     if (const char *e = std::getenv("BH_LISTS_SORT_LDS")) { const int b = std::atoi(e); if (b >= 2 && b <= kNblMaxLds) c->nbl.sort_lds = b; }
@@ -1048,6 +1053,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
       A(&c->bsum_sort, 2 * kBucketStartOffset);               // bucket totals, then bucket starts
       A(&c->splitters, kBucketsBig);
       A(&c->sort_dig, (size_t)std::min<int64_t>(cap, kBucketMaxNBig) + 16);
+      A(&c->sort_paths, 2 * kBucketsBig);
       if (c->sort_direct) {
           const int64_t most = std::min<int64_t>(cap, kBucketMaxNBig);        // (larger launches take the LSD passes)
           c->direct_cap = (uint32_t)std::min<int64_t>(most, c->sort_direct == 2 ? most : c->sort_direct_max);
@@ -1087,6 +1093,7 @@ int bh_create(const bh_config *cfg, bh_ctx **out)
     }
     if (rc) return bail(rc);
     if (hipMemset(c->ctr, 0, sizeof(TreeCounters)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
+    if (hipMemset(c->sort_paths, 0, 2 * kBucketsBig * sizeof(uint32_t)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
     if (c->direct_count && hipMemset(c->direct_count, 0, 2 * kDirectCounterWords * sizeof(uint32_t)) != hipSuccess) { c->err = "hipMemset failed"; return bail(BH_ERR_DEVICE); }
     if (!c->tree64()) {
         const void *wc[4] = {c->aux, c->spos, c->smass, nullptr};
@@ -1905,6 +1912,21 @@ int bh_stats(bh_ctx *c, bh_stats_t *out)
         out->build_bytes = (uint64_t)c->n * (keys_b + sort_b + prep_b + scan_b + nodes_b);
         out->walk_bytes = out->wave_nodes ? (uint64_t)c->n * 44u + out->wave_nodes * 20u : 0u;
     }
+    return BH_OK;
+}
+
+// How the in-LDS bucket sorts ended so far: out[0] buckets finished by placement, out[1] buckets that went through byte passes
+// (cumulative since bh_create; bh_sort.hpp "Placement").  The workgroup of bucket b counts in words of its own -- 256 atomics
+// on one word at the end of every bucket's chain cost the kernel 2.5 us --, summed here.  A wait and a copy, no launch.
+int bh_sort_paths(bh_ctx *c, uint64_t out[2])
+{
+    if (!c || !out) return fail(c, BH_ERR_ARG, "bh_sort_paths: null argument");
+    BH_HIP(c, hipSetDevice(c->device));
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> h((size_t)2 * kBucketsBig);
+    BH_HIP(c, hipMemcpy(h.data(), c->sort_paths, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    out[0] = out[1] = 0;
+    for (int b = 0; b < kBucketsBig; ++b) { out[0] += h[(size_t)b]; out[1] += h[(size_t)kBucketsBig + b]; }
     return BH_OK;
 }
 

@@ -507,43 +507,215 @@ __device__ __forceinline__ uint32_t bs_scan256(uint32_t v, uint32_t *sm, uint32_
 // the run.  A run longer than kFixRun (keys piled up on a few values below a wide span) sends the workgroup through
 // the full passes instead.  Either way the result is the stable order by key.
 constexpr int kFixRun = 8;
+//
+// Placement (a bucket that is in order but for a few keys; BH_SORT_PLACE=0 turns it off).  With direct input a bucket is a
+// range of an array that was sorted a few builds ago: bodies that overtook a neighbour along the curve since stand a place or
+// two from where they belong, everybody else stands right.  Such a bucket is finished without a byte pass:
+//   * an inversion is a pair j < i (input order) with K_j > K_i; the bucket is placeable with window W = kPlaceWindow iff no
+//     inversion has i - j > W.  Then the stable rank of key i is
+//         i - #{j in [i - W, i): K_j > K_i} + #{j in (i, i + W]: K_j < K_i},
+//     and every key is written straight to kout / vout at that rank, as the run fix-up writes;
+//   * the bucket's descents (K_i < K_{i-1}) are found on the way through the kmin / kmax reduction, each wave listing its own
+//     -- position, the key before ("peak"), the key itself ("valley") -- in its row of `match`.  More than
+//     kPlaceMaxDescents of them: straight to the passes, nothing else was done.  Otherwise every key is compared with the
+//     listed ones: the largest key before i is a peak before i or K_{i-1}, the smallest after i a valley after i or K_{i+1},
+//     so a key with no larger peak before it and no smaller valley after it stands where it belongs (no descents: all of
+//     them), and only the others read their window from `in`;
+//   * a peak larger than K_i more than W places before i, a valley smaller than K_i more than W places behind it, or
+//     K_{i-W-1} > K_i, is an inversion too far apart: refused;
+//   * crowds keep the passes and their re-run (`reruns` keeps its meaning): a bucket whose span exceeds 24 bits is refused
+//     when some K_i and K_{i+kFixRun} (input order) are equal in the top 24 bits of the span.
+// The decision is a function of the bucket's input alone (tests/sort_place_ref.py is its twin), every thread reads it from
+// LDS after a barrier, and a refused bucket goes on into the passes with the keys it holds in registers.  It is taken in two
+// steps: what the keys in registers and the list say first (crowd, a peak too far in front), so that a bucket with an
+// inversion far apart reads no window; then, only in a bucket that has descents, what the windows say.
+// Who is tested at all is decided by bucket_sort_kernel (`placeable`): single-bucket launches and the ranges of a direct build
+// in which NO body changed bucket, up to kPlaceItemsMax keys per thread.  A bucket that is tested and refused pays the test and
+// then the passes, and the kernel is as slow as its slowest bucket: builds that took the counting pass and builds with
+// crossers -- bodies on their way, which also stand far from their place inside ranges -- were measurably slower with the test
+// (profiles/sort_place/README.md) and take the passes untested.
+//
+// The stages, their barriers and what the LDS words hold between them:
+//   before barrier 1 (the kmin / kmax barrier): every wave clears its row of match and lists its descents in match[w][0 ..
+//     2 * kPlaceMaxDescents); thread 0 clears sm[4], sm[5] and puts this bucket's two counters into sm[6], sm[7] (kept to the end:
+//     bs_scan256 uses sm[0..3] only); s_red[2 * kBsWaves + w] = descents of wave w;
+//   after barrier 1: too many descents -> passes.  Else stage 1, from registers and the lists (read-only from here): crowd, peak
+//     and valley rule; a thread that refuses sets sm[4];
+//   barrier 2 (skipped when nothing can refuse: no descent, span <= 24 bits): sm[4] set -> passes.  Else stage 2: every key is
+//     written to its rank -- speculatively, the passes overwrite all of it after a refusal -- and a key one place beyond whose
+//     window a larger key stands sets sm[5];
+//   barrier 3 (only with descents): sm[5] set -> passes, else placed.
+//   On the way to the passes every wave zeroes the list entries of its own row again (all reads of them lie before barrier 2).
+constexpr int kPlaceWindow = 8;
+// (every key is compared with every listed descent, so what a bucket pays before it is refused grows with their number;
+// slow motion leaves one or two)
+constexpr int kPlaceMaxDescents = 8;
+// keys per thread up to which the in-LDS sort has the path: a range of the direct input holds at most 4,096 keys (L <= 4,096 up
+// to 4M bodies) and a single-bucket launch as many, so no larger tier ever meets a bucket that may be placed
+constexpr int kPlaceItemsMax = 4;
+static_assert(2 * kPlaceMaxDescents <= kDigits, "a wave lists its descents in its own row of match");
 template <int ITEMS>
 __device__ __forceinline__ void bucket_sort_lds(const uint64_t *in, int m, uint64_t *skey,
                                                 uint32_t (*woff)[kDigits], uint64_t (*match)[kDigits],
                                                 uint32_t *sm, uint64_t *s_red, uint32_t *s_flag,
                                                 uint64_t *__restrict__ kout, uint32_t *__restrict__ vout,
-                                                uint32_t *__restrict__ reruns)
+                                                uint32_t *__restrict__ reruns, uint32_t *__restrict__ paths, bool placeable)
 {
+    const bool place = ITEMS <= kPlaceItemsMax && placeable;    // (uniform)
     const int t = threadIdx.x, w = wave_id(), l = lane_id();
     const int wbase = w * (kWave * ITEMS);
+    // how often this bucket number was placed / went through the passes so far: thread 0 adds one to either at the end, in words
+    // nobody else touches (loaded here, with the keys, and kept in sm[6], sm[7]: no atomic and no load at the end of the chain).
+    // A plain load and store: right only because the bucket_sort_kernel launches of one context follow each other on one stream.
+    uint32_t seen[2] = {0u, 0u};
+    if (t == 0) { seen[0] = paths[0]; seen[1] = paths[kBucketsBig]; }
     uint64_t key[ITEMS];
+    // placement: every key's predecessor, loaded beside it (the same lines; passing it from lane to lane cost four cross-lane
+    // operations per key), and the kFixRun keys behind this wave's last (for the crowd rule)
+    uint64_t pred[ITEMS <= kPlaceItemsMax ? ITEMS : 1];
     uint64_t kmin = ~0ull, kmax = 0ull;
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
         const int i = wbase + r * kWave + l;
         key[r] = (i < m) ? in[i] : ~0ull;
+        if (ITEMS <= kPlaceItemsMax) pred[r] = (place && i > 0 && i < m) ? in[i - 1] : 0ull;
         if (i < m) {
             const uint64_t k = key[r] & kKeyMask40;
             kmin = (k < kmin) ? k : kmin; kmax = (k > kmax) ? k : kmax;
         }
     }
-    for (int k = t; k < kBsWaves * kDigits; k += kBsThreads) { (&woff[0][0])[k] = 0; (&match[0][0])[k] = 0ull; }
-    if (t == 0) *s_flag = 0u;
+    uint64_t behind = 0ull;
+    const bool has_behind = place && l >= kWave - kFixRun && wbase + kWave * ITEMS + l - (kWave - kFixRun) < m;
+    if (has_behind) behind = in[wbase + kWave * ITEMS + l - (kWave - kFixRun)];
+    // (every wave clears its own row of match: its list of descents below goes there, behind the zeroes)
+    for (int k = t; k < kBsWaves * kDigits; k += kBsThreads) (&woff[0][0])[k] = 0;
+#pragma unroll
+    for (int k = 0; k < kDigits / kWave; ++k) match[w][k * kWave + l] = 0ull;
+    if (t == 0) { *s_flag = 0u; sm[4] = 0u; sm[5] = 0u; sm[6] = seen[0]; sm[7] = seen[1]; }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const uint64_t a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
         kmin = (a < kmin) ? a : kmin; kmax = (b > kmax) ? b : kmax;
     }
-    if (l == 0) { s_red[w] = kmin; s_red[kBsWaves + w] = kmax; }
+    uint32_t ndesc = 0;                                         // this wave's descents (uniform)
+    if (place) {
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) {
+            const int i = wbase + r * kWave + l;
+            const uint64_t k = key[r] & kKeyMask40;
+            const uint64_t prev = pred[ITEMS <= kPlaceItemsMax ? r : 0] & kKeyMask40;
+            const bool desc = i < m && k < prev;
+            const uint64_t bal = __ballot(desc);
+            if (bal != 0ull) {                                  // (uniform; rare)
+                if (ndesc < (uint32_t)kPlaceMaxDescents) {      // (a wave that is over has nothing to list)
+                    const uint32_t slot = ndesc + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                    if (desc && slot < (uint32_t)kPlaceMaxDescents) {
+                        match[w][2 * slot] = prev | ((uint64_t)i << kPackShift);
+                        match[w][2 * slot + 1] = k;
+                    }
+                }
+                ndesc += (uint32_t)__popcll(bal);
+            }
+        }
+    }
+    if (l == 0) { s_red[w] = kmin; s_red[kBsWaves + w] = kmax; s_red[2 * kBsWaves + w] = ndesc; }
     __syncthreads();
     kmin = ~0ull; kmax = 0ull;
+    uint32_t descents = 0;
 #pragma unroll
     for (int k = 0; k < kBsWaves; ++k) {
         const uint64_t a = s_red[k], b = s_red[kBsWaves + k];
         kmin = (a < kmin) ? a : kmin; kmax = (b > kmax) ? b : kmax;
+        descents += (uint32_t)s_red[2 * kBsWaves + k];
     }
     const uint64_t span = kmax - kmin;
     const int bits = span ? 64 - __clzll(span) : 0;
+    if (place && descents <= (uint32_t)kPlaceMaxDescents) {     // (uniform)
+        bool refuse = false;
+        if (bits > 24) {                                        // the crowd rule
+            const int first = bits - 24;
+            uint32_t top[ITEMS + 1];
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) top[r] = (wbase + r * kWave + l < m) ? (uint32_t)(((key[r] & kKeyMask40) - kmin) >> first) : ~0u;
+            top[ITEMS] = has_behind ? (uint32_t)(((behind & kKeyMask40) - kmin) >> first) : ~0u;   // (lanes 56.. hold them)
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) {
+                const uint32_t a = (uint32_t)__shfl((int)top[r], (l + kFixRun) & (kWave - 1));
+                // (the round behind: lane l + 8 - 64; behind the last round the lane itself holds the word)
+                const uint32_t b = (r + 1 < ITEMS) ? (uint32_t)__shfl((int)top[r + 1], (l + kFixRun) & (kWave - 1)) : top[ITEMS];
+                const uint32_t other = (l < kWave - kFixRun) ? a : b;
+                refuse = refuse || (top[r] != ~0u && other == top[r]);
+            }
+        }
+        uint32_t low = 0, high = 0;                             // bit r: key r has a larger key before / a smaller one behind it
+        if (descents != 0u) {
+            for (int k = 0; k < kBsWaves; ++k) {
+                const uint32_t held = (uint32_t)s_red[2 * kBsWaves + k];
+                for (uint32_t e = 0; e < held; ++e) {
+                    const uint64_t word = match[k][2 * e], valley = match[k][2 * e + 1];
+                    const uint64_t peak = word & kKeyMask40;
+                    const int at = (int)(word >> kPackShift);   // the valley's position; the peak stands at at - 1
+#pragma unroll
+                    for (int r = 0; r < ITEMS; ++r) {
+                        const int i = wbase + r * kWave + l;
+                        const uint64_t kk = key[r] & kKeyMask40;
+                        if (i < m) {
+                            low |= (at <= i && peak > kk) ? 1u << r : 0u;
+                            high |= (at > i && valley < kk) ? 1u << r : 0u;
+                            // (a larger peak or a smaller valley further off than the window: an inversion too far apart.
+                            // What is left for the windows below is at most kPlaceWindow keys on either side of a descent)
+                            refuse = refuse || (at + kPlaceWindow <= i && peak > kk) || (at > i + kPlaceWindow && valley < kk);
+                        }
+                    }
+                }
+            }
+        }
+        // what the registers and the list say is decided first: a bucket with an arrival in front of its own keys, or a crowd,
+        // has read no window when it goes on to the passes (in order and a span of <= 24 bits: nothing can have refused)
+        bool placed = bits <= 24 && descents == 0u;
+        if (!placed) {
+            if (refuse) sm[4] = 1u;
+            __syncthreads();
+            placed = sm[4] == 0u;
+        }
+        if (placed) {
+            // every key goes straight to its place in memory; a key more than the window behind a larger one that is no peak
+            // (the run before a descent) shows only here, and then the passes overwrite all of it
+            refuse = false;
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) {
+                const int i = wbase + r * kWave + l;
+                if (i < m) {
+                    const uint64_t kk = key[r] & kKeyMask40;
+                    int delta = 0;
+                    if (((low | high) >> r) & 1u) {
+                        // both windows and the key one place beyond, loaded together (one after the other they are a chain
+                        // of seventeen memory latencies; a place outside the bucket counts as nothing)
+                        uint64_t back[kPlaceWindow + 1], ahead[kPlaceWindow];
+#pragma unroll
+                        for (int d = 1; d <= kPlaceWindow + 1; ++d) back[d - 1] = (i - d >= 0) ? in[i - d] & kKeyMask40 : 0ull;
+#pragma unroll
+                        for (int d = 1; d <= kPlaceWindow; ++d) ahead[d - 1] = (i + d < m) ? in[i + d] & kKeyMask40 : kKeyMask40;
+#pragma unroll
+                        for (int d = 0; d < kPlaceWindow; ++d) delta += ((ahead[d] < kk) ? 1 : 0) - ((back[d] > kk) ? 1 : 0);
+                        refuse = refuse || back[kPlaceWindow] > kk;
+                    }
+                    kout[i + delta] = kk;
+                    vout[i + delta] = (uint32_t)(key[r] >> kPackShift);
+                }
+            }
+            if (descents != 0u) {
+                if (refuse) sm[5] = 1u;
+                __syncthreads();
+                placed = sm[5] == 0u;
+            }
+            if (placed) {
+                if (t == 0) paths[0] = sm[6] + 1u;
+                return;
+            }
+        }
+    }
+    if (place && l < 2 * kPlaceMaxDescents && (uint32_t)l < 2u * ndesc) match[w][l] = 0ull;   // the wave's list: its row is zero again
     if (bits == 0) {                                            // all keys equal (or one key): order is final
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) {
@@ -625,6 +797,7 @@ __device__ __forceinline__ void bucket_sort_lds(const uint64_t *in, int m, uint6
         // the run that are larger); keys equal in all bits keep their order.
         const uint64_t lowmask = (1ull << first) - 1ull;
         bool too_long = false;
+        if (t == 0) paths[kBucketsBig] = sm[7] + 1u;          // (the same value again after a re-run)
         // (every key goes straight to its place in memory, at most kFixRun places from a coalesced store; should a run turn
         // out too long, the full sort below overwrites all of it)
 #pragma unroll
@@ -669,6 +842,7 @@ __device__ __forceinline__ void bucket_sort_lds(const uint64_t *in, int m, uint6
         __syncthreads();
         first = 0; passes = full; fix = false;
     }
+    if (t == 0) paths[kBucketsBig] = sm[7] + 1u;
     for (int i = t; i < m; i += kBsThreads) {
         const uint64_t k = skey[i];
         kout[i] = (k & kKeyMask40) + kmin;
@@ -715,13 +889,13 @@ __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__res
                                                                   const uint32_t *__restrict__ bucket_start,
                                                                   uint32_t *__restrict__ spills,
                                                                   uint32_t *__restrict__ reruns, int single_m,
-                                                                  BucketDirect dz = BucketDirect{})
+                                                                  BucketDirect dz, uint32_t *__restrict__ paths, int place)
 {
     __shared__ uint64_t skey[kBucketCap];
     __shared__ uint32_t woff[kBsWaves][kDigits];
     __shared__ uint64_t match[kBsWaves][kDigits];
     __shared__ uint32_t sm[8];
-    __shared__ uint64_t s_or[2 * kBsWaves];
+    __shared__ uint64_t s_or[3 * kBsWaves];
     __shared__ uint32_t s_flag;
     __shared__ uint32_t s_dz[3];                                // direct input: arrivals, arrivals from lower ranges, departures
     const int t = threadIdx.x, w = wave_id(), l = lane_id();
@@ -735,6 +909,9 @@ __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__res
     const int64_t counted_start = bucket_total ? (int64_t)bucket_start[blockIdx.x] : 0;
     const int counted_m = bucket_total ? (int)bucket_total[blockIdx.x] : single_m;
     const uint32_t crossers = dz.count ? direct_total(dz.count, dz.nsub, dz.cap, dz.subcap) : ~0u;       // (uniform)
+    // placement is tried only where the input can be in order: a single-bucket launch, and the ranges of a direct build without
+    // a crosser.  (uniform)
+    bool placeable = place != 0 && bucket_total == nullptr;
     if (crossers == ~0u) {
         start = counted_start;
         m = counted_m;
@@ -745,6 +922,7 @@ __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__res
         const int64_t r0 = ((int64_t)b * dz.len < dz.n) ? (int64_t)b * dz.len : dz.n;
         const int len = (int)((r0 + dz.len < dz.n ? r0 + dz.len : dz.n) - r0);
         if (crossers == 0u) {                                    // nobody changed bucket: the range as it stands
+            placeable = place != 0;
             start = r0; m = len;
             if (m == 0) return;
             in = dz.keys + r0;
@@ -841,13 +1019,13 @@ __global__ __launch_bounds__(kBsThreads) void bucket_sort_kernel(uint64_t *__res
     uint64_t *ko = kout + start;
     uint32_t *vo = vout + start;
 
-    if (m <= 1 * kBsThreads) { bucket_sort_lds<1>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= 2 * kBsThreads) { bucket_sort_lds<2>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= 4 * kBsThreads) { bucket_sort_lds<4>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= 5 * kBsThreads) { bucket_sort_lds<5>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= 6 * kBsThreads) { bucket_sort_lds<6>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= 8 * kBsThreads) { bucket_sort_lds<8>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
-    if (m <= kBucketCap) { bucket_sort_lds<kBucketItemsMax>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns); return; }
+    if (m <= 1 * kBsThreads) { bucket_sort_lds<1>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= 2 * kBsThreads) { bucket_sort_lds<2>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= 4 * kBsThreads) { bucket_sort_lds<4>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= 5 * kBsThreads) { bucket_sort_lds<5>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= 6 * kBsThreads) { bucket_sort_lds<6>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= 8 * kBsThreads) { bucket_sort_lds<8>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
+    if (m <= kBucketCap) { bucket_sort_lds<kBucketItemsMax>(in, m, skey, woff, match, sm, s_or, &s_flag, ko, vo, reruns, paths + blockIdx.x, placeable); return; }
 
     // which key bits differ inside the bucket: only those bytes need a pass
     const uint64_t k0 = in[0];

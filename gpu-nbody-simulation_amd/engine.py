@@ -1382,6 +1382,13 @@ class BarnesHutEngine:
         return BhSortSnapshot(True, n, nb, L, cap, subcap, nsub, ks[:n], pm[:n], dec, rk, lst[:nsub * subcap].reshape(nsub, subcap),
                               kin[:n], counting)
 
+    def sort_paths(self):
+        """(placed, passed): buckets of the bucket sort finished by placement, and buckets that went through byte passes,
+        both cumulative since the engine was created (bh_sort_paths)."""
+        out = (C.c_uint64 * 2)()
+        self._check(self._lib.bh_sort_paths(self._h, out))
+        return int(out[0]), int(out[1])
+
     def step_times(self):
         """(step_ms[k], walk_ms[k]) of the steps of the last step() call (at most 4,096): HIP events per step."""
         n = C.c_int32(0)

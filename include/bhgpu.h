@@ -760,6 +760,15 @@ int bh_step_times(bh_ctx *ctx, double *step_ms, double *walk_ms, int32_t cap, in
 int bh_sort_snapshot(bh_ctx *ctx, int64_t info[8], uint32_t *decision, uint64_t *range_keys, uint64_t *list, uint64_t *keys_in,
                      uint64_t *keys_sorted, uint32_t *perm);
 
+/* How the buckets of the bucket sort's in-LDS sort ended, cumulative since bh_create:
+ * out[0] buckets finished by placement -- nearly ordered input, every key written straight to its rank, no byte pass; tried
+ *   for single-bucket launches and for the ranges of a direct build in which no body changed bucket
+ *   (BH_SORT_PLACE=0 at bh_create turns that path off: out[0] stays 0);
+ * out[1] buckets that went through byte passes (those counted in bh_stats_t.sort_rerun_buckets among them).
+ * A bucket of equal keys with placement off, and a bucket sorted through memory (sort_spill_buckets), count in neither.
+ * Waits for the stream; no launch. */
+int bh_sort_paths(bh_ctx *ctx, uint64_t out[2]);
+
 /* --- multi-GPU plumbing -----------------------------------------------------------------
  * The reference is single-GPU.  One process per GPU owns a contiguous range [lo, hi) of
  * the sorted (space-filling-curve order) bodies: bh_step then walks and integrates only that range, and the
