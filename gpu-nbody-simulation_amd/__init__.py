@@ -10,7 +10,8 @@ from .engine import (BarnesHutEngine, BhConfig, BhError, BhForceError, BhGroups,
                      BhTimestep, LagrangianSelect, Precision, correlation_from, density_centre_from, force_error_stats, lagrangian_from,
                      local_density_from, radial_edges, radial_exponents, radial_profile_from_planes,
                      BhMassSegregation, BhSpanningTree, mass_segregation_from, spanning_tree_from, BhBinaries, binaries_from_records,
-                     BhNeighbourLists, neighbour_lists_from)
+                     BhNeighbourLists, neighbour_lists_from, BhAzimuthalModes, BhModeTotal, azimuthal_modes_from_planes,
+                     modes_exponents, modes_planes)
 from .textio import loadSimulationDataFromText, save_init_files  # noqa: F401
 
 __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups", "BhMomentMap", "BhTimestep", "Precision",
@@ -18,4 +19,5 @@ __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups",
            "BhRadialProfile", "BhLagrangian", "LagrangianSelect", "radial_edges", "radial_exponents",
            "radial_profile_from_planes", "lagrangian_from", "BhPairCounts", "correlation_from", "BhSortSnapshot",
            "BhSpanningTree", "BhMassSegregation", "mass_segregation_from", "spanning_tree_from",
-           "BhBinaries", "binaries_from_records", "BhNeighbourLists", "neighbour_lists_from"]
+           "BhBinaries", "binaries_from_records", "BhNeighbourLists", "neighbour_lists_from",
+           "BhAzimuthalModes", "BhModeTotal", "azimuthal_modes_from_planes", "modes_exponents", "modes_planes"]

@@ -130,6 +130,11 @@ SIGNATURES = {
                                       C.POINTER(C.c_int32)]),
     "bh_radial_select": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(_vp)]),
     "bh_radial_times": (C.c_int, [_ctx, _dp, _dp, _dp]),
+    "bh_azimuthal_modes": (C.c_int, [_ctx, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int32)]),
+    "bh_modes_max": (C.c_int, [_ctx, _dp, _dp, C.c_int32, C.c_int32, _dp]),
+    "bh_modes_deposit": (C.c_int, [_ctx, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp)]),
+    "bh_modes_times": (C.c_int, [_ctx, _dp, _dp]),
     "bh_neighbours": (C.c_int,[_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
     "bh_count_within": (C.c_int, [_ctx, _dp, C.c_int64, C.c_double, C.POINTER(C.c_uint32)]),
     "bh_neighbours_times": (C.c_int, [_ctx, _dp, _dp]),

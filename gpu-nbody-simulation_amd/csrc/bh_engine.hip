@@ -1,6 +1,6 @@
 // bh_engine.hip -- libbhgpu.so: the C-ABI of include/bhgpu.h.  In this file: the context and its helpers, the tree build, the
 // walks' launchers, the step and the split operators, the diagnostics, direct sums and force check, tree export, the
-// locally-essential trees and migration.  The analysis queries' host code -- moment maps, radial profiles, field at points,
+// locally-essential trees and migration.  The analysis queries' host code -- moment maps, radial profiles, azimuthal modes, field at points,
 // neighbours, pair counts, groups, spanning trees -- is bh_queries_host.hpp, included below as part of this unit.
 // Compiled with -ffp-contract=off (tree build + exact walk must not fuse multiply-adds; the fp32
 // walk lives in bh_walk_fast.hip, compiled separately).  gfx950 only, no CPU fallback.
@@ -30,6 +30,7 @@
 #include "bh_split.hpp"
 #include "bh_moments.hpp"
 #include "bh_radial.hpp"
+#include "bh_modes.hpp"
 #include "bh_neighbours.hpp"
 #include "bh_neighbour_lists.hpp"
 #include "bh_pairs.hpp"
@@ -170,6 +171,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     // the analysis queries (bh_queries_host.hpp; one struct per family, bh_queries_state.hpp), all allocated on first use
     MapState map;
     RadState rad;
+    ModState mod;
     FieldState field;
     NbState nb;
     PairState pair;
@@ -1117,7 +1119,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
-    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mst.ev); destroy(c->bin.ev); destroy(c->nbl.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mod.ev); destroy(c->mst.ev); destroy(c->bin.ev); destroy(c->nbl.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

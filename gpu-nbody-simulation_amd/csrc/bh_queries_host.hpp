@@ -1,8 +1,8 @@
-// bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, the field
+// bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, azimuthal modes, the field
 // at points, neighbour queries and lists, pair counts, friends-of-friends groups, spanning trees and bound pairs, with their entry points
 // of include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
 // (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp,
-// bh_radial.hpp, bh_field.hpp, bh_neighbours.hpp, bh_neighbour_lists.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
+// bh_radial.hpp, bh_modes.hpp, bh_field.hpp, bh_neighbours.hpp, bh_neighbour_lists.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
 // bh_queries_state.hpp,
 // the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes first.
 #pragma once
@@ -343,6 +343,96 @@ int rad_select_round(bh_ctx *c, const char *who, const RadCentre &ctr, int32_t e
     if (flags & kRadFlagLarge)
         return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e0) + " is too large for this context's masses and body count");
     return BH_OK;
+}
+
+// ---- azimuthal modes (bh_modes.hpp).  As the radial profiles: they read pos / vel / mass as they lie in memory and write
+// buffers of their own -- no tree, no build, no record of bh_run_state.hpp.
+int mod_alloc(bh_ctx *c)
+{
+    ModState &s = c->mod;
+    if (s.max) return BH_OK;
+    return alloc_all(c, {part(&s.max, 1), part(&s.e2, (size_t)kModMaxBins + 1),
+                         part(&s.planes, (size_t)kModMaxPlanes * (kModMaxBins + 2))});
+}
+
+// pass 1: maxA and maxD on the host when this returns (without rates the velocities are not read and maxD is 0);
+// BH_ERR_ARG when a body is not finite
+int mod_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, int M, bool rates, double (&maxabs)[2])
+{
+    ModState &s = c->mod;
+    maxabs[0] = maxabs[1] = 0.0;
+    s.max_ms = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = mod_alloc(c)) return rc;
+    if (int rc = mark(c, s.ev[0])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(ModMax), c->stream));
+    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+        dispatch([&](auto r) {
+            hipLaunchKernelGGL((modes_max_kernel<decltype(r)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(rad_grid(c)),
+                               dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, M, s.max);
+        }, rates);
+    });
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[1])) return rc;
+    ModMax r{};
+    if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
+    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.max_ms)) return rc;
+    if (r.bad)
+        return fail(c, BH_ERR_ARG, std::string(who) + ": the first pass found a body with a non-finite position, " +
+                                   (rates ? "velocity, " : "") + "mass or squared radius, or a contribution m c_k, m s_k" +
+                                   (rates ? ", m w c_k, m w s_k (w = b / r2)" : "") + " that overflows fp64");
+    return BH_OK;
+}
+
+int mod_args(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, int32_t M, RadCentre *ctr)
+{
+    if (int rc = rad_centre(c, who, centre, centre_vel, ctr)) return rc;
+    if (M < 0 || M > kModMaxM) return fail(c, BH_ERR_ARG, std::string(who) + ": M must be 0 .. BH_MODES_MAX_M = " + std::to_string(kModMaxM));
+    return BH_OK;
+}
+
+// both passes.  e: the caller's two exponents `given` or, without, the rule's own from this context's maxima.  The planes stay
+// on the device (mod.planes, P x (nb + 2)).
+int mod_passes(bh_ctx *c, const char *who, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int32_t M,
+               bool rates, const int32_t *given, int32_t (&e)[2])
+{
+    ModState &s = c->mod;
+    const std::string w(who);
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = mod_args(c, who, centre, centre_vel, M, &ctr)) return rc;
+    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
+    const unsigned why = squared_edges(edges, nb, kModMaxBins, e2);
+    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_MODES_MAX_BINS = " + std::to_string(kModMaxBins));
+    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
+    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
+    if (why) return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
+    if (int rc = need_upload(c, w + " before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double maxabs[2];
+    if (int rc = mod_maxima(c, who, ctr, M, rates, maxabs)) return rc;
+    for (int p = 0; p < 2; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
+    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    if (int rc = mod_alloc(c)) return rc;
+    const int S = nb + 2, P = modes_planes(M, rates);
+    s.deposit_ms = 0.0;
+    if (int rc = mark(c, s.ev[2])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)P * S * sizeof(long long), c->stream));
+    if (c->n > 0) {
+        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        const ModesPlan plan = modes_plan(P, nb);
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            dispatch([&](auto r) {
+                hipLaunchKernelGGL((modes_deposit_kernel<decltype(r)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>),
+                                   dim3(rad_grid(c)), dim3(kBlock), plan.bytes, c->stream, pos, vel, mass, c->n, ctr, s.e2, (int)nb, (int)M,
+                                   plan.tile, (int)e[0], (int)e[1], s.planes);
+            }, rates);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[3])) return rc;
+    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
+    return span_ms(c, s.ev[2], s.ev[3], &s.deposit_ms);
 }
 
 // ---- the field at arbitrary points (bh_field.hpp)
@@ -764,6 +854,51 @@ int bh_radial_times(bh_ctx *c, double *max_ms, double *main_ms, double *rounds_m
     *max_ms = c->rad.max_ms;
     *main_ms = c->rad.main_ms;
     if (rounds_ms) std::copy(c->rad.round_ms, c->rad.round_ms + kRadRounds, rounds_ms);
+    return BH_OK;
+}
+
+int bh_modes_max(bh_ctx *c, const double *centre, const double *centre_vel, int32_t M, int32_t rates, double *maxabs)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!maxabs) return fail(c, BH_ERR_ARG, "bh_modes_max: null output");
+    RadCentre ctr{};
+    if (int rc = mod_args(c, "bh_modes_max", centre, centre_vel, M, &ctr)) return rc;
+    if (int rc = need_upload(c, "bh_modes_max before bh_upload/bh_initialize")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    double m[2];
+    if (int rc = mod_maxima(c, "bh_modes_max", ctr, M, rates != 0, m)) return rc;
+    std::copy(m, m + 2, maxabs);
+    return BH_OK;
+}
+
+int bh_modes_deposit(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int32_t M,
+                     int32_t rates, const int32_t *exponents, void **planes_dev)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!exponents || !planes_dev) return fail(c, BH_ERR_ARG, "bh_modes_deposit: null argument");
+    int32_t e[2];
+    if (int rc = mod_passes(c, "bh_modes_deposit", centre, centre_vel, edges, nb, M, rates != 0, exponents, e)) return rc;
+    *planes_dev = c->mod.planes;
+    return BH_OK;
+}
+
+int bh_azimuthal_modes(bh_ctx *c, const double *centre, const double *centre_vel, const double *edges, int32_t nb, int32_t M,
+                       int32_t rates, int64_t *planes, int32_t *exponents)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_azimuthal_modes: null argument");
+    int32_t e[2];
+    if (int rc = mod_passes(c, "bh_azimuthal_modes", centre, centre_vel, edges, nb, M, rates != 0, nullptr, e)) return rc;
+    BH_HIP(c, hipMemcpy(planes, c->mod.planes, (size_t)modes_planes(M, rates != 0) * (nb + 2) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + 2, exponents);
+    return BH_OK;
+}
+
+int bh_modes_times(bh_ctx *c, double *max_ms, double *deposit_ms)
+{
+    if (!c || !max_ms || !deposit_ms) return fail(c, BH_ERR_ARG, "bh_modes_times: null argument");
+    *max_ms = c->mod.max_ms;
+    *deposit_ms = c->mod.deposit_ms;
     return BH_OK;
 }
 

@@ -34,6 +34,16 @@ struct RadState {
     double max_ms = 0.0, main_ms = 0.0, round_ms[kRadRounds] = {};     // of the last call (bh_radial_times)
 };
 
+// azimuthal modes (bh_modes.hpp): the first pass's record, the squared edges, and the int64 planes of up to kModMaxPlanes x
+// (BH_MODES_MAX_BINS + 2) slots; the launch shape is the radial kernels' (rad.blocks)
+struct ModState {
+    ModMax *max = nullptr;
+    double *e2 = nullptr;
+    long long *planes = nullptr;
+    hipEvent_t ev[4] = {};                                      // around the first pass and around the deposit
+    double max_ms = 0.0, deposit_ms = 0.0;                      // of the last call (bh_modes_times)
+};
+
 // the field at arbitrary points (bh_field.hpp): one block for a launch of up to block.cap points -- the points, their results, two
 // key arrays and the sorted order, the sort's count matrix and row totals
 struct FieldState {

@@ -57,6 +57,23 @@ inline unsigned squared_edges(const double *edges, int32_t nb, int32_t max_bins,
     return 0;
 }
 
+// ---- azimuthal modes (bh_modes.hpp): P planes of nb + 2 slots in the 64 KiB of dynamic LDS a launch may ask for without opting
+// in.  The whole histogram and the nb + 1 squared edges when they fit (tile 0: private); else a tile of floor(65,536 / (8 P))
+// slots for the range a workgroup's bodies touch.  bytes: the dynamic LDS of the launch.
+constexpr int kModesLdsBytes = 65536;
+
+inline int modes_planes(int M, bool rates) { return (rates ? 2 : 1) * (1 + 2 * M) + 1; }
+
+struct ModesPlan { int tile; size_t bytes; };
+
+inline ModesPlan modes_plan(int P, int nb)
+{
+    const size_t whole = 8 * (size_t)P * ((size_t)nb + 2) + 8 * ((size_t)nb + 1);
+    if (whole <= (size_t)kModesLdsBytes) return ModesPlan{0, whole};
+    const int tile = kModesLdsBytes / (8 * P);
+    return ModesPlan{tile, 8 * (size_t)P * (size_t)tile};
+}
+
 // ---- query points {x, y}: the first with a coordinate that is not finite, or -1 (no points: -1)
 inline int64_t first_nonfinite_point(const double *points, int64_t n_points)
 {

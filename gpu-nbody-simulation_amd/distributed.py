@@ -676,6 +676,31 @@ class LetStepper:
         g = self._all_reduce_(g, dist.ReduceOp.SUM)
         return radial_profile_from_planes(g.cpu().numpy().reshape(6, nb + 2).copy(), e, ed, c, u, raw)
 
+    def azimuthal_modes(self, edges, m_max: int = 4, centre="com", centre_velocity=None, rates: bool = False, raw: bool = False):
+        """BhAzimuthalModes of the WHOLE system (engine.azimuthal_modes), the same bits on every rank and the same bits as one
+        engine's modes of the same bodies.  all_reduce MAX of the ranks' two maxima and SUM of their body counts, from which
+        every rank derives the same two exponents; each rank sums its own bodies in fixed point; one all_reduce(SUM) of the
+        int64 planes.  centre: "com" or a pair.  Collective: every rank must call it with the same arguments (checked:
+        ValueError on every rank if not).  Reads the state only."""
+        import numpy as np
+        from .engine import azimuthal_modes_from_planes, modes_exponents, modes_planes
+        c = self._radial_centre(centre, "azimuthal_modes")
+        u = np.zeros(2) if centre_velocity is None else np.ascontiguousarray(centre_velocity, dtype=np.float64).reshape(2)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb, M, rates = len(ed) - 1, int(m_max), bool(rates)
+        try:
+            mx, bad = self.eng.modes_max(c, u, M, rates), None
+        except Exception as err:                                  # noqa: BLE001 -- re-raised below, after the collective
+            mx, bad = np.zeros(2), err
+        hi, n_total = self._radial_agree("azimuthal_modes", [*c, *u, float(nb), float(M), float(rates), *ed], mx, bad)
+        e = modes_exponents(hi, n_total)
+        g = self.eng.modes_deposit(ed, c, u, e, M, rates)
+        P = modes_planes(M, rates)
+        if not isinstance(g, torch.Tensor):                       # stand-in engines hand a tensor over directly
+            g = wrap_device(g, P * (nb + 2), "<i8", self.device)
+        g = self._all_reduce_(g, dist.ReduceOp.SUM)
+        return azimuthal_modes_from_planes(g.cpu().numpy().reshape(P, nb + 2).copy(), e, ed, M, rates, c, u, raw)
+
     def lagrangian_radii(self, fractions=(0.01, 0.1, 0.5, 0.9), centre="com"):
         """BhLagrangian of the WHOLE system (engine.lagrangian_radii), the same bits on every rank and the same bits as one
         engine's radii of the same bodies.  all_reduce MAX of the ranks' largest masses and SUM of their body counts give the

@@ -9,7 +9,8 @@ import ctypes as C
 import enum
 import math
 import os
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, field, replace
+from typing import NamedTuple
 
 import numpy as np
 
@@ -337,6 +338,147 @@ def lagrangian_from(fractions, r2, count, mass_units, exponent: int, centre) -> 
     units = np.asarray(mass_units, dtype=np.int64).copy()
     return BhLagrangian(np.asarray(fractions, dtype=np.float64).copy(), np.sqrt(r2), r2, np.asarray(count, dtype=np.int64).copy(),
                         np.ldexp(units.astype(np.float64), -int(exponent)), units, int(exponent), tuple(float(x) for x in centre))
+
+
+MODES_MAX_M = 16                        # BH_MODES_MAX_M
+MODES_MAX_BINS = 4096                   # BH_MODES_MAX_BINS
+
+
+class BhModeTotal(NamedTuple):
+    """One harmonic of the coherent sum over a range of bins (BhAzimuthalModes.total)."""
+    amplitude: float             # |A_k| / A_0 (NaN without mass)
+    phase: float                 # atan2(Im A_k, Re A_k) / k (0 for k = 0)
+    pattern_speed: float         # Re(D_k / A_k); NaN for k = 0, A_k = 0 or without rates
+
+
+def modes_planes(m_max: int, rates: bool) -> int:
+    """The number of int64 planes of azimuthal modes up to m_max: A, with rates D, and the count."""
+    return (2 if rates else 1) * (1 + 2 * int(m_max)) + 1
+
+
+def modes_exponents(maxabs, n_total: int) -> np.ndarray:
+    """The two exponents 62 - E - L of the A- and the D-planes from the maxima {maxA, maxD} (bh_modes_max, combined over the
+    ranks with MAX) and the body count of the whole system; 0 where the maximum is 0."""
+    m = np.asarray(maxabs, dtype=np.float64).reshape(-1)
+    if len(m) != 2:
+        raise ValueError("two maxima")
+    return radial_exponents(m, n_total)
+
+
+def _mode_numbers(re_a, im_a, a0, re_d, im_d, k):
+    """(amplitude, phase, pattern speed) of one harmonic from the values of its sums (arrays or scalars; re_d None: no rates)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        amp = np.hypot(re_a, im_a) / a0
+        amp = np.where(a0 == 0.0, np.nan, amp)
+        phase = np.arctan2(im_a, re_a) / k if k else np.zeros_like(amp)
+        if re_d is None or k == 0:
+            speed = np.full_like(amp, np.nan)
+        else:
+            speed = (re_d * re_a + im_d * im_a) / (re_a * re_a + im_a * im_a)
+            speed = np.where((re_a == 0.0) & (im_a == 0.0), np.nan, speed)
+    return amp, phase, speed
+
+
+@dataclass
+class BhAzimuthalModes:
+    """Azimuthal Fourier modes of the current state about a centre on the nb bins between edges (azimuthal_modes):
+    A_k(bin) = sum m exp(i k phi) for k = 0 .. m_max, and with rates D_k(bin) = sum m w exp(i k phi), w the angular velocity of
+    a body about the centre.  The sums are fixed-point integers times 2^-exponent; everything else is derived from them.
+
+    pattern_speed = Re(D_k / A_k) is the INSTANTANEOUS rate of the phase of A_k with the membership of the bin held fixed.  It
+    is exact for the sum over all slots and for a rigidly turning pattern; for a single narrow bin it ignores the flux of
+    bodies across the bin's edges.  For a measured speed take pattern_speed_between two results a time dt apart."""
+    edges: np.ndarray            # (nb + 1,)
+    centre: tuple
+    centre_velocity: tuple
+    m_max: int
+    count: np.ndarray            # (nb,) bodies per bin, int64
+    mass: np.ndarray             # (nb,) A_0 per bin
+    inside: float                # the mass inside edges[0] ...
+    beyond: float                # ... and at or beyond edges[nb]
+    coeff: np.ndarray            # (m_max + 1, nb) complex: A_k
+    amplitude: np.ndarray        # (m_max + 1, nb): |A_k| / A_0, NaN in a bin without mass; row 0 is 1
+    phase: np.ndarray            # (m_max + 1, nb): atan2(Im A_k, Re A_k) / k; row 0 is 0
+    rate_coeff: np.ndarray | None = None       # rates: (m_max + 1, nb) complex D_k; row 0 / mass is the mean angular velocity
+    pattern_speed: np.ndarray | None = None    # rates: (m_max + 1, nb) Re(D_k / A_k); NaN for k = 0 or A_k = 0
+    planes: np.ndarray | None = None           # raw=True: the int64 sums (P, nb + 2) ...
+    exponents: np.ndarray | None = None        # ... and the two exponents {A, D}: value = planes * 2^-exponent
+    _units: np.ndarray | None = field(default=None, repr=False)       # the planes, kept for total()
+    _exp: tuple = field(default=(0, 0), repr=False)
+
+    @property
+    def rates(self) -> bool:
+        return self.rate_coeff is not None
+
+    def total(self, k: int = 2, r_min=None, r_max=None) -> BhModeTotal:
+        """Amplitude, phase and pattern speed of harmonic k of the COHERENT sum -- the integer planes added, then converted --
+        over the bins whose two edges lie in [r_min, r_max] (None: from the first edge, to the last): the global bar strength
+        for k = 2.  The bodies inside edges[0] and beyond edges[nb] are not part of it."""
+        k = int(k)
+        if not 0 <= k <= self.m_max:
+            raise ValueError(f"k must be 0 .. m_max = {self.m_max}")
+        lo = -np.inf if r_min is None else float(r_min)
+        hi = np.inf if r_max is None else float(r_max)
+        sel = np.concatenate([[False], (self.edges[:-1] >= lo) & (self.edges[1:] <= hi), [False]])
+        n_a = 1 + 2 * self.m_max
+
+        def summed(p, e):
+            return float(np.ldexp(float(sum(int(v) for v in self._units[p][sel])), -e))
+
+        e_a, e_d = self._exp
+        a0 = summed(0, e_a)
+        re_a, im_a = (a0, 0.0) if k == 0 else (summed(2 * k - 1, e_a), summed(2 * k, e_a))
+        re_d = im_d = None
+        if self.rates and k > 0:
+            re_d, im_d = summed(n_a + 2 * k - 1, e_d), summed(n_a + 2 * k, e_d)
+        amp, phase, speed = _mode_numbers(np.float64(re_a), np.float64(im_a), np.float64(a0), re_d, im_d, k)
+        return BhModeTotal(float(amp), float(phase), float(speed))
+
+    @staticmethod
+    def pattern_speed_between(a: "BhAzimuthalModes", b: "BhAzimuthalModes", dt: float, k: int = 2, r_min=None, r_max=None) -> float:
+        """The mean pattern speed of harmonic k between two results a time dt apart: the difference of the phases of their
+        total(k, r_min, r_max), b's minus a's, unwrapped into (-pi / k, pi / k], over dt.  A pattern that turns
+        by pi / k or more in dt cannot be followed."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        period = 2.0 * math.pi / k
+        d = math.remainder(b.total(k, r_min, r_max).phase - a.total(k, r_min, r_max).phase, period)
+        if d <= -0.5 * period:
+            d += period
+        return d / float(dt)
+
+
+def azimuthal_modes_from_planes(planes, exponents, edges, m_max: int, rates: bool, centre, centre_velocity=(0.0, 0.0),
+                                raw: bool = False) -> BhAzimuthalModes:
+    """BhAzimuthalModes of the int64 sums (P, nb + 2), P = modes_planes(m_max, rates), and their two exponents."""
+    planes = np.asarray(planes, dtype=np.int64)
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1).copy()
+    nb, M, rates = len(edges) - 1, int(m_max), bool(rates)
+    if planes.shape != (modes_planes(M, rates), nb + 2):
+        raise ValueError("planes must be (modes_planes(m_max, rates), nb + 2)")
+    e_a, e_d = (int(x) for x in exponents)
+    n_a = 1 + 2 * M
+
+    def complex_rows(first, e):
+        val = np.ldexp(planes[first:first + n_a].astype(np.float64), -e)
+        out = np.zeros((M + 1, nb + 2), dtype=np.complex128)
+        out[0] = val[0]
+        out[1:] = val[1::2] + 1j * val[2::2]
+        return out
+
+    a_all = complex_rows(0, e_a)
+    a = a_all[:, 1:-1]
+    mass = a[0].real.copy()
+    d = complex_rows(n_a, e_d)[:, 1:-1] if rates else None
+    amp, phase, speed = np.zeros((M + 1, nb)), np.zeros((M + 1, nb)), np.full((M + 1, nb), np.nan)
+    for k in range(M + 1):
+        amp[k], phase[k], speed[k] = _mode_numbers(a[k].real, a[k].imag, mass, d[k].real if rates else None,
+                                                   d[k].imag if rates else None, k)
+    return BhAzimuthalModes(edges, tuple(float(x) for x in centre), tuple(float(x) for x in centre_velocity), M,
+                            planes[-1, 1:-1].copy(), mass, float(a_all[0, 0].real), float(a_all[0, -1].real), a.copy(), amp, phase,
+                            d.copy() if rates else None, speed if rates else None, planes if raw else None,
+                            np.array([e_a, e_d], dtype=np.int32) if raw else None, planes, (e_a, e_d))
 
 
 @dataclass
@@ -1105,6 +1247,54 @@ class BarnesHutEngine:
         a, b, r = C.c_double(), C.c_double(), np.zeros(8)
         self._check(self._lib.bh_radial_times(self._h, C.byref(a), C.byref(b), _dptr(r)))
         return a.value, b.value, r
+
+    # -- azimuthal modes --------------------------------------------------------------------------
+    def azimuthal_modes(self, edges, m_max: int = 4, centre="density", centre_velocity=None, rates: bool = False,
+                        raw: bool = False) -> BhAzimuthalModes:
+        """The azimuthal Fourier coefficients A_k = sum m exp(i k phi), k = 0 .. m_max, of the current state in the bins between
+        `edges` (nb + 1 ascending radii, see radial_edges) about `centre` ("density", "com" or a pair): relative amplitude
+        (k = 2: the bar strength) and phase per bin, and with rates=True the sums D_k = sum m w exp(i k phi) and the
+        instantaneous pattern speed Re(D_k / A_k), velocities relative to centre_velocity (default 0).  Summed on the device in
+        fixed point without a trigonometric function: the same bodies give the same bits in any order.  pattern_speed holds
+        the membership of a bin fixed: exact for the sum over all slots and for a rigid pattern, it ignores the flux of bodies
+        across the edges of a single narrow bin (see BhAzimuthalModes).  Reads the state only; the run is not perturbed.
+        raw: also the int64 planes and their two exponents."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb, M, rates = len(ed) - 1, int(m_max), bool(rates)
+        ok = 1 <= nb <= MODES_MAX_BINS and 0 <= M <= MODES_MAX_M   # (else the call refuses before it writes)
+        planes = np.zeros((modes_planes(M, rates), nb + 2) if ok else (1, 3), dtype=np.int64)
+        e = np.zeros(2, dtype=np.int32)
+        self._check(self._lib.bh_azimuthal_modes(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, nb, M, int(rates),
+                                                 planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        return azimuthal_modes_from_planes(planes, e, ed, M, rates, c, u, raw)
+
+    def modes_max(self, centre, centre_velocity=None, m_max: int = 4, rates: bool = False) -> np.ndarray:
+        """{maxA, maxD}: the largest |m c_k|, |m s_k| and (rates) |m w c_k|, |m w s_k| over this context's bodies and k = 0 ..
+        m_max about the pair `centre` (zeros without bodies; maxD = 0 without rates)."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        m = np.zeros(2)
+        self._check(self._lib.bh_modes_max(self._h, _dptr(c), _dptr(u), int(m_max), int(bool(rates)), _dptr(m)))
+        return m
+
+    def modes_deposit(self, edges, centre, centre_velocity, exponents, m_max: int = 4, rates: bool = False) -> int:
+        """Device pointer of the int64 planes modes_planes(m_max, rates) x (nb + 2): this context's bodies summed with the
+        caller's two exponents (modes_exponents); valid until the next modes call."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+        if len(e) != 2:
+            raise ValueError("two exponents")
+        p = C.c_void_p()
+        self._check(self._lib.bh_modes_deposit(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, len(ed) - 1, int(m_max),
+                                               int(bool(rates)), e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p)))
+        return p.value
+
+    def modes_times(self):
+        """(max_ms, deposit_ms) of the last modes call: HIP events around the first pass and around the deposit."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._lib.bh_modes_times(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # -- neighbours -----------------------------------------------------------------------------
     def _query_points(self, points):

@@ -86,7 +86,10 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      pairs_randoms: int | None = None, pairs_seed: int = 0, mst_file: str | None = None,
                      segregation_file: str | None = None, segregation_massive: int | None = None, segregation_random: int = 500,
                      segregation_seed: int = 0, binaries_file: str | None = None, binaries_separation: float | None = None,
-                     encounters_file: str | None = None, encounters_radius: float | None = None):
+                     encounters_file: str | None = None, encounters_radius: float | None = None,
+                     modes_file: str | None = None, modes_bins: int | None = None, modes_max: int = 4, modes_range=None,
+                     modes_spacing: str = "log", modes_centre="density", bar_file: str | None = None, bar_mode: int = 2,
+                     bar_every: int = 0, bar_range=None, bar_centre="density"):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -144,6 +147,14 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     (BarnesHutEngine.neighbours_within(encounters_radius).pairs()): the line `# i,j,r`, then one row per pair of bodies no
     farther apart than encounters_radius (%.17g), i < j, ascending in (i, j): the two body indices and their separation
     sqrt(d2).  Not part of gpu_parallel_duration_us.
+    modes_file: after the last step, also write the azimuthal Fourier modes of the final state
+    (BarnesHutEngine.azimuthal_modes(edges, modes_max, modes_centre)) in modes_bins bins, modes_spacing "log" or "linear", over
+    modes_range (None: as profile_range): the line `# r_lo,r_hi,count,mass,amp_1,phase_1,...,amp_M,phase_M`, then one row per
+    bin (%.17g; nan in a bin without mass).  Not part of gpu_parallel_duration_us.
+    bar_file: also write the strength of harmonic bar_mode of the state with the cadence rules of energy_file (bar_every), one
+    line each: `step,t,cx,cy,amplitude,phase,pattern_speed` (%.17g) -- BarnesHutEngine.azimuthal_modes(..., rates=True)
+    .total(bar_mode) of the one bin over bar_range = (rmin, rmax) about bar_centre (range None: from 0 out to just beyond the
+    farthest body); velocities relative to a centre at rest.  Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -163,6 +174,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("profile_file and profile_bins go together")
     if pairs_file is not None and (pairs_bins is None or pairs_range is None):
         raise ValueError("pairs_file needs pairs_bins and pairs_range")
+    if (modes_file is None) != (modes_bins is None):
+        raise ValueError("modes_file and modes_bins go together")
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -190,6 +203,9 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         lagrange = None
         if lagrange_file is not None:
             lagrange = open(os.path.join(out_dir, lagrange_file) if not os.path.isabs(lagrange_file) else lagrange_file, "w")
+        bar = None
+        if bar_file is not None:
+            bar = open(os.path.join(out_dir, bar_file) if not os.path.isabs(bar_file) else bar_file, "w")
         done = 0
         # (file, steps between its lines, what writes a line)
         samplers = []
@@ -208,12 +224,20 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             lr = eng.lagrangian_radii(lagrange_fractions, lagrange_centre)
             lagrange.write(",".join([str(done)] + ["%.17g" % v for v in (done * delta_t, *lr.centre, *lr.r)]) + "\n")
 
+        def sample_bar():
+            centre = eng.centre_of(bar_centre)
+            edges = profile_edges(1, bar_range, "linear", eng.download()[0] if bar_range is None else None, centre)
+            t = eng.azimuthal_modes(edges, bar_mode, centre, rates=True).total(bar_mode)
+            bar.write(",".join([str(done)] + ["%.17g" % v for v in (done * delta_t, *centre, t.amplitude, t.phase, t.pattern_speed)]) + "\n")
+
         if energy is not None:
             samplers.append((energy_every, sample_energy))
         if ferr is not None:
             samplers.append((force_error_every, sample_force_error))
         if lagrange is not None:
             samplers.append((lagrange_every, sample_lagrange))
+        if bar is not None:
+            samplers.append((bar_every, sample_bar))
 
         advance_engine = eng.step if integrator == "euler" else eng.step_kdk
 
@@ -298,6 +322,15 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, profile_file) if not os.path.isabs(profile_file) else profile_file, "w") as f:
                 f.write("# r_lo,r_hi,count,sigma,vr,vt,sigma_r,sigma_t\n")
                 f.write("".join("%.17g,%.17g,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(*cols)))
+        if modes_file is not None:
+            centre = eng.centre_of(modes_centre)
+            md = eng.azimuthal_modes(profile_edges(modes_bins, modes_range, modes_spacing, pos, centre), modes_max, centre)
+            cols = [md.edges[:-1], md.edges[1:], md.count, md.mass]
+            for k in range(1, md.m_max + 1):
+                cols += [md.amplitude[k], md.phase[k]]
+            with open(os.path.join(out_dir, modes_file) if not os.path.isabs(modes_file) else modes_file, "w") as f:
+                f.write("# r_lo,r_hi,count,mass" + "".join(",amp_%d,phase_%d" % (k, k) for k in range(1, md.m_max + 1)) + "\n")
+                f.write("".join(("%.17g,%.17g,%d" + ",%.17g" * (1 + 2 * md.m_max) + "\n") % r for r in zip(*cols)))
         if pairs_file is not None:
             edges = radial_edges(float(pairs_range[0]), float(pairs_range[1]), int(pairs_bins), pairs_spacing)
             with open(os.path.join(out_dir, pairs_file) if not os.path.isabs(pairs_file) else pairs_file, "w") as f:
@@ -333,7 +366,7 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                 f.write("".join("%d,%d,%.17g\n" % r for r in zip(lo, hi, np.sqrt(d2))))
         if traj is not None:
             traj.close()
-        for f in (energy, ferr, lagrange):
+        for f in (energy, ferr, lagrange, bar):
             if f is not None:
                 f.close()
     return pos, vel, gpu_parallel_us
@@ -455,6 +488,24 @@ def _parse(argv):
     ap.add_argument("--profile-spacing", choices=["log", "linear"], default="log", help="spacing of the bin edges")
     ap.add_argument("--profile-centre", nargs="+", default=None, metavar="C",
                     help="density (the density centre, default), com (the centre of mass) or X Y")
+    ap.add_argument("--modes-file", default=None, metavar="PATH",
+                    help="also write r_lo,r_hi,count,mass,amp_1,phase_1,...,amp_M,phase_M (the azimuthal Fourier modes of the final "
+                         "state: relative amplitude and phase per harmonic) of the --modes-bins radial bins about --modes-centre")
+    ap.add_argument("--modes-bins", type=int, default=None, metavar="NB", help="bins of --modes-file (1 .. 4096)")
+    ap.add_argument("--modes-max", type=int, default=None, metavar="M", help="highest harmonic of --modes-file (0 .. 16, default 4)")
+    ap.add_argument("--modes-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
+                    help="radii of the first and the last edge (default: as --profile-range)")
+    ap.add_argument("--modes-spacing", choices=["log", "linear"], default="log", help="spacing of the bin edges")
+    ap.add_argument("--modes-centre", nargs="+", default=None, metavar="C", help="density (default), com or X Y")
+    ap.add_argument("--bar-file", default=None, metavar="PATH",
+                    help="also write step,t,cx,cy,amplitude,phase,pattern_speed (harmonic --bar-mode of the whole --bar-range: the "
+                         "bar strength) before the first step, every --bar-every steps and after the last")
+    ap.add_argument("--bar-mode", type=int, default=None, metavar="K", help="harmonic of --bar-file (1 .. 16, default 2)")
+    ap.add_argument("--bar-every", type=int, default=0, metavar="N",
+                    help="steps between two lines of --bar-file (0: first and last state only)")
+    ap.add_argument("--bar-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
+                    help="radii between which the bodies count (default: from 0 to just beyond the farthest body)")
+    ap.add_argument("--bar-centre", nargs="+", default=None, metavar="C", help="density (default), com or X Y")
     ap.add_argument("--lagrange-file", default=None, metavar="PATH",
                     help="also write step,t,cx,cy,r_f1,... (the centre and the radii that enclose the --lagrange-fractions of the "
                          "mass) before the first step, every --lagrange-every steps and after the last")
@@ -530,6 +581,25 @@ def _parse(argv):
         ap.error("--profile-range: 0 <= RMIN < RMAX, finite")
     if a.profile_range is not None and a.profile_spacing == "log" and a.profile_range[0] <= 0.0:
         ap.error("--profile-range: log spacing needs RMIN > 0")
+    if (a.modes_file is None) != (a.modes_bins is None):
+        ap.error("--modes-file and --modes-bins go together")
+    if a.modes_file is None and (a.modes_range is not None or a.modes_centre is not None or a.modes_max is not None):
+        ap.error("--modes-max, --modes-range and --modes-centre need --modes-file")
+    if a.modes_bins is not None and not 1 <= a.modes_bins <= 4096:
+        ap.error("--modes-bins: 1 .. 4096")
+    if a.modes_max is not None and not 0 <= a.modes_max <= 16:
+        ap.error("--modes-max: 0 .. 16")
+    for flag, rng in (("--modes-range", a.modes_range), ("--bar-range", a.bar_range)):
+        if rng is not None and not (0.0 <= rng[0] < rng[1] < float("inf")):
+            ap.error(flag + ": 0 <= RMIN < RMAX, finite")
+    if a.modes_range is not None and a.modes_spacing == "log" and a.modes_range[0] <= 0.0:
+        ap.error("--modes-range: log spacing needs RMIN > 0")
+    if a.bar_file is None and (a.bar_mode is not None or a.bar_every or a.bar_range is not None or a.bar_centre is not None):
+        ap.error("--bar-mode, --bar-every, --bar-range and --bar-centre need --bar-file")
+    if a.bar_mode is not None and not 1 <= a.bar_mode <= 16:
+        ap.error("--bar-mode: 1 .. 16")
+    if a.bar_every < 0:
+        ap.error("--bar-every: at least 0")
     if a.lagrange_file is None and (a.lagrange_fractions is not None or a.lagrange_centre is not None or a.lagrange_every):
         ap.error("--lagrange-fractions, --lagrange-every and --lagrange-centre need --lagrange-file")
     if a.lagrange_fractions is not None and (len(a.lagrange_fractions) > 32 or not all(0.0 < f <= 1.0 for f in a.lagrange_fractions)):
@@ -566,6 +636,8 @@ def _parse(argv):
         ap.error("--encounters-radius: finite and >= 0")
     a.profile_centre = _centre_arg(ap, "--profile-centre", a.profile_centre)
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
+    a.modes_centre = _centre_arg(ap, "--modes-centre", a.modes_centre)
+    a.bar_centre = _centre_arg(ap, "--bar-centre", a.bar_centre)
     if a.groups_min is not None and a.groups_min < 1:
         ap.error("--groups-min: at least 1")
     if a.linking_length is not None and not (a.linking_length >= 0.0 and a.linking_length < float("inf")):
@@ -643,7 +715,10 @@ def main(argv=None) -> int:
         pairs_seed=a.pairs_seed or 0, mst_file=a.mst_file, segregation_file=a.segregation_file,
         segregation_massive=a.segregation_massive, segregation_random=500 if a.segregation_random is None else a.segregation_random,
         segregation_seed=a.segregation_seed or 0, binaries_file=a.binaries_file, binaries_separation=a.binaries_separation,
-        encounters_file=a.encounters_file, encounters_radius=a.encounters_radius)
+        encounters_file=a.encounters_file, encounters_radius=a.encounters_radius, modes_file=a.modes_file,
+        modes_bins=a.modes_bins, modes_max=4 if a.modes_max is None else a.modes_max, modes_range=a.modes_range,
+        modes_spacing=a.modes_spacing, modes_centre=a.modes_centre, bar_file=a.bar_file,
+        bar_mode=2 if a.bar_mode is None else a.bar_mode, bar_every=a.bar_every, bar_range=a.bar_range, bar_centre=a.bar_centre)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

@@ -512,6 +512,51 @@ int bh_radial_select(bh_ctx *ctx, const double centre[2], int32_t exponent, int3
                      void **hist_dev);
 int bh_radial_times(bh_ctx *ctx, double *max_ms, double *main_ms, double rounds_ms[8]);
 
+/* --- azimuthal Fourier modes: bar strength, phase and pattern speed of a disc ------------------------------------------------
+ * What a radial profile loses by construction: A_k(bin) = sum over the bin's bodies of m exp(i k phi), k = 0 .. M, and with
+ * rates D_k(bin) = sum m w exp(i k phi), w the angular velocity of the body about the centre.  |A_k| / A_0 is the relative
+ * amplitude (k = 2: the bar strength), arg(A_k) / k the phase, Re(D_k / A_k) the instantaneous pattern speed.
+ * centre = {cx, cy}; centre_vel = {ucx, ucy} (NULL: 0).  Per body of the CURRENT state, in fp64 in the written order with
+ * nothing fused (an fp32 state is widened first, exactly):
+ *     dx = x - cx;  dy = y - cy;  r2 = dx * dx + dy * dy
+ *     r2 >= 2^-1022:  r = sqrt(r2);  c1 = dx / r;  s1 = dy / r
+ *     c_0 = 1;  s_0 = 0;  k = 1 .. M:  c_k = c_{k-1} * c1 - s_{k-1} * s1;  s_k = s_{k-1} * c1 + c_{k-1} * s1
+ *     r2 < 2^-1022 (zero or subnormal, no direction):  c_k = s_k = 0 for k >= 1, w = 0
+ *     rates:  ux = vx - ucx;  uy = vy - ucy;  b = dx * uy - dy * ux;  w = b / r2;  mw = m * w
+ *   The recurrence -- a complex multiplication by (c1 + i s1) -- IS the definition of cos k phi and sin k phi here: no
+ *   trigonometric function is called and nothing is renormalised, so the planes are a pure function of the set of bodies.
+ * Bins.  edges[nb + 1] under the rules of the radial profiles with BH_MODES_MAX_BINS; the same nb + 2 slots on r2.
+ * Planes.  planes[P][nb + 2], plane-major, P = (rates ? 2 : 1) * (1 + 2 M) + 1:
+ *     A-planes: m c_0, then m c_k, m s_k for k = 1 .. M;   D-planes (rates only): mw c_0, then mw c_k, mw s_k;   last: the count.
+ *   Fixed point of the moment maps with TWO exponents: a first pass runs the same recurrence and takes maxA, the largest
+ *   |m c_k| or |m s_k| over all bodies and all k (k = 0 gives |m|), and with rates maxD, the same with mw; exponents[0] = 62 -
+ *   E(maxA) - L for the A-planes, exponents[1] likewise from maxD for the D-planes (E the frexp exponent, L = ceil(log2(max(n,
+ *   1))) for the n bodies of the WHOLE system, 0 for a zero maximum; exponents[1] = 0 without rates).  A contribution is
+ *   (int64) rint(ldexp(q, exponent)), added with 64-bit integer atomics.  value = planes * 2^-exponent.
+ * 0 <= M <= BH_MODES_MAX_M; M = 0 is a mass profile.  Without rates the velocities are not read.
+ * bh_azimuthal_modes: both passes and the download.
+ * bh_modes_max: the first pass alone, maxabs = {maxA, maxD} over this context's bodies (0 without bodies or rates).
+ * bh_modes_deposit: the second pass alone with the caller's two exponents (a distributed call: the MAX of the ranks' maxima and
+ *   the SUM of their body counts give every rank the same exponents), the planes left on the device: *planes_dev points at
+ *   P * (nb + 2) int64, valid until the next modes call or bh_destroy.  Exponents too large for this context's own maxima and
+ *   body count are refused.
+ * bh_modes_times: HIP-event times of the last of these calls: the first pass, the deposit.
+ * Valid whenever the radial calls are: any time after bh_upload / bh_initialize / bh_migrate_unpack, in every precision, in
+ * LET mode too (the context's own bodies); they read the state only, build no tree and change nothing a step reads.  They
+ * wait for the stream.  The buffers are allocated on the first call.
+ * Errors: BH_ERR_ARG for a null pointer (centre_vel excepted), a centre or centre velocity that is not finite, M outside
+ *   0 .. BH_MODES_MAX_M, nb < 1 or > BH_MODES_MAX_BINS, bad edges (as the radial calls), and -- found by the first pass, with a
+ *   message that says so -- a body whose position, mass, velocity (with rates), r2 or any contribution is not finite (w
+ *   overflowing for a tiny r2 included).  Negative masses are allowed.  BH_ERR_STATE before any upload. */
+#define BH_MODES_MAX_M 16
+#define BH_MODES_MAX_BINS 4096
+int bh_azimuthal_modes(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *edges, int32_t nb, int32_t M,
+                       int32_t rates, int64_t *planes, int32_t exponents[2]);
+int bh_modes_max(bh_ctx *ctx, const double centre[2], const double centre_vel[2], int32_t M, int32_t rates, double maxabs[2]);
+int bh_modes_deposit(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *edges, int32_t nb, int32_t M,
+                     int32_t rates, const int32_t exponents[2], void **planes_dev);
+int bh_modes_times(bh_ctx *ctx, double *max_ms, double *deposit_ms);
+
 /* --- neighbours: which bodies are next to a body or a point, and how far away ------------------------------------------
  * Queries.  points == NULL: the queries are the n bodies in caller order and n_points must be n; body i is left out of its
  *   own answer by index -- another body at the same place is not: it is a neighbour at d2 = 0.  Otherwise points[n_points][2]
