@@ -11,7 +11,8 @@ from .engine import (BarnesHutEngine, BhConfig, BhError, BhForceError, BhGroups,
                      local_density_from, radial_edges, radial_exponents, radial_profile_from_planes,
                      BhMassSegregation, BhSpanningTree, mass_segregation_from, spanning_tree_from, BhBinaries, binaries_from_records,
                      BhNeighbourLists, neighbour_lists_from, BhAzimuthalModes, BhModeTotal, azimuthal_modes_from_planes,
-                     modes_exponents, modes_planes)
+                     modes_exponents, modes_planes, BhRotationCurve, BhResonances, rotation_curve_from_planes, toomre_q_from,
+                     resonances_from, disc_velocity_table_from, epicyclic_from)
 from .textio import loadSimulationDataFromText, save_init_files  # noqa: F401
 
 __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups", "BhMomentMap", "BhTimestep", "Precision",
@@ -20,4 +21,6 @@ __all__ = ["BarnesHutEngine", "BhConfig", "BhError", "BhForceError", "BhGroups",
            "radial_profile_from_planes", "lagrangian_from", "BhPairCounts", "correlation_from", "BhSortSnapshot",
            "BhSpanningTree", "BhMassSegregation", "mass_segregation_from", "spanning_tree_from",
            "BhBinaries", "binaries_from_records", "BhNeighbourLists", "neighbour_lists_from",
-           "BhAzimuthalModes", "BhModeTotal", "azimuthal_modes_from_planes", "modes_exponents", "modes_planes"]
+           "BhAzimuthalModes", "BhModeTotal", "azimuthal_modes_from_planes", "modes_exponents", "modes_planes",
+           "BhRotationCurve", "BhResonances", "rotation_curve_from_planes", "toomre_q_from", "resonances_from",
+           "disc_velocity_table_from", "epicyclic_from"]

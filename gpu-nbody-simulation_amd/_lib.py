@@ -118,6 +118,7 @@ SIGNATURES = {
     "bh_drift": (C.c_int, [_ctx, C.c_double]),
     "bh_timestep": (C.c_int, [_ctx, C.c_double, C.c_double, C.POINTER(bh_timestep_t)]),
     "bh_step_kdk": (C.c_int, [_ctx, C.c_int32]),
+    "bh_forces_current": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "bh_moment_map": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64)]),
     "bh_moment_map_max": (C.c_int, [_ctx, _dp]),
@@ -135,6 +136,10 @@ SIGNATURES = {
     "bh_modes_max": (C.c_int, [_ctx, _dp, _dp, C.c_int32, C.c_int32, _dp]),
     "bh_modes_deposit": (C.c_int, [_ctx, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp)]),
     "bh_modes_times": (C.c_int, [_ctx, _dp, _dp]),
+    "bh_initialize_disc": (C.c_int, [_ctx, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_double]),
+    "bh_rotation_curve": (C.c_int, [_ctx, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "bh_set_disc_velocities": (C.c_int, [_ctx, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_uint64]),
+    "bh_disc_times": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "bh_neighbours": (C.c_int,[_ctx, _dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint32)]),
     "bh_count_within": (C.c_int, [_ctx, _dp, C.c_int64, C.c_double, C.POINTER(C.c_uint32)]),
     "bh_neighbours_times": (C.c_int, [_ctx, _dp, _dp]),

@@ -31,6 +31,7 @@
 #include "bh_moments.hpp"
 #include "bh_radial.hpp"
 #include "bh_modes.hpp"
+#include "bh_disc.hpp"
 #include "bh_neighbours.hpp"
 #include "bh_neighbour_lists.hpp"
 #include "bh_pairs.hpp"
@@ -172,6 +173,7 @@ struct bh_ctx : RunState {   // (is / carry / last and their events: bh_run_stat
     MapState map;
     RadState rad;
     ModState mod;
+    DiscState disc;
     FieldState field;
     NbState nb;
     PairState pair;
@@ -1119,7 +1121,7 @@ void bh_destroy(bh_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     auto destroy = [](auto &evs) { for (auto e : evs) if (e) (void)hipEventDestroy(e); };
     destroy(c->ev); destroy(c->ev_step); destroy(c->ev_build); destroy(c->ev_grp); destroy(c->ev_let); destroy(c->nb.ev);
-    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mod.ev); destroy(c->mst.ev); destroy(c->bin.ev); destroy(c->nbl.ev);
+    destroy(c->fof.ev); destroy(c->rad.ev); destroy(c->mod.ev); destroy(c->disc.ev); destroy(c->mst.ev); destroy(c->bin.ev); destroy(c->nbl.ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1354,6 +1356,13 @@ static int need_forces(bh_ctx *c, const char *what)
                                  "(bh_compute_forces first; a step, bh_drift, bh_upload, bh_build_tree and a new softening length outdate them)");
 }
 
+int bh_forces_current(bh_ctx *c, int32_t *current)
+{
+    if (!c || !current) return fail(c, BH_ERR_ARG, "bh_forces_current: null argument");
+    *current = c->is.forces_current ? 1 : 0;
+    return BH_OK;
+}
+
 // v += a h on the force buffer; h == 0 launches nothing
 static int enqueue_kick(bh_ctx *c, double h)
 {
@@ -1522,6 +1531,186 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
     BH_HIP(c, hipSetDevice(c->device));
     BH_HIP(c, hipStreamSynchronize(c->stream));
     return counts_to_caller_order(c, c->body_counts, out);
+}
+
+// ---- the disc (bh_disc.hpp): initial conditions, the rotation curve's sums, velocities about a table.  The curve reads pos, mass
+// and the force buffer as they lie in memory (slot for slot) and writes buffers of its own; the velocities write vel alone: no
+// record of bh_run_state.hpp changes on either, as on bh_kick.
+}  // extern "C"
+
+namespace {
+
+int disc_alloc(bh_ctx *c)
+{
+    DiscState &s = c->disc;
+    if (s.max) return BH_OK;
+    return alloc_all(c, {part(&s.max, 1), part(&s.e2, (size_t)kDiscMaxBins + 1), part(&s.tables, (size_t)kDiscTables * kDiscMaxTable),
+                         part(&s.planes, (size_t)(kDiscPlanes + 1) * (kDiscMaxBins + 2))});
+}
+
+// f(pos, mass, force) as the precision types them: the force buffer holds fp32 accelerations unless the tree is fp64
+template <typename F>
+void curve_ptrs(const bh_ctx *c, F &&f)
+{
+    switch (c->mode) {
+    case Mode::F32: f((const float2 *)c->pos, (const float *)c->mass, (const float2 *)c->force); break;
+    case Mode::Mixed: f((const double2 *)c->pos, (const double *)c->mass, (const float2 *)c->force); break;
+    case Mode::F64:
+    case Mode::Exact: f((const double2 *)c->pos, (const double *)c->mass, (const double2 *)c->force); break;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bh_initialize_disc(bh_ctx *c, int64_t n, uint64_t seed, double mass, double scale, double r_max)
+{
+    if (!c) return BH_ERR_ARG;
+    if (n < 0 || n > c->cfg.capacity)
+        return fail(c, BH_ERR_ARG, "Requested number of bodies exceeds N_BODIES.");
+    if (!(std::isfinite(scale) && scale > 0)) return fail(c, BH_ERR_ARG, "bh_initialize_disc: scale must be finite and > 0");
+    if (!(r_max > 0)) return fail(c, BH_ERR_ARG, "bh_initialize_disc: truncation radius r_max must be > 0 (+inf: none)");
+    if (!std::isfinite(mass)) return fail(c, BH_ERR_ARG, "bh_initialize_disc: mass must be finite");
+    BH_HIP(c, hipSetDevice(c->device));
+    DiscState &s = c->disc;
+    s.init_ms = 0.0;
+    s.init_pending = false;
+    if (n > 0) {
+        const double F = std::isinf(r_max) ? 1.0 : 1.0 - scale / std::sqrt(r_max * r_max + scale * scale);
+        const double m = mass / (double)n;
+        if (int rc = mark(c, s.ev[0])) return rc;
+        with_state(c, [&](auto r2) {
+            using Real2 = decltype(r2);
+            using Real = decltype(r2.x);
+            hipLaunchKernelGGL((disc_init_kernel<Real2, Real>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, (Real2 *)c->pos,
+                               (Real2 *)c->vel, (Real *)c->mass, n, seed, scale, F, m);
+        });
+        BH_HIP(c, hipGetLastError());
+        if (int rc = mark(c, s.ev[1])) return rc;
+        s.init_pending = true;
+    }
+    BH_HIP(c, hipMemsetAsync(c->force, 0, force_bytes(c, n), c->stream));
+    return upload_done(c, n);
+}
+
+int bh_rotation_curve(bh_ctx *c, const double *centre, const double *edges, int32_t nb, int64_t *planes, int32_t *exponents)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_rotation_curve: null argument");
+    DiscState &s = c->disc;
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = rad_centre(c, "bh_rotation_curve", centre, nullptr, &ctr)) return rc;
+    if (!edges) return fail(c, BH_ERR_ARG, "bh_rotation_curve: null edges");
+    const unsigned why = squared_edges(edges, nb, kDiscMaxBins, e2);
+    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, "bh_rotation_curve: nb must be 1 .. BH_DISC_MAX_BINS = " + std::to_string(kDiscMaxBins));
+    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, "bh_rotation_curve: an edge or its square is not finite");
+    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, "bh_rotation_curve: the edges must be >= 0");
+    if (why) return fail(c, BH_ERR_ARG, "bh_rotation_curve: the edges and their squares must be strictly ascending");
+    if (int rc = split_check(c, "bh_rotation_curve")) return rc;
+    if (int rc = need_forces(c, "bh_rotation_curve")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = disc_alloc(c)) return rc;
+    const int S = nb + 2;
+    s.max_ms = s.deposit_ms = 0.0;
+    double maxabs[kDiscPlanes] = {0.0, 0.0, 0.0, 0.0};
+    if (c->n > 0) {
+        if (int rc = mark(c, s.ev[2])) return rc;
+        BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(DiscMax), c->stream));
+        curve_ptrs(c, [&](auto pos, auto mass, auto force) {
+            hipLaunchKernelGGL((curve_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>), dim3(rad_grid(c)),
+                               dim3(kBlock), 0, c->stream, pos, mass, force, c->n, ctr, s.max);
+        });
+        BH_HIP(c, hipGetLastError());
+        if (int rc = mark(c, s.ev[3])) return rc;
+        DiscMax r{};
+        if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
+        if (int rc = span_ms(c, s.ev[2], s.ev[3], &s.max_ms)) return rc;
+        if (r.bad)
+            return fail(c, BH_ERR_ARG, "bh_rotation_curve: a body has a non-finite position, mass or acceleration (a massless body of an "
+                                       "fp64 tree: 0 / 0), or a squared radius or a contribution m r, m (x . a), m (x x a) that overflows fp64");
+    }
+    int32_t e[kDiscPlanes];
+    for (int p = 0; p < kDiscPlanes; ++p) e[p] = plane_exponent(maxabs[p], log2_ceil(c->n));
+    if (int rc = mark(c, s.ev[4])) return rc;
+    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)(kDiscPlanes + 1) * S * sizeof(long long), c->stream));
+    if (c->n > 0) {
+        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        DiscExp ex{};
+        for (int p = 0; p < kDiscPlanes; ++p) ex.e[p] = e[p];
+        const size_t lds = ((size_t)(kDiscPlanes + 1) * S + (size_t)nb + 1) * 8;
+        curve_ptrs(c, [&](auto pos, auto mass, auto force) {
+            hipLaunchKernelGGL((curve_deposit_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>),
+                               dim3(rad_grid(c)), dim3(kBlock), lds, c->stream, pos, mass, force, c->n, ctr, s.e2, (int)nb, ex, s.planes);
+        });
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, s.ev[5])) return rc;
+    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
+    if (int rc = span_ms(c, s.ev[4], s.ev[5], &s.deposit_ms)) return rc;
+    BH_HIP(c, hipMemcpy(planes, s.planes, (size_t)(kDiscPlanes + 1) * S * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kDiscPlanes, exponents);
+    return BH_OK;
+}
+
+int bh_set_disc_velocities(bh_ctx *c, const double *centre, const double *centre_vel, const double *radii, const double *vt,
+                           const double *sigma_r, const double *sigma_t, int32_t k, uint64_t seed)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!radii || !vt || !sigma_r || !sigma_t) return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: null table");
+    RadCentre ctr{};
+    if (int rc = rad_centre(c, "bh_set_disc_velocities", centre, centre_vel, &ctr)) return rc;
+    if (k < 1 || k > kDiscMaxTable)
+        return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: k must be 1 .. BH_DISC_MAX_TABLE = " + std::to_string(kDiscMaxTable));
+    std::vector<double> tab((size_t)kDiscTables * k);
+    for (int32_t j = 0; j < k; ++j) {
+        const double r = radii[j], r2 = r * r;
+        if (!(std::isfinite(r) && std::isfinite(r2) && r >= 0.0))
+            return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: a radius (or its square) is not finite or is negative");
+        if (j > 0 && !(radii[j - 1] < r && tab[(size_t)j - 1] < r2))
+            return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: the radii and their squares must be strictly ascending");
+        if (!(std::isfinite(vt[j]) && std::isfinite(sigma_r[j]) && std::isfinite(sigma_t[j])))
+            return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: a table entry is not finite");
+        if (sigma_r[j] < 0.0 || sigma_t[j] < 0.0) return fail(c, BH_ERR_ARG, "bh_set_disc_velocities: a dispersion is negative");
+        tab[(size_t)j] = r2; tab[(size_t)k + j] = r; tab[(size_t)2 * k + j] = vt[j]; tab[(size_t)3 * k + j] = sigma_r[j];
+        tab[(size_t)4 * k + j] = sigma_t[j];
+    }
+    if (int rc = split_check(c, "bh_set_disc_velocities")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = disc_alloc(c)) return rc;
+    DiscState &s = c->disc;
+    s.vel_ms = 0.0;
+    if (c->n == 0) return BH_OK;
+    if (int rc = mark(c, s.ev[6])) return rc;
+    BH_HIP(c, hipMemcpyAsync(s.tables, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const uint32_t *orig = (c->tree64() || c->is.orig_identity) ? nullptr : c->orig;
+    with_state(c, [&](auto r2) {
+        using Real2 = decltype(r2);
+        hipLaunchKernelGGL((disc_velocities_kernel<Real2>), dim3(rad_grid(c)), dim3(kBlock), tab.size() * sizeof(double), c->stream,
+                           (const Real2 *)c->pos, (Real2 *)c->vel, orig, c->n, ctr, seed, s.tables, (int)k);
+    });
+    BH_HIP(c, hipGetLastError());
+    if (int rc = mark(c, s.ev[7])) return rc;
+    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (tab lives on this stack until the copy has run)
+    return span_ms(c, s.ev[6], s.ev[7], &s.vel_ms);
+}
+
+int bh_disc_times(bh_ctx *c, double *init_ms, double *curve_max_ms, double *curve_deposit_ms, double *velocities_ms)
+{
+    if (!c || !init_ms || !curve_max_ms || !curve_deposit_ms || !velocities_ms) return fail(c, BH_ERR_ARG, "bh_disc_times: null argument");
+    DiscState &s = c->disc;
+    if (s.init_pending) {                                          // bh_initialize_disc does not wait for its kernel: this does
+        BH_HIP(c, hipSetDevice(c->device));
+        BH_HIP(c, hipStreamSynchronize(c->stream));
+        if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.init_ms)) return rc;
+        s.init_pending = false;
+    }
+    *init_ms = s.init_ms;
+    *curve_max_ms = s.max_ms;
+    *curve_deposit_ms = s.deposit_ms;
+    *velocities_ms = s.vel_ms;
+    return BH_OK;
 }
 
 // ---- diagnostics (bh_diag.hpp): potential walk and reductions

@@ -44,6 +44,17 @@ struct ModState {
     double max_ms = 0.0, deposit_ms = 0.0;                      // of the last call (bh_modes_times)
 };
 
+// the disc (bh_disc.hpp): the rotation curve's first-pass record, squared edges and 5-plane int64 sums of up to
+// BH_DISC_MAX_BINS + 2 slots, and the five tables of bh_set_disc_velocities; the launch shape is the radial kernels' (rad.blocks)
+struct DiscState {
+    DiscMax *max = nullptr;
+    double *e2 = nullptr, *tables = nullptr;
+    long long *planes = nullptr;
+    hipEvent_t ev[8] = {};                                      // around the initialiser, the first pass, the deposit, the velocities
+    bool init_pending = false;                                  // ev[0], ev[1] are recorded and not yet read (bh_initialize_disc does not wait)
+    double init_ms = 0.0, max_ms = 0.0, deposit_ms = 0.0, vel_ms = 0.0;     // of the last call of each (bh_disc_times)
+};
+
 // the field at arbitrary points (bh_field.hpp): one block for a launch of up to block.cap points -- the points, their results, two
 // key arrays and the sorted order, the sort's count matrix and row totals
 struct FieldState {

@@ -481,6 +481,135 @@ def azimuthal_modes_from_planes(planes, exponents, edges, m_max: int, rates: boo
                             np.array([e_a, e_d], dtype=np.int32) if raw else None, planes, (e_a, e_d))
 
 
+DISC_MAX_BINS = 1022                    # BH_DISC_MAX_BINS
+DISC_MAX_TABLE = 1024                   # BH_DISC_MAX_TABLE
+TOOMRE_STELLAR = 3.36                   # Toomre (1964): Q = sigma_R kappa / (3.36 G Sigma) for a stellar disc
+
+
+@dataclass
+class BhRotationCurve:
+    """The rotation curve of the engine's own forces about a centre on the nb bins between edges (rotation_curve): fp64 arrays
+    (nb,) unless said otherwise.  mass and torque are the fixed-point sums times 2^-exponent, the others are derived from them,
+    NaN in a bin where they are not defined."""
+    edges: np.ndarray            # (nb + 1,)
+    count: np.ndarray            # bodies per bin, int64
+    mass: np.ndarray             # sum m
+    radius: np.ndarray           # sum m r / sum m: the radius the bin's numbers belong to
+    vc2: np.ndarray              # - sum m (x . a) / sum m: the squared circular speed (negative where the force points outwards)
+    vc: np.ndarray               # sqrt(max(vc2, 0))
+    omega: np.ndarray            # vc / radius
+    kappa: np.ndarray            # epicyclic frequency: omega sqrt(clip(4 + d ln omega^2 / d ln radius, 1, 4)), see epicyclic_from
+    torque: np.ndarray           # sum m (x cross a): the gravitational torque on the bin
+    torque_cumulative: np.ndarray    # (nb + 1,): the torque on everything inside every edge, summed in integers
+    mass_inside: float           # inside edges[0] ...
+    mass_outside: float          # ... and at or beyond edges[nb]
+    count_inside: int
+    count_outside: int
+    centre: tuple
+    planes: np.ndarray | None = None      # raw=True: the int64 sums (5, nb + 2), plane 4 the counts ...
+    exponents: np.ndarray | None = None   # ... and the four exponents: value = planes * 2^-exponent
+
+
+class BhResonances(NamedTuple):
+    """The radii where a pattern speed meets the disc's frequencies (resonances_from)."""
+    corotation: np.ndarray       # omega = pattern speed
+    inner: np.ndarray            # omega - kappa / m = pattern speed: inner Lindblad resonances
+    outer: np.ndarray            # omega + kappa / m = pattern speed: outer Lindblad resonance
+
+
+def _dlog(y, x) -> np.ndarray:
+    """d ln y / d ln x by np.gradient over the (unevenly spaced) points; needs two points at least."""
+    return np.gradient(np.log(y), np.log(x))
+
+
+def epicyclic_from(radius, omega) -> np.ndarray:
+    """kappa from kappa^2 = omega^2 clip(4 + d ln omega^2 / d ln radius, 1, 4) (between a Keplerian and a rigid curve), the
+    derivative by np.gradient over the points given: all of them need radius > 0 and omega > 0, and there are two at least."""
+    radius, omega = np.asarray(radius, dtype=np.float64), np.asarray(omega, dtype=np.float64)
+    return omega * np.sqrt(np.clip(4.0 + _dlog(omega * omega, radius), 1.0, 4.0))
+
+
+def rotation_curve_from_planes(planes, exponents, edges, centre, raw: bool = False) -> BhRotationCurve:
+    """BhRotationCurve of the int64 sums (5, nb + 2) and their four exponents.  kappa takes its derivative over the bins that
+    have mass and vc2 > 0 (NaN in the others, and everywhere when fewer than two have)."""
+    planes = np.asarray(planes, dtype=np.int64)
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1).copy()
+    nb = len(edges) - 1
+    if planes.shape != (5, nb + 2):
+        raise ValueError("planes must be (5, nb + 2)")
+    e = [int(x) for x in exponents]
+    val = [np.ldexp(planes[p].astype(np.float64), -e[p]) for p in range(4)]
+    mass, mr, mxa, torque = (v[1:-1] for v in val)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        radius, vc2 = mr / mass, -mxa / mass
+        vc = np.sqrt(np.maximum(vc2, 0.0))
+        omega = vc / radius
+    empty = mass == 0.0
+    for a in (radius, vc2, vc, omega):
+        a[empty] = np.nan
+    good = ~empty & (vc2 > 0.0) & (radius > 0.0) & np.isfinite(omega)
+    kappa = np.full(nb, np.nan)
+    if good.sum() >= 2:
+        kappa[good] = epicyclic_from(radius[good], omega[good])
+    cumulative = np.ldexp(np.cumsum(planes[3, :-1]).astype(np.float64), -e[3])        # (integer sums: |total| <= 2^62)
+    return BhRotationCurve(edges, planes[4, 1:-1].copy(), mass, radius, vc2, vc, omega, kappa, torque, cumulative, float(val[0][0]),
+                           float(val[0][-1]), int(planes[4, 0]), int(planes[4, -1]), tuple(float(x) for x in centre),
+                           planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+
+
+def toomre_q_from(curve: BhRotationCurve, profile: BhRadialProfile, G: float) -> np.ndarray:
+    """Toomre's Q = sigma_R kappa / (3.36 G Sigma) per bin from the curve and the radial profile of the same edges and centre;
+    NaN where kappa, the dispersion or a positive surface density is missing."""
+    if len(curve.edges) != len(profile.edges) or not np.array_equal(curve.edges, profile.edges):
+        raise ValueError("the curve and the profile must share their edges")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = profile.sigma_r * curve.kappa / (TOOMRE_STELLAR * float(G) * profile.sigma)
+    q[~(profile.sigma > 0.0) | ~np.isfinite(q)] = np.nan
+    return q
+
+
+def _crossings(x, f, level: float) -> np.ndarray:
+    """Where the broken line through (x, f) meets `level`: a point on it counts once."""
+    out = []
+    d = f - level
+    for i in range(len(x)):
+        if d[i] == 0.0:
+            out.append(x[i])
+        elif i + 1 < len(x) and d[i] * d[i + 1] < 0.0:
+            out.append(x[i] + (x[i + 1] - x[i]) * (d[i] / (d[i] - d[i + 1])))
+    return np.array(out, dtype=np.float64)
+
+
+def resonances_from(curve: BhRotationCurve, pattern_speed: float, m: int = 2) -> BhResonances:
+    """The radii where omega (corotation), omega - kappa / m (inner) and omega + kappa / m (outer Lindblad resonance) cross
+    pattern_speed, by linear interpolation between the radii of neighbouring bins that have a kappa."""
+    ok = np.isfinite(curve.kappa) & np.isfinite(curve.omega) & np.isfinite(curve.radius)
+    r, w, k = curve.radius[ok], curve.omega[ok], curve.kappa[ok] / float(m)
+    p = float(pattern_speed)
+    return BhResonances(_crossings(r, w, p), _crossings(r, w - k, p), _crossings(r, w + k, p))
+
+
+def disc_velocity_table_from(curve: BhRotationCurve, profile: BhRadialProfile, G: float, Q: float, min_count: int = 8):
+    """(radii, vt, sigma_r, sigma_t) for set_disc_velocities: the table that gives the disc Toomre's Q everywhere.  Over the bins
+    with count >= min_count and vc2 > 0 (ValueError when fewer than two): Sigma of the profile, omega and kappa of the curve's
+    radius and vc2 (epicyclic_from over these bins), sigma_r = Q 3.36 G Sigma / kappa, sigma_t = sigma_r kappa / (2 omega)
+    (the epicyclic ratio), and the asymmetric drift
+    vt^2 = vc2 + sigma_r^2 (1 - kappa^2 / (4 omega^2) + d ln(Sigma sigma_r^2) / d ln radius), floored at 0."""
+    if len(curve.edges) != len(profile.edges) or not np.array_equal(curve.edges, profile.edges):
+        raise ValueError("the curve and the profile must share their edges")
+    with np.errstate(invalid="ignore"):
+        keep = (curve.count >= int(min_count)) & (curve.vc2 > 0.0) & (curve.radius > 0.0) & (profile.sigma > 0.0)
+    if keep.sum() < 2:
+        raise ValueError("fewer than two bins with count >= min_count and vc2 > 0")
+    radius, vc2, sigma = curve.radius[keep], curve.vc2[keep], profile.sigma[keep]
+    omega = np.sqrt(vc2) / radius
+    kappa = epicyclic_from(radius, omega)
+    sigma_r = float(Q) * TOOMRE_STELLAR * float(G) * sigma / kappa
+    sigma_t = sigma_r * kappa / (2.0 * omega)
+    vt2 = vc2 + sigma_r * sigma_r * (1.0 - kappa * kappa / (4.0 * omega * omega) + _dlog(sigma * sigma_r * sigma_r, radius))
+    return radius, np.sqrt(np.maximum(vt2, 0.0)), sigma_r, sigma_t
+
+
 @dataclass
 class BhGroups:
     """Friends-of-friends groups of the current state (groups): the label of every body, and a catalogue of the groups with at
@@ -970,6 +1099,13 @@ class BarnesHutEngine:
         current positions).  The arithmetic per precision: include/bhgpu.h."""
         self._check(self._lib.bh_kick(self._h, float(h)))
 
+    def forces_current(self) -> bool:
+        """Whether the force buffer holds the accelerations of the current positions: whether kick(), timestep() and
+        rotation_curve() would accept it.  The host's record; nothing is launched."""
+        cur = C.c_int32()
+        self._check(self._lib.bh_forces_current(self._h, C.byref(cur)))
+        return bool(cur.value)
+
     def drift(self, h: float) -> None:
         """p += v h.  The forces, the potential and the tree stop being current."""
         self._check(self._lib.bh_drift(self._h, float(h)))
@@ -1295,6 +1431,72 @@ class BarnesHutEngine:
         a, b = C.c_double(), C.c_double()
         self._check(self._lib.bh_modes_times(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # -- a disc: initial conditions, rotation curve, Toomre's Q, velocities -------------------------
+    def initialize_disc(self, n: int, seed: int = 0, mass: float = 1.0, scale: float = 0.02, r_max: float = 0.2) -> None:
+        """On-device positions of a Kuzmin-Toomre disc: surface density mass scale / (2 pi (R^2 + scale^2)^(3/2)) cut at r_max
+        (inf: no cut), equal masses mass / n, zero velocities -- equilibrate_disc gives it velocities.  Body i is a function of
+        (seed, i) alone, bit for bit that of tests/disc_ref.py.  BhError -1 unless scale is finite and > 0, r_max > 0 and mass
+        finite."""
+        self._check(self._lib.bh_initialize_disc(self._h, int(n), int(seed), float(mass), float(scale), float(r_max)))
+        self.n = int(n)
+
+    def rotation_curve(self, edges, centre="density", raw: bool = False) -> BhRotationCurve:
+        """Circular speed, omega, kappa and gravitational torque of the current state in the bins between `edges` (nb + 1
+        ascending radii, nb <= 1,022) about `centre` ("density", "com" or a pair), from the accelerations of the last
+        compute_forces() (BhError -5 when they are not those of the current positions); summed on the device in fixed point:
+        the same bodies give the same bits in any order.  Reads the state and the forces only; the run is not perturbed.
+        raw: also the int64 planes and their exponents."""
+        c = self.centre_of(centre)
+        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(ed) - 1
+        ok = 1 <= nb <= DISC_MAX_BINS                              # (else the call refuses before it writes)
+        planes = np.zeros((5, nb + 2) if ok else (5, 3), dtype=np.int64)
+        e = np.zeros(4, dtype=np.int32)
+        self._check(self._lib.bh_rotation_curve(self._h, _dptr(c), _dptr(ed) if len(ed) else None, nb,
+                                                planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rotation_curve_from_planes(planes, e, ed, c, raw)
+
+    def toomre_q(self, edges, centre="density") -> np.ndarray:
+        """Toomre's Q per bin (toomre_q_from) of the current state: its rotation curve and its radial profile about one centre."""
+        c = self.centre_of(centre)
+        return toomre_q_from(self.rotation_curve(edges, c), self.radial_profile(edges, c), self.cfg.G)
+
+    def set_disc_velocities(self, radii, vt, sigma_r, sigma_t, seed: int = 0, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0)) -> None:
+        """Every body's velocity from a table over ascending radii (1 .. 1,024 of them), interpolated linearly at the body's
+        radius about `centre` and held constant beyond the table's ends: the tangential speed vt + sigma_t g2 and the radial
+        speed sigma_r g1 with g1, g2 two standard deviates of (seed, caller index) alone, plus centre_velocity; a body at the
+        centre gets centre_velocity.  Only the velocities change: the forces stay current, as after kick()."""
+        c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
+        tabs = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in (radii, vt, sigma_r, sigma_t)]
+        k = len(tabs[0])
+        if any(len(t) != k for t in tabs):
+            raise ValueError("radii, vt, sigma_r and sigma_t must have the same length")
+        ptrs = [_dptr(t) if k else None for t in tabs]
+        self._check(self._lib.bh_set_disc_velocities(self._h, _dptr(c), _dptr(u), *ptrs, k, int(seed)))
+
+    def equilibrate_disc(self, Q: float = 1.5, edges=None, seed: int = 0, centre="com"):
+        """Velocities that hold the current bodies -- a disc at rest, as initialize_disc leaves it -- in equilibrium with
+        Toomre's Q: the forces (computed when they are not current), their rotation curve and the radial profile in `edges`
+        (default: 32 log bins from a tenth of the half-mass radius to the largest body radius), the table of
+        disc_velocity_table_from and set_disc_velocities.  Returns (curve, (radii, vt, sigma_r, sigma_t))."""
+        c = self.centre_of(centre)
+        if edges is None:
+            lag = self.lagrangian_radii((0.5, 1.0), c)
+            edges = radial_edges(0.1 * float(lag.r[0]), float(np.nextafter(lag.r[1], np.inf)), 32, "log")
+        if not self.forces_current():
+            self._check(self._lib.bh_compute_forces(self._h))
+        curve = self.rotation_curve(edges, c)
+        table = disc_velocity_table_from(curve, self.radial_profile(edges, c), self.cfg.G, Q)
+        self.set_disc_velocities(*table, seed=seed, centre=c)
+        return curve, table
+
+    def disc_times(self):
+        """(init_ms, curve_max_ms, curve_deposit_ms, velocities_ms): HIP events around the kernels of the last initialize_disc,
+        rotation_curve (its two passes) and set_disc_velocities."""
+        t = [C.c_double() for _ in range(4)]
+        self._check(self._lib.bh_disc_times(self._h, *(C.byref(x) for x in t)))
+        return tuple(x.value for x in t)
 
     # -- neighbours -----------------------------------------------------------------------------
     def _query_points(self, points):

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from .engine import BarnesHutEngine, BhConfig, Precision, radial_edges, sample_targets
+from .engine import BarnesHutEngine, BhConfig, Precision, radial_edges, sample_targets, toomre_q_from
 from .textio import loadSimulationDataFromText
 
 # project.cu:27-35, 60-61
@@ -69,6 +69,24 @@ def initializeGpu(n_bodies: int, seed: int = 0, precision: Precision = Precision
     return masses, positions, velocities
 
 
+def initializeDisc(n_bodies: int, seed: int = 0, mass: float = 1.0, scale: float = 0.02, r_max: float = 0.2, q: float = 1.5,
+                   precision: Precision = Precision.F64_EXACT, theta: float = THETA, g: float = G,
+                   max_depth: int = QUADTREE_MAX_DEPTH, reference_compat: bool = True, softening: float = 0.0,
+                   save_to_file: bool = False, device: int = 0):
+    """A Kuzmin-Toomre disc in equilibrium: BarnesHutEngine.initialize_disc, then equilibrate_disc(q) under the force law the
+    run will use (theta, g, softening).  Reproducible for a given seed."""
+    with BarnesHutEngine(BhConfig(capacity=max(n_bodies, 1), theta=theta, G=g, max_depth=max_depth, precision=precision,
+                                  reference_compat=reference_compat, device=device, softening=softening)) as eng:
+        eng.initialize_disc(n_bodies, seed, mass, scale, r_max)
+        eng.equilibrate_disc(q, seed=seed)
+        positions, velocities = eng.download()
+        masses = eng.masses()
+    if save_to_file:
+        from .textio import save_init_files
+        save_init_files(masses, positions, velocities)
+    return masses, positions, velocities
+
+
 def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_threads: int = 0,
                      theta: float = THETA, g: float = G, delta_t: float = DELTA_T,
                      max_depth: int = QUADTREE_MAX_DEPTH, precision: Precision = Precision.F64_EXACT,
@@ -89,7 +107,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
                      encounters_file: str | None = None, encounters_radius: float | None = None,
                      modes_file: str | None = None, modes_bins: int | None = None, modes_max: int = 4, modes_range=None,
                      modes_spacing: str = "log", modes_centre="density", bar_file: str | None = None, bar_mode: int = 2,
-                     bar_every: int = 0, bar_range=None, bar_centre="density"):
+                     bar_every: int = 0, bar_range=None, bar_centre="density", curve_file: str | None = None,
+                     curve_bins: int | None = None, curve_range=None, curve_spacing: str = "log", curve_centre="density"):
     """Returns (final_positions, final_velocities, gpu_parallel_duration_us).
 
     positions is NOT modified in place (the reference updates its by-reference argument,
@@ -155,6 +174,11 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
     line each: `step,t,cx,cy,amplitude,phase,pattern_speed` (%.17g) -- BarnesHutEngine.azimuthal_modes(..., rates=True)
     .total(bar_mode) of the one bin over bar_range = (rmin, rmax) about bar_centre (range None: from 0 out to just beyond the
     farthest body); velocities relative to a centre at rest.  Not part of gpu_parallel_duration_us.
+    curve_file: after the last step and every other output, one BarnesHutEngine.compute_forces() of the final state and its
+    rotation curve (BarnesHutEngine.rotation_curve, radial_profile and toomre_q_from about curve_centre) in curve_bins bins
+    (at most 1,022), curve_spacing "log" or "linear", over curve_range (None: as profile_range): the line
+    `# r_lo,r_hi,count,r,vc,omega,kappa,sigma_r,q,torque`, then one row per bin (%.17g; nan where a number is not defined).
+    Not part of gpu_parallel_duration_us.
     softening: Plummer softening length (BarnesHutEngine.set_softening) of the forces and of every diagnostic above; 0 is
     the reference's unsoftened law, the only one Precision.F64_EXACT takes.
     integrator: "euler" is the reference's fused kick-drift (BarnesHutEngine.step); "kdk" runs every batch between two
@@ -176,6 +200,8 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
         raise ValueError("pairs_file needs pairs_bins and pairs_range")
     if (modes_file is None) != (modes_bins is None):
         raise ValueError("modes_file and modes_bins go together")
+    if (curve_file is None) != (curve_bins is None):
+        raise ValueError("curve_file and curve_bins go together")
     n = len(masses)
     # both files are opened (truncated) up front, as the reference's ofstreams are (project.cu:928-929)
     init_path = os.path.join(out_dir, "quadtree_init_gpu.txt")
@@ -364,6 +390,16 @@ def runSimulationGpu(masses, positions, velocities, n_simulations: int, *, n_thr
             with open(os.path.join(out_dir, encounters_file) if not os.path.isabs(encounters_file) else encounters_file, "w") as f:
                 f.write("# i,j,r\n")
                 f.write("".join("%d,%d,%.17g\n" % r for r in zip(lo, hi, np.sqrt(d2))))
+        if curve_file is not None:                                  # (last: its force walk may re-order the state in memory)
+            centre = eng.centre_of(curve_centre)
+            edges = profile_edges(curve_bins, curve_range, curve_spacing, pos, centre)
+            eng.compute_forces()
+            rc, prof = eng.rotation_curve(edges, centre), eng.radial_profile(edges, centre)
+            cols = (rc.edges[:-1], rc.edges[1:], rc.count, rc.radius, rc.vc, rc.omega, rc.kappa, prof.sigma_r, toomre_q_from(rc, prof, g),
+                    rc.torque)
+            with open(os.path.join(out_dir, curve_file) if not os.path.isabs(curve_file) else curve_file, "w") as f:
+                f.write("# r_lo,r_hi,count,r,vc,omega,kappa,sigma_r,q,torque\n")
+                f.write("".join("%.17g,%.17g,%d,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n" % r for r in zip(*cols)))
         if traj is not None:
             traj.close()
         for f in (energy, ferr, lagrange, bar):
@@ -437,10 +473,23 @@ def _parse(argv):
     ap.add_argument("--n-bodies", type=int)
     ap.add_argument("--n-threads", type=int)
     ap.add_argument("--n-simulations", type=int)
-    ap.add_argument("--init", choices=["auto", "files", "random", "gpu"], default="auto",
+    ap.add_argument("--init", choices=["auto", "files", "random", "gpu", "disc"], default="auto",
                     help="files: loadSimulationDataFromText from the CWD; random: initializeCpu; "
                          "gpu: initializeGpu (on-device generator); auto: files when masses_init.txt "
-                         "exists, else gpu -- the reference as shipped calls initializeGpu")
+                         "exists, else gpu -- the reference as shipped calls initializeGpu; disc: an on-device "
+                         "Kuzmin-Toomre disc in equilibrium (--disc-mass, --disc-scale, --disc-rmax, --disc-q)")
+    ap.add_argument("--disc-mass", type=float, default=None, metavar="M", help="total mass of --init disc (default 1)")
+    ap.add_argument("--disc-scale", type=float, default=None, metavar="A", help="scale length of --init disc (default 0.02)")
+    ap.add_argument("--disc-rmax", type=float, default=None, metavar="R", help="truncation radius of --init disc (default 0.2; inf: none)")
+    ap.add_argument("--disc-q", type=float, default=None, metavar="Q", help="Toomre's Q of --init disc (default 1.5)")
+    ap.add_argument("--curve-file", default=None, metavar="PATH",
+                    help="also write r_lo,r_hi,count,r,vc,omega,kappa,sigma_r,q,torque (the rotation curve of the final state's own "
+                         "forces, with Toomre's Q and the gravitational torque) of the --curve-bins radial bins about --curve-centre")
+    ap.add_argument("--curve-bins", type=int, default=None, metavar="NB", help="bins of --curve-file (1 .. 1022)")
+    ap.add_argument("--curve-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
+                    help="range of --curve-file (default: out to just beyond the farthest body)")
+    ap.add_argument("--curve-spacing", choices=["log", "linear"], default="log", help="spacing of the bin edges")
+    ap.add_argument("--curve-centre", nargs="+", default=None, metavar="C", help="density (default), com or X Y")
     ap.add_argument("--positions-file", default=None, help="also write the trajectory (savePositions format)")
     ap.add_argument("--energy-file", default=None, metavar="PATH",
                     help="also write step,t,kinetic,potential,total,px,py,Lz before the first step, every "
@@ -594,6 +643,26 @@ def _parse(argv):
             ap.error(flag + ": 0 <= RMIN < RMAX, finite")
     if a.modes_range is not None and a.modes_spacing == "log" and a.modes_range[0] <= 0.0:
         ap.error("--modes-range: log spacing needs RMIN > 0")
+    if a.init != "disc" and any(v is not None for v in (a.disc_mass, a.disc_scale, a.disc_rmax, a.disc_q)):
+        ap.error("--disc-mass, --disc-scale, --disc-rmax and --disc-q need --init disc")
+    if a.disc_mass is not None and not math.isfinite(a.disc_mass):
+        ap.error("--disc-mass: finite")
+    if a.disc_scale is not None and not (0.0 < a.disc_scale < math.inf):
+        ap.error("--disc-scale: finite and > 0")
+    if a.disc_rmax is not None and not a.disc_rmax > 0.0:
+        ap.error("--disc-rmax: > 0 (inf: no truncation)")
+    if a.disc_q is not None and not (0.0 <= a.disc_q < math.inf):
+        ap.error("--disc-q: finite and >= 0")
+    if (a.curve_file is None) != (a.curve_bins is None):
+        ap.error("--curve-file and --curve-bins go together")
+    if a.curve_file is None and (a.curve_range is not None or a.curve_centre is not None):
+        ap.error("--curve-range and --curve-centre need --curve-file")
+    if a.curve_bins is not None and not 1 <= a.curve_bins <= 1022:
+        ap.error("--curve-bins: 1 .. 1022")
+    if a.curve_range is not None and not (0.0 <= a.curve_range[0] < a.curve_range[1] < float("inf")):
+        ap.error("--curve-range: 0 <= RMIN < RMAX, finite")
+    if a.curve_range is not None and a.curve_spacing == "log" and a.curve_range[0] <= 0.0:
+        ap.error("--curve-range: log spacing needs RMIN > 0")
     if a.bar_file is None and (a.bar_mode is not None or a.bar_every or a.bar_range is not None or a.bar_centre is not None):
         ap.error("--bar-mode, --bar-every, --bar-range and --bar-centre need --bar-file")
     if a.bar_mode is not None and not 1 <= a.bar_mode <= 16:
@@ -638,6 +707,7 @@ def _parse(argv):
     a.lagrange_centre = _centre_arg(ap, "--lagrange-centre", a.lagrange_centre)
     a.modes_centre = _centre_arg(ap, "--modes-centre", a.modes_centre)
     a.bar_centre = _centre_arg(ap, "--bar-centre", a.bar_centre)
+    a.curve_centre = _centre_arg(ap, "--curve-centre", a.curve_centre)
     if a.groups_min is not None and a.groups_min < 1:
         ap.error("--groups-min: at least 1")
     if a.linking_length is not None and not (a.linking_length >= 0.0 and a.linking_length < float("inf")):
@@ -690,6 +760,12 @@ def main(argv=None) -> int:
             "masses_init.txt", "positions_init.txt", "velocities_init.txt", n, N_BODIES=n)
     elif a.init == "random":
         masses, positions, velocities = initializeCpu(n, seed=a.seed, save_to_file=a.save_init)
+    elif a.init == "disc":
+        masses, positions, velocities = initializeDisc(
+            n, seed=a.seed, mass=1.0 if a.disc_mass is None else a.disc_mass, scale=0.02 if a.disc_scale is None else a.disc_scale,
+            r_max=0.2 if a.disc_rmax is None else a.disc_rmax, q=1.5 if a.disc_q is None else a.disc_q,
+            precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32, theta=a.theta, max_depth=a.max_depth,
+            reference_compat=not a.no_compat, softening=a.softening or 0.0, save_to_file=a.save_init)
     else:
         masses, positions, velocities = initializeGpu(
             n, seed=a.seed, precision=Precision.F64_EXACT if a.precision == "f64" else Precision.F32,
@@ -718,7 +794,9 @@ def main(argv=None) -> int:
         encounters_file=a.encounters_file, encounters_radius=a.encounters_radius, modes_file=a.modes_file,
         modes_bins=a.modes_bins, modes_max=4 if a.modes_max is None else a.modes_max, modes_range=a.modes_range,
         modes_spacing=a.modes_spacing, modes_centre=a.modes_centre, bar_file=a.bar_file,
-        bar_mode=2 if a.bar_mode is None else a.bar_mode, bar_every=a.bar_every, bar_range=a.bar_range, bar_centre=a.bar_centre)
+        bar_mode=2 if a.bar_mode is None else a.bar_mode, bar_every=a.bar_every, bar_range=a.bar_range, bar_centre=a.bar_centre,
+        curve_file=a.curve_file, curve_bins=a.curve_bins, curve_range=a.curve_range, curve_spacing=a.curve_spacing,
+        curve_centre=a.curve_centre)
     duration_ms = int((time.perf_counter() - start) * 1e3)
 
     # project.cu:1090-1102, blank lines included

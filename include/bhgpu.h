@@ -409,6 +409,10 @@ int bh_kick(bh_ctx *ctx, double h);
 int bh_drift(bh_ctx *ctx, double h);
 int bh_timestep(bh_ctx *ctx, double eta, double length, bh_timestep_t *out);
 int bh_step_kdk(bh_ctx *ctx, int32_t nsteps);
+/* bh_forces_current: *current = 1 when the force buffer holds the accelerations of the current positions of all bodies under the
+ * current law -- when bh_kick, bh_timestep and bh_rotation_curve would accept it --, else 0 (before any upload too).  It asks
+ * the host's record only: no launch, no wait.  BH_ERR_ARG for a null pointer. */
+int bh_forces_current(bh_ctx *ctx, int32_t *current);
 
 /* --- moment maps: where the mass is, how it streams, how hot it is ----------------------------------------------------
  * The reference draws its pictures on the host from the downloaded state (plot_2d.py); these deposit on the device, so a
@@ -556,6 +560,58 @@ int bh_modes_max(bh_ctx *ctx, const double centre[2], const double centre_vel[2]
 int bh_modes_deposit(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *edges, int32_t nb, int32_t M,
                      int32_t rates, const int32_t exponents[2], void **planes_dev);
 int bh_modes_times(bh_ctx *ctx, double *max_ms, double *deposit_ms);
+
+/* --- a disc: initial conditions, the rotation curve of the engine's own forces, velocities about a radial table ---------------
+ * Everything below is written down operation by operation in fp64 with nothing fused and goes through no mathematical
+ * library beyond the correctly rounded sqrt: a twin in numpy gives the same bits (tests/disc_ref.py).
+ * bh_initialize_disc: n bodies of a Kuzmin-Toomre disc, surface density mass * scale / (2 pi (R^2 + scale^2)^(3/2)) cut at
+ *   r_max (+inf: no cut), every mass mass / n (one host division), velocities zero.  Body i is a function of (seed, i):
+ *     F = 1 - scale / sqrt(r_max^2 + scale^2) on the host (1 without a cut)
+ *     stream 96:       u = u01(w0, w1) * F;  t = u * (2 - u);  R = (scale * sqrt(t)) / (1 - u)
+ *     stream 128 + k:  p = 2 u01(w0, w1) - 1;  q = 2 u01(w2, w3) - 1;  s = p * p + q * q;  taken when 2^-1022 <= s <= 1, else
+ *                      the next stream, 64 at most; the 64th stands whatever its s ((1, 0) when its s < 2^-1022)
+ *     x = R * (p / sqrt(s));  y = R * (q / sqrt(s)), rounded to the state type
+ *   (u01: the 53-bit uniform of bh_initialize; its streams 0-2 and 16-79 are not used here.)  It fires the events of
+ *   bh_initialize: a new body set in caller order, nothing current.  It does not wait for the stream.
+ *   Errors: BH_ERR_ARG for n < 0 or n > capacity (the message of bh_initialize), scale not finite or <= 0, r_max not > 0, mass
+ *   not finite.
+ * bh_rotation_curve: per body of the CURRENT state, with centre = {cx, cy} and (ax, ay) the acceleration in the force buffer
+ *   -- widened from fp32, or Fx / m, Fy / m by one division each with an fp64 tree: what bh_get_accel returns --
+ *     dx = x - cx;  dy = y - cy;  r2 = dx * dx + dy * dy;  r = sqrt(r2)
+ *     q0 = m   q1 = m * r   q2 = m * (dx * ax + dy * ay)   q3 = m * (dx * ay - dy * ax)
+ *   summed over the nb + 2 slots of the radial profiles (decided on r2 against the squared edges; a body on an edge belongs to
+ *   the bin above it) into planes[5][nb + 2], plane-major: planes 0-3 in the fixed point of the moment maps with
+ *   exponents[p] = 62 - E(max |q_p|) - L from a first pass over the whole system, plane 4 the body count.
+ *   value = planes * 2^-exponent.  -q2 / q0 of a bin is its squared circular speed, q1 / q0 its mean radius, q3 the torque on it.
+ *   nb <= BH_DISC_MAX_BINS.  It needs the forces of the current positions (bh_compute_forces, bh_step_kdk; bh_kick keeps them),
+ *   reads the state and the force buffer only and changes nothing a step reads.  It waits for the stream.
+ *   Errors: BH_ERR_ARG for a null pointer, a centre that is not finite, nb < 1 or > BH_DISC_MAX_BINS, bad edges (as the radial
+ *   calls), and -- found by the first pass -- a body whose position, mass, acceleration, r2 or contribution is not finite (a
+ *   massless body with an fp64 tree: 0 / 0).  BH_ERR_STATE before any upload, in LET mode or with world > 1, and when the forces
+ *   are not current.
+ * bh_set_disc_velocities: the velocity of every body from k ascending radii and three tables over them -- the mean tangential
+ *   speed vt and the radial and tangential dispersions --, about centre with the velocity centre_vel = {ucx, ucy} (NULL: 0).
+ *   Per body with caller index i (dx, dy, r2 as above):
+ *     r2 < 2^-1022:  v = (ucx, ucy)
+ *     r = sqrt(r2);  j = the number of radii with radii[.]^2 <= r2
+ *     j = 0: f = y[0];  j = k: f = y[k-1];  else t = (r - radii[j-1]) / (radii[j] - radii[j-1]);  f = y[j-1] + t * (y[j] - y[j-1])
+ *     g1 = ((int64) sum of the twelve 32-bit words of streams 192 .. 194 of (seed, i)  -  6 (2^32 - 1)) * 2^-32;  g2: 195 .. 197
+ *     vr = sr * g1;  vtt = vt + st * g2;  vx = ucx + (vr * dx - vtt * dy) / r;  vy = ucy + (vr * dy + vtt * dx) / r
+ *   rounded to the state type.  g is a sum of twelve uniforms (Irwin-Hall): mean 0 exactly, variance 1 - 2^-64, |g| <= 6, exact.
+ *   Only the velocities are written: positions, masses, the force buffer and what is current stay, as after bh_kick.  It waits
+ *   for the stream.
+ *   Errors: BH_ERR_ARG for a null table, a centre or centre velocity that is not finite, k outside 1 .. BH_DISC_MAX_TABLE, radii
+ *   (or squares) not finite, negative or not strictly ascending, a table entry that is not finite, a negative dispersion.
+ *   BH_ERR_STATE before any upload, in LET mode or with world > 1.
+ * bh_disc_times: HIP-event times of the last bh_initialize_disc (it waits for the stream when that has not been read yet), of
+ *   the two passes of the last bh_rotation_curve, and of the last bh_set_disc_velocities. */
+#define BH_DISC_MAX_BINS 1022
+#define BH_DISC_MAX_TABLE 1024
+int bh_initialize_disc(bh_ctx *ctx, int64_t n, uint64_t seed, double mass, double scale, double r_max);
+int bh_rotation_curve(bh_ctx *ctx, const double centre[2], const double *edges, int32_t nb, int64_t *planes, int32_t exponents[4]);
+int bh_set_disc_velocities(bh_ctx *ctx, const double centre[2], const double centre_vel[2], const double *radii, const double *vt,
+                           const double *sigma_r, const double *sigma_t, int32_t k, uint64_t seed);
+int bh_disc_times(bh_ctx *ctx, double *init_ms, double *curve_max_ms, double *curve_deposit_ms, double *velocities_ms);
 
 /* --- neighbours: which bodies are next to a body or a point, and how far away ------------------------------------------
  * Queries.  points == NULL: the queries are the n bodies in caller order and n_points must be n; body i is left out of its
