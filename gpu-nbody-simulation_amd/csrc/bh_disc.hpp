@@ -17,8 +17,8 @@
 //      (ax, ay) = the acceleration, or (Fx / m, Fy / m): what bh_get_accel returns
 //      q0 = m   q1 = m * r   q2 = m * (dx * ax + dy * ay)   q3 = m * (dx * ay - dy * ax)
 //    Slots by radial_slot on r2, nb + 2 of them, nb <= 1022: planes 0-3 are the sums of q0-q3 in the fixed point of the moment
-//    maps, one exponent each from the system-wide maxima; plane 4 is the body count.  The histogram is always
-//    workgroup-private in LDS (5 x (nb + 2) words and the nb + 1 squared edges): one code path.
+//    maps, one exponent each from the system-wide maxima; plane 4 is the body count.  The histogram (SlotHist, bh_binned.hpp)
+//    is always workgroup-private in LDS (5 x (nb + 2) words and the nb + 1 squared edges): one code path.
 //
 // 3. disc_velocities_kernel.  k <= 1024 strictly ascending radii Rn with their squares, three tables vt, sr, st.  Per slot, with
 //    the caller index i of the slot (through orig where the state has been re-ordered):
@@ -102,15 +102,12 @@ __device__ __forceinline__ bool curve_body(const Real2 *__restrict__ pos, const 
     return map_finite((double)pp.x) && map_finite((double)pp.y) && map_finite(m) && map_finite(ax) && map_finite(ay);
 }
 
-// pass 1: out must be zeroed.  As radial_max_kernel: a thread folds its trips, the workgroup folds its threads in LDS, lane 0
-// sends one atomic per plane.
+// pass 1: out must be zeroed.  A thread folds its trips, fold_maxima (bh_binned.hpp) the workgroup.
 template <typename Real2, typename Real, typename Acc2>
 __global__ __launch_bounds__(kBlock) void curve_max_kernel(const Real2 *__restrict__ pos, const Real *__restrict__ mass,
                                                            const Acc2 *__restrict__ force, int64_t n, RadCentre ctr,
                                                            DiscMax *__restrict__ out)
 {
-    __shared__ double sh[kDiscPlanes][kBlock];
-    __shared__ int sh_flag[kBlock];
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     double a[kDiscPlanes] = {0.0, 0.0, 0.0, 0.0};
     int flag = 0;
@@ -124,33 +121,11 @@ __global__ __launch_bounds__(kBlock) void curve_max_kernel(const Real2 *__restri
             if (!bad && fabs(q[p]) > a[p]) a[p] = fabs(q[p]);
         flag |= bad ? 1 : 0;
     }
-#pragma unroll
-    for (int p = 0; p < kDiscPlanes; ++p) sh[p][threadIdx.x] = a[p];
-    sh_flag[threadIdx.x] = flag;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-#pragma unroll
-            for (int p = 0; p < kDiscPlanes; ++p) {
-                const double b = sh[p][threadIdx.x + h];
-                if (b > sh[p][threadIdx.x]) sh[p][threadIdx.x] = b;
-            }
-            sh_flag[threadIdx.x] |= sh_flag[threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int p = 0; p < kDiscPlanes; ++p) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(sh[p][0]);
-            if (b) atomicMax(&out->bits[p], b);
-        }
-        if (sh_flag[0] & 1) atomicOr(&out->bad, 1ull);
-    }
+    if (fold_maxima(a, flag, out) & 1) atomicOr(&out->bad, 1ull);
 }
 
-// pass 2: planes[p][slot] += contribution, planes[4][slot] += 1, S = nb + 2 <= kDiscLdsSlots slots per plane.  Dynamic LDS:
-// 5 * S words of histogram, then the nb + 1 squared edges.  Contributions that round to zero are skipped.
+// pass 2: planes[p][slot] += contribution, planes[4][slot] += 1, S = nb + 2 <= kDiscLdsSlots slots per plane, through a
+// SlotHist (bh_binned.hpp) in its private form alone (tile 0, a constant): 5 * S words of dynamic LDS and the nb + 1 squared edges.
 template <typename Real2, typename Real, typename Acc2>
 __global__ __launch_bounds__(kBlock) void curve_deposit_kernel(const Real2 *__restrict__ pos, const Real *__restrict__ mass,
                                                                const Acc2 *__restrict__ force, int64_t n, RadCentre ctr,
@@ -158,29 +133,17 @@ __global__ __launch_bounds__(kBlock) void curve_deposit_kernel(const Real2 *__re
                                                                long long *__restrict__ planes)
 {
     extern __shared__ unsigned long long disc_lds[];
-    const int S = nb + 2;
-    unsigned long long *hist = disc_lds;
-    double *e2 = reinterpret_cast<double *>(disc_lds + (kDiscPlanes + 1) * S);
-    for (int k = threadIdx.x; k <= nb; k += kBlock) e2[k] = e2_mem[k];
-    for (int k = threadIdx.x; k < (kDiscPlanes + 1) * S; k += kBlock) hist[k] = 0ull;
-    __syncthreads();
+    const SlotHist h = slot_hist(disc_lds, kDiscPlanes + 1, nb, 0, e2_mem, planes, pos, n, ctr);
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         double r2, q[kDiscPlanes];
         curve_body(pos, mass, force, i, ctr, r2, q);
-        const int s = radial_slot(e2, nb, r2);
+        const int s = radial_slot(h.e2, nb, r2);
 #pragma unroll
-        for (int p = 0; p < kDiscPlanes; ++p) {
-            const long long v = (long long)rint(ldexp(q[p], ex.e[p]));
-            if (v) atomicAdd(&hist[p * S + s], (unsigned long long)v);
-        }
-        atomicAdd(&hist[kDiscPlanes * S + s], 1ull);
+        for (int p = 0; p < kDiscPlanes; ++p) h.put(p, s, (long long)rint(ldexp(q[p], ex.e[p])));
+        h.put(kDiscPlanes, s, 1ll);
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < (kDiscPlanes + 1) * S; k += kBlock) {
-        const unsigned long long v = hist[k];
-        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(planes + k), v);
-    }
+    h.flush();
 }
 
 // the sum of the twelve words of three streams, centred and scaled: exact in fp64

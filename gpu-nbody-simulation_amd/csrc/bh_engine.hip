@@ -1,7 +1,8 @@
 // bh_engine.hip -- libbhgpu.so: the C-ABI of include/bhgpu.h.  In this file: the context and its helpers, the tree build, the
 // walks' launchers, the step and the split operators, the diagnostics, direct sums and force check, tree export, the
-// locally-essential trees and migration.  The analysis queries' host code -- moment maps, radial profiles, azimuthal modes, field at points,
-// neighbours, pair counts, groups, spanning trees -- is bh_queries_host.hpp, included below as part of this unit.
+// locally-essential trees and migration, and of the disc what writes the state (initial conditions, velocities).  The analysis
+// queries' host code -- moment maps, radial profiles, azimuthal modes, the rotation curve, field at points, neighbours, pair counts,
+// groups, spanning trees -- is bh_queries_host.hpp, included below as part of this unit.
 // Compiled with -ffp-contract=off (tree build + exact walk must not fuse multiply-adds; the fp32
 // walk lives in bh_walk_fast.hip, compiled separately).  gfx950 only, no CPU fallback.
 #include "../../include/bhgpu.h"
@@ -889,6 +890,16 @@ int diag_check(bh_ctx *c, const char *what)
                                      "and the energy sums; the replicated scheme (world > 1) and the other diagnostics have no distributed form");
 }
 
+// the split operators and the disc: uploaded, one context, and -- need_forces -- forces of the positions as they are
+int split_check(bh_ctx *c, const char *what) { return single_gpu_check(c, what, ": single GPU only (not in LET mode or with world > 1)"); }
+
+int need_forces(bh_ctx *c, const char *what)
+{
+    if (c->is.forces_current) return BH_OK;
+    return fail(c, BH_ERR_STATE, std::string(what) + ": the force buffer does not hold the accelerations of the current positions "
+                                 "(bh_compute_forces first; a step, bh_drift, bh_upload, bh_build_tree and a new softening length outdate them)");
+}
+
 // the LET calls' preconditions (c may be null): configured, and on demand bodies or a tree in the buffers
 enum LetNeed { kLetConfigured, kLetBodies, kLetTree };
 int let_check(bh_ctx *c, const char *who, LetNeed need)
@@ -952,8 +963,8 @@ int quietly(bh_ctx *c, unsigned opts, Body body)
 
 }  // namespace
 
-// the analysis queries: moment maps, radial profiles, field at points, neighbours, pair counts, groups, spanning trees -- and the helpers they
-// share, which the diagnostics below use as well
+// the analysis queries: moment maps, radial profiles, azimuthal modes, the rotation curve, field at points, neighbours, pair counts,
+// groups, spanning trees -- and the helpers they share, which the diagnostics and the disc below use as well
 #include "bh_queries_host.hpp"
 
 // ================================================================================================
@@ -1347,15 +1358,6 @@ int bh_step(bh_ctx *c, int32_t nsteps)
 }
 
 // ---- the split operators (bh_split.hpp): kick, drift, the time-step criterion, and the leapfrog built from them
-static int split_check(bh_ctx *c, const char *what) { return single_gpu_check(c, what, ": single GPU only (not in LET mode or with world > 1)"); }
-
-static int need_forces(bh_ctx *c, const char *what)
-{
-    if (c->is.forces_current) return BH_OK;
-    return fail(c, BH_ERR_STATE, std::string(what) + ": the force buffer does not hold the accelerations of the current positions "
-                                 "(bh_compute_forces first; a step, bh_drift, bh_upload, bh_build_tree and a new softening length outdate them)");
-}
-
 int bh_forces_current(bh_ctx *c, int32_t *current)
 {
     if (!c || !current) return fail(c, BH_ERR_ARG, "bh_forces_current: null argument");
@@ -1533,37 +1535,8 @@ int bh_get_interaction_counts(bh_ctx *c, uint32_t *out)
     return counts_to_caller_order(c, c->body_counts, out);
 }
 
-// ---- the disc (bh_disc.hpp): initial conditions, the rotation curve's sums, velocities about a table.  The curve reads pos, mass
-// and the force buffer as they lie in memory (slot for slot) and writes buffers of its own; the velocities write vel alone: no
-// record of bh_run_state.hpp changes on either, as on bh_kick.
-}  // extern "C"
-
-namespace {
-
-int disc_alloc(bh_ctx *c)
-{
-    DiscState &s = c->disc;
-    if (s.max) return BH_OK;
-    return alloc_all(c, {part(&s.max, 1), part(&s.e2, (size_t)kDiscMaxBins + 1), part(&s.tables, (size_t)kDiscTables * kDiscMaxTable),
-                         part(&s.planes, (size_t)(kDiscPlanes + 1) * (kDiscMaxBins + 2))});
-}
-
-// f(pos, mass, force) as the precision types them: the force buffer holds fp32 accelerations unless the tree is fp64
-template <typename F>
-void curve_ptrs(const bh_ctx *c, F &&f)
-{
-    switch (c->mode) {
-    case Mode::F32: f((const float2 *)c->pos, (const float *)c->mass, (const float2 *)c->force); break;
-    case Mode::Mixed: f((const double2 *)c->pos, (const double *)c->mass, (const float2 *)c->force); break;
-    case Mode::F64:
-    case Mode::Exact: f((const double2 *)c->pos, (const double *)c->mass, (const double2 *)c->force); break;
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- the disc (bh_disc.hpp): what writes the state -- initial conditions, and velocities about a table, which write vel alone
+// and change no record of bh_run_state.hpp, as bh_kick.  The rotation curve is a query: bh_queries_host.hpp, with disc_alloc.
 int bh_initialize_disc(bh_ctx *c, int64_t n, uint64_t seed, double mass, double scale, double r_max)
 {
     if (!c) return BH_ERR_ARG;
@@ -1592,66 +1565,6 @@ int bh_initialize_disc(bh_ctx *c, int64_t n, uint64_t seed, double mass, double 
     }
     BH_HIP(c, hipMemsetAsync(c->force, 0, force_bytes(c, n), c->stream));
     return upload_done(c, n);
-}
-
-int bh_rotation_curve(bh_ctx *c, const double *centre, const double *edges, int32_t nb, int64_t *planes, int32_t *exponents)
-{
-    if (!c) return BH_ERR_ARG;
-    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_rotation_curve: null argument");
-    DiscState &s = c->disc;
-    RadCentre ctr{};
-    std::vector<double> e2;
-    if (int rc = rad_centre(c, "bh_rotation_curve", centre, nullptr, &ctr)) return rc;
-    if (!edges) return fail(c, BH_ERR_ARG, "bh_rotation_curve: null edges");
-    const unsigned why = squared_edges(edges, nb, kDiscMaxBins, e2);
-    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, "bh_rotation_curve: nb must be 1 .. BH_DISC_MAX_BINS = " + std::to_string(kDiscMaxBins));
-    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, "bh_rotation_curve: an edge or its square is not finite");
-    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, "bh_rotation_curve: the edges must be >= 0");
-    if (why) return fail(c, BH_ERR_ARG, "bh_rotation_curve: the edges and their squares must be strictly ascending");
-    if (int rc = split_check(c, "bh_rotation_curve")) return rc;
-    if (int rc = need_forces(c, "bh_rotation_curve")) return rc;
-    BH_HIP(c, hipSetDevice(c->device));
-    if (int rc = disc_alloc(c)) return rc;
-    const int S = nb + 2;
-    s.max_ms = s.deposit_ms = 0.0;
-    double maxabs[kDiscPlanes] = {0.0, 0.0, 0.0, 0.0};
-    if (c->n > 0) {
-        if (int rc = mark(c, s.ev[2])) return rc;
-        BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(DiscMax), c->stream));
-        curve_ptrs(c, [&](auto pos, auto mass, auto force) {
-            hipLaunchKernelGGL((curve_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>), dim3(rad_grid(c)),
-                               dim3(kBlock), 0, c->stream, pos, mass, force, c->n, ctr, s.max);
-        });
-        BH_HIP(c, hipGetLastError());
-        if (int rc = mark(c, s.ev[3])) return rc;
-        DiscMax r{};
-        if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
-        if (int rc = span_ms(c, s.ev[2], s.ev[3], &s.max_ms)) return rc;
-        if (r.bad)
-            return fail(c, BH_ERR_ARG, "bh_rotation_curve: a body has a non-finite position, mass or acceleration (a massless body of an "
-                                       "fp64 tree: 0 / 0), or a squared radius or a contribution m r, m (x . a), m (x x a) that overflows fp64");
-    }
-    int32_t e[kDiscPlanes];
-    for (int p = 0; p < kDiscPlanes; ++p) e[p] = plane_exponent(maxabs[p], log2_ceil(c->n));
-    if (int rc = mark(c, s.ev[4])) return rc;
-    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)(kDiscPlanes + 1) * S * sizeof(long long), c->stream));
-    if (c->n > 0) {
-        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        DiscExp ex{};
-        for (int p = 0; p < kDiscPlanes; ++p) ex.e[p] = e[p];
-        const size_t lds = ((size_t)(kDiscPlanes + 1) * S + (size_t)nb + 1) * 8;
-        curve_ptrs(c, [&](auto pos, auto mass, auto force) {
-            hipLaunchKernelGGL((curve_deposit_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>),
-                               dim3(rad_grid(c)), dim3(kBlock), lds, c->stream, pos, mass, force, c->n, ctr, s.e2, (int)nb, ex, s.planes);
-        });
-        BH_HIP(c, hipGetLastError());
-    }
-    if (int rc = mark(c, s.ev[5])) return rc;
-    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
-    if (int rc = span_ms(c, s.ev[4], s.ev[5], &s.deposit_ms)) return rc;
-    BH_HIP(c, hipMemcpy(planes, s.planes, (size_t)(kDiscPlanes + 1) * S * sizeof(int64_t), hipMemcpyDeviceToHost));
-    std::copy(e, e + kDiscPlanes, exponents);
-    return BH_OK;
 }
 
 int bh_set_disc_velocities(bh_ctx *c, const double *centre, const double *centre_vel, const double *radii, const double *vt,

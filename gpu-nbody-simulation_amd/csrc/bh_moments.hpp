@@ -29,7 +29,7 @@
 // LDS first (moment_deposit_kernel).  All memory traffic is ordinary vector loads, stores and atomics.
 #pragma once
 
-#include "bh_prims.hpp"
+#include "bh_binned.hpp"
 
 namespace bh {
 
@@ -62,13 +62,11 @@ __device__ __forceinline__ void map_moments(const Real2 *__restrict__ vel, const
     q[3] = m * (vx * vx + vy * vy);
 }
 
-// pass 1: out must be zeroed.  One thread per body; the workgroup folds its maxima in LDS, lane 0 sends one atomic per plane.
+// pass 1: out must be zeroed.  One thread per body; fold_maxima (bh_binned.hpp) folds the workgroup and sends its atomics.
 template <typename Real2, typename Real>
 __global__ __launch_bounds__(kBlock) void moment_max_kernel(const Real2 *__restrict__ pos, const Real2 *__restrict__ vel,
                                                             const Real *__restrict__ mass, int64_t n, MapMax *__restrict__ out)
 {
-    __shared__ double sh[kMapPlanes][kBlock];
-    __shared__ int sh_bad[kBlock];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     double a[kMapPlanes] = {0.0, 0.0, 0.0, 0.0};
     int bad = 0;
@@ -83,29 +81,7 @@ __global__ __launch_bounds__(kBlock) void moment_max_kernel(const Real2 *__restr
 #pragma unroll
         for (int p = 0; p < kMapPlanes; ++p) a[p] = bad ? 0.0 : fabs(q[p]);
     }
-#pragma unroll
-    for (int p = 0; p < kMapPlanes; ++p) sh[p][threadIdx.x] = a[p];
-    sh_bad[threadIdx.x] = bad;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-#pragma unroll
-            for (int p = 0; p < kMapPlanes; ++p) {
-                const double b = sh[p][threadIdx.x + h];
-                if (b > sh[p][threadIdx.x]) sh[p][threadIdx.x] = b;
-            }
-            sh_bad[threadIdx.x] |= sh_bad[threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int p = 0; p < kMapPlanes; ++p) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(sh[p][0]);
-            if (b) atomicMax(&out->bits[p], b);
-        }
-        if (sh_bad[0]) atomicOr(&out->bad, 1ull);
-    }
+    if (fold_maxima(a, bad, out)) atomicOr(&out->bad, 1ull);
 }
 
 // pass 2: planes[p][iy][ix] += contribution; *deposited += bodies with at least one corner inside (one atomic per wave).

@@ -1,10 +1,11 @@
-// bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, azimuthal modes, the field
-// at points, neighbour queries and lists, pair counts, friends-of-friends groups, spanning trees and bound pairs, with their entry points
-// of include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after the context and the engine's helpers
-// (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp,
-// bh_radial.hpp, bh_modes.hpp, bh_field.hpp, bh_neighbours.hpp, bh_neighbour_lists.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp, the state in
-// bh_queries_state.hpp,
-// the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes first.
+// bh_queries_host.hpp -- the host side of the analysis queries: moment maps, radial profiles and Lagrangian radii, azimuthal modes,
+// the rotation curve, the field at points, neighbour queries and lists, pair counts, friends-of-friends groups, spanning trees and
+// bound pairs, with their entry points of include/bhgpu.h.  Part of the bh_engine.hip translation unit: included there once, after
+// the context and the engine's helpers (fail, BH_HIP, dev_alloc, with_state, dispatch, quietly, split_check, need_forces,
+// enqueue_lsd_passes ...).  The kernels are in bh_moments.hpp, bh_radial.hpp, bh_modes.hpp, bh_disc.hpp (with bh_binned.hpp under
+// all four), bh_field.hpp, bh_neighbours.hpp, bh_neighbour_lists.hpp, bh_pairs.hpp, bh_groups.hpp, bh_mst.hpp and bh_binaries.hpp,
+// the state in bh_queries_state.hpp, the arithmetic that needs no device in bh_query_host.hpp.  What every family shares comes
+// first, with the two passes of the binned sums: first_pass, plane_exponents, radial_edges, deposit_pass.
 #pragma once
 
 #include "bh_query_host.hpp"
@@ -85,18 +86,64 @@ int read_maxima(bh_ctx *c, const Rec *dev, Rec *rec, double (&maxabs)[P], void *
     return BH_OK;
 }
 
-// the caller's exponents must cover this context's own maxima and body count -- else a contribution or a sum could leave int64
+// A first pass of the binned sums (bh_binned.hpp): the record zeroed, `launch` enqueued, then as read_maxima; the record's flags
+// are the caller's to test and to word.  ev: the two marks around the pass, *ms the span between them (null: not timed).
+template <typename Rec, int P, typename Launch>
+int first_pass(bh_ctx *c, Rec *dev, Rec *rec, double (&maxabs)[P], Launch &&launch, hipEvent_t *ev = nullptr, double *ms = nullptr)
+{
+    if (ev) { if (int rc = mark(c, ev[0])) return rc; }
+    BH_HIP(c, hipMemsetAsync(dev, 0, sizeof(Rec), c->stream));
+    launch();
+    BH_HIP(c, hipGetLastError());
+    if (ev) { if (int rc = mark(c, ev[1])) return rc; }
+    if (int rc = read_maxima(c, dev, rec, maxabs)) return rc;
+    return ev ? span_ms(c, ev[0], ev[1], ms) : BH_OK;
+}
+
+// e: the caller's exponents `given` or, without, the rule's own from this context's maxima and body count.  A caller's must cover
+// those -- else a contribution or a sum could leave int64.
 template <int P>
-int exponents_fit(bh_ctx *c, const char *who, const int32_t *e, const double (&maxabs)[P])
+int plane_exponents(bh_ctx *c, const char *who, const int32_t *given, const double (&maxabs)[P], int32_t (&e)[P])
 {
     const int L = log2_ceil(c->n);
     for (int p = 0; p < P; ++p) {
+        e[p] = given ? given[p] : plane_exponent(maxabs[p], L);
         int32_t most = 0;
         if (!exponent_fits(e[p], maxabs[p], L, &most))
             return fail(c, BH_ERR_ARG, std::string(who) + ": exponent " + std::to_string(e[p]) + " of plane " + std::to_string(p) +
                                        " is too large for this context's bodies (at most " + std::to_string(most) + ")");
     }
     return BH_OK;
+}
+
+// a caller's nb + 1 bin edges, squared on the host: BH_ERR_ARG unless nb is 1 .. limit and the edges and their squares are finite,
+// >= 0 and strictly ascending
+int radial_edges(bh_ctx *c, const std::string &who, const double *edges, int32_t nb, const char *limit_name, int32_t limit,
+                 std::vector<double> &e2)
+{
+    if (!edges) return fail(c, BH_ERR_ARG, who + ": null edges");
+    const char *fault = edges_fault(squared_edges(edges, nb, limit, e2));
+    if (!fault) return BH_OK;
+    const std::string most = fault == kEdgesCountFault ? limit_name + std::string(" = ") + std::to_string(limit) : std::string();
+    return fail(c, BH_ERR_ARG, who + ": " + fault + most);
+}
+
+// A deposit pass over radial slots between the marks ev[0] and ev[1], *ms the span: `words` of planes zeroed and, with bodies,
+// the squared edges uploaded and `launch` enqueued.  Waits for the stream: e2 is the caller's to drop after this.
+template <typename Launch>
+int deposit_pass(bh_ctx *c, hipEvent_t *ev, double *ms, long long *planes, size_t words, double *e2_dev, const std::vector<double> &e2,
+                 Launch &&launch)
+{
+    if (int rc = mark(c, ev[0])) return rc;
+    BH_HIP(c, hipMemsetAsync(planes, 0, words * sizeof(long long), c->stream));
+    if (c->n > 0) {
+        BH_HIP(c, hipMemcpyAsync(e2_dev, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        launch();
+        BH_HIP(c, hipGetLastError());
+    }
+    if (int rc = mark(c, ev[1])) return rc;
+    BH_HIP(c, hipStreamSynchronize(c->stream));
+    return span_ms(c, ev[0], ev[1], ms);
 }
 
 int points_finite(bh_ctx *c, const char *who, const double *points, int64_t n_points)
@@ -156,14 +203,14 @@ int map_maxima(bh_ctx *c, const char *who, double (&maxabs)[kMapPlanes])
     for (double &v : maxabs) v = 0.0;
     if (c->n == 0) return BH_OK;
     if (int rc = map_alloc(c, 0)) return rc;
-    BH_HIP(c, hipMemsetAsync(c->map.max, 0, sizeof(MapMax), c->stream));
-    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
-        hipLaunchKernelGGL((moment_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(blocks_for(c->n, kBlock)),
-                           dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, c->map.max);
-    });
-    BH_HIP(c, hipGetLastError());
     MapMax r{};
-    if (int rc = read_maxima(c, c->map.max, &r, maxabs)) return rc;
+    const int rc = first_pass(c, c->map.max, &r, maxabs, [&] {
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            hipLaunchKernelGGL((moment_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(blocks_for(c->n, kBlock)),
+                               dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, c->map.max);
+        });
+    });
+    if (rc) return rc;
     if (r.bad)
         return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a moment m v, m |v|^2 that "
                                    "overflows fp64)");
@@ -179,8 +226,7 @@ int map_passes(bh_ctx *c, const char *who, const double *box, int32_t nx, int32_
     BH_HIP(c, hipSetDevice(c->device));
     double maxabs[kMapPlanes];
     if (int rc = map_maxima(c, who, maxabs)) return rc;
-    for (int p = 0; p < kMapPlanes; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
-    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    if (int rc = plane_exponents(c, who, given, maxabs, e)) return rc;
     const int64_t cells = (int64_t)nx * ny;
     if (int rc = map_alloc(c, cells)) return rc;
     BH_HIP(c, hipMemsetAsync(c->map.planes, 0, (size_t)kMapPlanes * cells * sizeof(long long), c->stream));
@@ -241,19 +287,16 @@ int rad_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, bool with_vel, 
     s.max_ms = 0.0;
     if (c->n == 0) return BH_OK;
     if (int rc = rad_alloc(c)) return rc;
-    if (int rc = mark(c, s.ev[0])) return rc;
-    BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(RadMax), c->stream));
-    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
-        dispatch([&](auto v) {
-            hipLaunchKernelGGL((radial_max_kernel<decltype(v)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(rad_grid(c)),
-                               dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, s.max);
-        }, with_vel);
-    });
-    BH_HIP(c, hipGetLastError());
-    if (int rc = mark(c, s.ev[1])) return rc;
     RadMax r{};
-    if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
-    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.max_ms)) return rc;
+    const int rc = first_pass(c, s.max, &r, maxabs, [&] {
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            dispatch([&](auto v) {
+                hipLaunchKernelGGL((radial_max_kernel<decltype(v)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>),
+                                   dim3(rad_grid(c)), dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, s.max);
+            }, with_vel);
+        });
+    }, s.ev, &s.max_ms);
+    if (rc) return rc;
     if (r.bad)
         return fail(c, BH_ERR_ARG, std::string(who) + ": a body has a non-finite position, velocity or mass (or a squared radius or a "
                                    "moment m vr, m vt, m vr^2, m vt^2 that overflows fp64)");
@@ -271,27 +314,17 @@ int rad_passes(bh_ctx *c, const char *who, const double *centre, const double *c
     RadCentre ctr{};
     std::vector<double> e2;
     if (int rc = rad_centre(c, who, centre, centre_vel, &ctr)) return rc;
-    // the squared edges on the host: BH_ERR_ARG unless the edges and their squares are finite, >= 0 and strictly ascending
-    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
-    const unsigned why = squared_edges(edges, nb, kRadMaxBins, e2);
-    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_RADIAL_MAX_BINS = " + std::to_string(kRadMaxBins));
-    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
-    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
-    if (why) return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
+    if (int rc = radial_edges(c, w, edges, nb, "BH_RADIAL_MAX_BINS", kRadMaxBins, e2)) return rc;
     if (int rc = need_upload(c, w + " before bh_upload/bh_initialize")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     double maxabs[kRadPlanes];
     if (int rc = rad_maxima(c, who, ctr, true, false, maxabs)) return rc;
-    for (int p = 0; p < kRadPlanes; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
-    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    if (int rc = plane_exponents(c, who, given, maxabs, e)) return rc;
     if (int rc = rad_alloc(c)) return rc;
     const int S = nb + 2;
     s.main_ms = 0.0;
     for (double &v : s.round_ms) v = 0.0;
-    if (int rc = mark(c, s.ev[2])) return rc;
-    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)(kRadPlanes + 1) * S * sizeof(long long), c->stream));
-    if (c->n > 0) {
-        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return deposit_pass(c, s.ev + 2, &s.main_ms, s.planes, (size_t)(kRadPlanes + 1) * S, s.e2, e2, [&] {
         RadExp ex{};
         for (int p = 0; p < kRadPlanes; ++p) ex.e[p] = e[p];
         const bool priv = S <= kRadLdsSlots;
@@ -302,11 +335,7 @@ int rad_passes(bh_ctx *c, const char *who, const double *centre, const double *c
                                    dim3(rad_grid(c)), dim3(kBlock), lds, c->stream, pos, vel, mass, c->n, ctr, s.e2, (int)nb, ex, s.planes);
             }, priv);
         });
-        BH_HIP(c, hipGetLastError());
-    }
-    if (int rc = mark(c, s.ev[3])) return rc;
-    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
-    return span_ms(c, s.ev[2], s.ev[3], &s.main_ms);
+    });
 }
 
 // one round: rad.hist[np][256][2] on the device and complete when this returns; timed between rad.ev[4 + 2 round] and the next
@@ -364,19 +393,16 @@ int mod_maxima(bh_ctx *c, const char *who, const RadCentre &ctr, int M, bool rat
     s.max_ms = 0.0;
     if (c->n == 0) return BH_OK;
     if (int rc = mod_alloc(c)) return rc;
-    if (int rc = mark(c, s.ev[0])) return rc;
-    BH_HIP(c, hipMemsetAsync(s.max, 0, sizeof(ModMax), c->stream));
-    state_ptrs(c, [&](auto pos, auto vel, auto mass) {
-        dispatch([&](auto r) {
-            hipLaunchKernelGGL((modes_max_kernel<decltype(r)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>), dim3(rad_grid(c)),
-                               dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, M, s.max);
-        }, rates);
-    });
-    BH_HIP(c, hipGetLastError());
-    if (int rc = mark(c, s.ev[1])) return rc;
     ModMax r{};
-    if (int rc = read_maxima(c, s.max, &r, maxabs)) return rc;
-    if (int rc = span_ms(c, s.ev[0], s.ev[1], &s.max_ms)) return rc;
+    const int rc = first_pass(c, s.max, &r, maxabs, [&] {
+        state_ptrs(c, [&](auto pos, auto vel, auto mass) {
+            dispatch([&](auto rt) {
+                hipLaunchKernelGGL((modes_max_kernel<decltype(rt)::value, Pointee<decltype(pos)>, Pointee<decltype(mass)>>),
+                                   dim3(rad_grid(c)), dim3(kBlock), 0, c->stream, pos, vel, mass, c->n, ctr, M, s.max);
+            }, rates);
+        });
+    }, s.ev, &s.max_ms);
+    if (rc) return rc;
     if (r.bad)
         return fail(c, BH_ERR_ARG, std::string(who) + ": the first pass found a body with a non-finite position, " +
                                    (rates ? "velocity, " : "") + "mass or squared radius, or a contribution m c_k, m s_k" +
@@ -401,25 +427,16 @@ int mod_passes(bh_ctx *c, const char *who, const double *centre, const double *c
     RadCentre ctr{};
     std::vector<double> e2;
     if (int rc = mod_args(c, who, centre, centre_vel, M, &ctr)) return rc;
-    if (!edges) return fail(c, BH_ERR_ARG, w + ": null edges");
-    const unsigned why = squared_edges(edges, nb, kModMaxBins, e2);
-    if (why & kEdgesCount) return fail(c, BH_ERR_ARG, w + ": nb must be 1 .. BH_MODES_MAX_BINS = " + std::to_string(kModMaxBins));
-    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return fail(c, BH_ERR_ARG, w + ": an edge or its square is not finite");
-    if (why & kEdgeNegative) return fail(c, BH_ERR_ARG, w + ": the edges must be >= 0");
-    if (why) return fail(c, BH_ERR_ARG, w + ": the edges and their squares must be strictly ascending");
+    if (int rc = radial_edges(c, w, edges, nb, "BH_MODES_MAX_BINS", kModMaxBins, e2)) return rc;
     if (int rc = need_upload(c, w + " before bh_upload/bh_initialize")) return rc;
     BH_HIP(c, hipSetDevice(c->device));
     double maxabs[2];
     if (int rc = mod_maxima(c, who, ctr, M, rates, maxabs)) return rc;
-    for (int p = 0; p < 2; ++p) e[p] = given ? given[p] : plane_exponent(maxabs[p], log2_ceil(c->n));
-    if (int rc = exponents_fit(c, who, e, maxabs)) return rc;
+    if (int rc = plane_exponents(c, who, given, maxabs, e)) return rc;
     if (int rc = mod_alloc(c)) return rc;
     const int S = nb + 2, P = modes_planes(M, rates);
     s.deposit_ms = 0.0;
-    if (int rc = mark(c, s.ev[2])) return rc;
-    BH_HIP(c, hipMemsetAsync(s.planes, 0, (size_t)P * S * sizeof(long long), c->stream));
-    if (c->n > 0) {
-        BH_HIP(c, hipMemcpyAsync(s.e2, e2.data(), e2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return deposit_pass(c, s.ev + 2, &s.deposit_ms, s.planes, (size_t)P * S, s.e2, e2, [&] {
         const ModesPlan plan = modes_plan(P, nb);
         state_ptrs(c, [&](auto pos, auto vel, auto mass) {
             dispatch([&](auto r) {
@@ -428,11 +445,29 @@ int mod_passes(bh_ctx *c, const char *who, const double *centre, const double *c
                                    plan.tile, (int)e[0], (int)e[1], s.planes);
             }, rates);
         });
-        BH_HIP(c, hipGetLastError());
+    });
+}
+
+// ---- the rotation curve (bh_disc.hpp).  It reads pos, mass and the force buffer as they lie in memory (slot for slot) and
+// writes buffers of its own: no record of bh_run_state.hpp changes.  disc_alloc serves bh_set_disc_velocities (bh_engine.hip) too.
+int disc_alloc(bh_ctx *c)
+{
+    DiscState &s = c->disc;
+    if (s.max) return BH_OK;
+    return alloc_all(c, {part(&s.max, 1), part(&s.e2, (size_t)kDiscMaxBins + 1), part(&s.tables, (size_t)kDiscTables * kDiscMaxTable),
+                         part(&s.planes, (size_t)(kDiscPlanes + 1) * (kDiscMaxBins + 2))});
+}
+
+// f(pos, mass, force) as the precision types them: the force buffer holds fp32 accelerations unless the tree is fp64
+template <typename F>
+void curve_ptrs(const bh_ctx *c, F &&f)
+{
+    switch (c->mode) {
+    case Mode::F32: f((const float2 *)c->pos, (const float *)c->mass, (const float2 *)c->force); break;
+    case Mode::Mixed: f((const double2 *)c->pos, (const double *)c->mass, (const float2 *)c->force); break;
+    case Mode::F64:
+    case Mode::Exact: f((const double2 *)c->pos, (const double *)c->mass, (const double2 *)c->force); break;
     }
-    if (int rc = mark(c, s.ev[3])) return rc;
-    BH_HIP(c, hipStreamSynchronize(c->stream));                  // (e2 lives on this stack until the copy has run)
-    return span_ms(c, s.ev[2], s.ev[3], &s.deposit_ms);
 }
 
 // ---- the field at arbitrary points (bh_field.hpp)
@@ -899,6 +934,52 @@ int bh_modes_times(bh_ctx *c, double *max_ms, double *deposit_ms)
     if (!c || !max_ms || !deposit_ms) return fail(c, BH_ERR_ARG, "bh_modes_times: null argument");
     *max_ms = c->mod.max_ms;
     *deposit_ms = c->mod.deposit_ms;
+    return BH_OK;
+}
+
+int bh_rotation_curve(bh_ctx *c, const double *centre, const double *edges, int32_t nb, int64_t *planes, int32_t *exponents)
+{
+    if (!c) return BH_ERR_ARG;
+    if (!planes || !exponents) return fail(c, BH_ERR_ARG, "bh_rotation_curve: null argument");
+    DiscState &s = c->disc;
+    RadCentre ctr{};
+    std::vector<double> e2;
+    if (int rc = rad_centre(c, "bh_rotation_curve", centre, nullptr, &ctr)) return rc;
+    if (int rc = radial_edges(c, "bh_rotation_curve", edges, nb, "BH_DISC_MAX_BINS", kDiscMaxBins, e2)) return rc;
+    if (int rc = split_check(c, "bh_rotation_curve")) return rc;
+    if (int rc = need_forces(c, "bh_rotation_curve")) return rc;
+    BH_HIP(c, hipSetDevice(c->device));
+    if (int rc = disc_alloc(c)) return rc;
+    const int S = nb + 2;
+    s.max_ms = s.deposit_ms = 0.0;
+    double maxabs[kDiscPlanes] = {0.0, 0.0, 0.0, 0.0};
+    if (c->n > 0) {
+        DiscMax r{};
+        const int rc = first_pass(c, s.max, &r, maxabs, [&] {
+            curve_ptrs(c, [&](auto pos, auto mass, auto force) {
+                hipLaunchKernelGGL((curve_max_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>),
+                                   dim3(rad_grid(c)), dim3(kBlock), 0, c->stream, pos, mass, force, c->n, ctr, s.max);
+            });
+        }, s.ev + 2, &s.max_ms);
+        if (rc) return rc;
+        if (r.bad)
+            return fail(c, BH_ERR_ARG, "bh_rotation_curve: a body has a non-finite position, mass or acceleration (a massless body of an "
+                                       "fp64 tree: 0 / 0), or a squared radius or a contribution m r, m (x . a), m (x x a) that overflows fp64");
+    }
+    int32_t e[kDiscPlanes];
+    if (int rc = plane_exponents(c, "bh_rotation_curve", nullptr, maxabs, e)) return rc;
+    const int rc = deposit_pass(c, s.ev + 4, &s.deposit_ms, s.planes, (size_t)(kDiscPlanes + 1) * S, s.e2, e2, [&] {
+        DiscExp ex{};
+        for (int p = 0; p < kDiscPlanes; ++p) ex.e[p] = e[p];
+        const size_t lds = ((size_t)(kDiscPlanes + 1) * S + (size_t)nb + 1) * 8;
+        curve_ptrs(c, [&](auto pos, auto mass, auto force) {
+            hipLaunchKernelGGL((curve_deposit_kernel<Pointee<decltype(pos)>, Pointee<decltype(mass)>, Pointee<decltype(force)>>),
+                               dim3(rad_grid(c)), dim3(kBlock), lds, c->stream, pos, mass, force, c->n, ctr, s.e2, (int)nb, ex, s.planes);
+        });
+    });
+    if (rc) return rc;
+    BH_HIP(c, hipMemcpy(planes, s.planes, (size_t)(kDiscPlanes + 1) * S * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::copy(e, e + kDiscPlanes, exponents);
     return BH_OK;
 }
 

@@ -1,5 +1,5 @@
 // bh_queries_state.hpp -- what the context keeps for the analysis queries of bh_queries_host.hpp, one struct per family
-// (bh_ctx has one member of each).  Everything is allocated on first use and lives as long as the context.  Part of the
+// (bh_ctx has one member of each; DiscState serves the rotation curve there and bh_set_disc_velocities in bh_engine.hip).  Everything is allocated on first use and lives as long as the context.  Part of the
 // bh_engine.hip translation unit, included there after the kernels' headers and before bh_ctx -- bh_queries_host.hpp needs the
 // whole context and comes after it: hence a header of its own.
 #pragma once

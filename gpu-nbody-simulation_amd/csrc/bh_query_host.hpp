@@ -1,8 +1,8 @@
-// bh_query_host.hpp -- the host arithmetic of the analysis queries (moment maps, radial profiles and Lagrangian radii, field at
-// points, neighbours, pair counts, groups): the fixed-point exponent rule, the squared bin edges, the query points' check, the
-// decisions of the Lagrangian select, the catalogue's order and the layout of a device block.  Standard C++ only -- nothing of
-// HIP, nothing of the context -- so tests/query_host_replay.cpp runs it with the host compiler; bh_queries_host.hpp is its
-// one user in the library.
+// bh_query_host.hpp -- the host arithmetic of the analysis queries (moment maps, radial profiles and Lagrangian radii, modes,
+// rotation curve, field at points, neighbours, pair counts, groups): the fixed-point exponent rule, the squared bin edges and how
+// a fault of theirs is worded, the query points' check, the decisions of the Lagrangian select, the catalogue's order and the
+// layout of a device block.  Standard C++ only -- nothing of HIP, nothing of the context -- so tests/query_host_replay.cpp runs
+// it with the host compiler; bh_queries_host.hpp is its one user in the library.
 #pragma once
 
 #include <algorithm>
@@ -55,6 +55,20 @@ inline unsigned squared_edges(const double *edges, int32_t nb, int32_t max_bins,
         if (why) return why;
     }
     return 0;
+}
+
+// how the radial profiles, the azimuthal modes and the rotation curve word a reason: null for 0, else the one text, the count
+// before not finite before negative before not ascending.  The count's text is kEdgesCountFault, which ends where the caller
+// names its own limit: "BH_..._MAX_BINS = <value>".  (The pair counts word theirs differently.)
+constexpr const char *kEdgesCountFault = "nb must be 1 .. ";
+
+inline const char *edges_fault(unsigned why)
+{
+    if (!why) return nullptr;
+    if (why & kEdgesCount) return kEdgesCountFault;
+    if (why & (kEdgeNotFinite | kEdgeSquareNotFinite)) return "an edge or its square is not finite";
+    if (why & kEdgeNegative) return "the edges must be >= 0";
+    return "the edges and their squares must be strictly ascending";
 }
 
 // ---- azimuthal modes (bh_modes.hpp): P planes of nb + 2 slots in the 64 KiB of dynamic LDS a launch may ask for without opting

@@ -18,8 +18,8 @@
 // the bodies that returns, for up to 32 prefixes (the digits already decided), 256 x {sum w, count}.  No sort, no gather, and
 // every number that decides anything is an integer sum: the same on any launch shape, body order or number of ranks.
 //
-// Launch shape: a fixed grid of persistent workgroups that stride over the bodies; the deposit and the select keep a
-// workgroup-private histogram in LDS (64-bit LDS atomics) and flush every non-zero entry to memory once.  All memory traffic is
+// Launch shape: a fixed grid of persistent workgroups that stride over the bodies; the deposit (SlotHist, bh_binned.hpp) and the
+// select keep a workgroup-private histogram in LDS (64-bit LDS atomics) and flush every non-zero entry to memory once.  All memory traffic is
 // ordinary vector loads, stores and atomics.
 #pragma once
 
@@ -42,7 +42,6 @@ struct RadMax {
     unsigned long long bad;                    // != 0: a non-finite position, velocity, mass, r2 or moment
     unsigned long long negative;               // != 0: a mass < 0
 };
-struct RadCentre { double cx, cy, ux, uy; };
 struct RadExp { int32_t e[kRadPlanes]; };
 
 // VEL = false (the Lagrangian radii): the velocities are not read, q1 .. q4 are 0.  Returns whether every input is finite.
@@ -75,27 +74,14 @@ __device__ __forceinline__ bool radial_body(const Real2 *__restrict__ pos, const
     return ok;
 }
 
-// the number of squared edges e2[0 .. nb] that are <= r2
-__device__ __forceinline__ int radial_slot(const double *e2, int nb, double r2)
-{
-    int lo = 0, hi = nb + 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e2[mid] <= r2) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // pass 1: out must be zeroed.  gridDim.x workgroups stride over the bodies (the one atomic per plane and workgroup all land on
 // one line: at N = 1M, 4,096 workgroups of one trip took 0.247 ms, 512 of eight trips 0.047 ms); a thread folds its trips,
-// the workgroup folds its threads in LDS, lane 0 sends one atomic per plane.
+// fold_maxima (bh_binned.hpp) folds the workgroup's threads in LDS and sends one atomic per plane.
 template <bool VEL, typename Real2, typename Real>
 __global__ __launch_bounds__(kBlock) void radial_max_kernel(const Real2 *__restrict__ pos, const Real2 *__restrict__ vel,
                                                             const Real *__restrict__ mass, int64_t n, RadCentre ctr,
                                                             RadMax *__restrict__ out)
 {
-    __shared__ double sh[kRadPlanes][kBlock];
-    __shared__ int sh_flag[kBlock];            // bit 0: bad, bit 1: a negative mass
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     double a[kRadPlanes] = {0.0, 0.0, 0.0, 0.0, 0.0};
     int flag = 0;
@@ -109,39 +95,16 @@ __global__ __launch_bounds__(kBlock) void radial_max_kernel(const Real2 *__restr
             if (!bad && fabs(q[p]) > a[p]) a[p] = fabs(q[p]);
         flag |= (bad ? 1 : 0) | (q[0] < 0.0 ? 2 : 0);
     }
-#pragma unroll
-    for (int p = 0; p < kRadPlanes; ++p) sh[p][threadIdx.x] = a[p];
-    sh_flag[threadIdx.x] = flag;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-#pragma unroll
-            for (int p = 0; p < kRadPlanes; ++p) {
-                const double b = sh[p][threadIdx.x + h];
-                if (b > sh[p][threadIdx.x]) sh[p][threadIdx.x] = b;
-            }
-            sh_flag[threadIdx.x] |= sh_flag[threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int p = 0; p < kRadPlanes; ++p) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(sh[p][0]);
-            if (b) atomicMax(&out->bits[p], b);
-        }
-        if (sh_flag[0] & 1) atomicOr(&out->bad, 1ull);
-        if (sh_flag[0] & 2) atomicOr(&out->negative, 1ull);
-    }
+    const int f = fold_maxima(a, flag, out);   // bit 0: bad, bit 1: a negative mass
+    if (f & 1) atomicOr(&out->bad, 1ull);
+    if (f & 2) atomicOr(&out->negative, 1ull);
 }
 
 // pass 2: planes[p][slot] += contribution, planes[5][slot] += 1, S = nb + 2 slots per plane.  gridDim.x workgroups stride over
-// the bodies; every workgroup has at least one body (the host sizes the grid so).  Dynamic LDS:
-//   PRIVATE  (S <= kRadLdsSlots): 6 * S words of histogram, then the nb + 1 squared edges: the whole histogram is private.
-//   !PRIVATE: 6 * kRadLdsSlots words.  The edges are searched in memory; a first trip over the workgroup's bodies takes the
-//             range of slots they touch; a range of at most kRadLdsSlots slots is summed in LDS at that offset, a wider one
-//             goes to memory directly.
-// The same integers either way, so the same planes.  Contributions that round to zero are skipped.
+// the bodies into a SlotHist (bh_binned.hpp) of 6 planes in dynamic LDS:
+//   PRIVATE  (S <= kRadLdsSlots): its private form, 6 * S words and the nb + 1 squared edges.
+//   !PRIVATE: its tiled form with a tile of kRadLdsSlots slots, 6 * kRadLdsSlots words.
+// The same integers either way, so the same planes.
 template <bool PRIVATE, typename Real2, typename Real>
 __global__ __launch_bounds__(kBlock) void radial_deposit_kernel(const Real2 *__restrict__ pos, const Real2 *__restrict__ vel,
                                                                 const Real *__restrict__ mass, int64_t n, RadCentre ctr,
@@ -149,58 +112,17 @@ __global__ __launch_bounds__(kBlock) void radial_deposit_kernel(const Real2 *__r
                                                                 long long *__restrict__ planes)
 {
     extern __shared__ unsigned long long rad_lds[];
-    __shared__ int range[2];                   // first and last slot touched (!PRIVATE)
-    const int S = nb + 2;
-    const int tile = PRIVATE ? S : kRadLdsSlots;
-    unsigned long long *hist = rad_lds;
-    const double *e2 = e2_mem;
-    if constexpr (PRIVATE) {
-        double *e2_lds = reinterpret_cast<double *>(rad_lds + (kRadPlanes + 1) * S);
-        for (int k = threadIdx.x; k <= nb; k += kBlock) e2_lds[k] = e2_mem[k];
-        e2 = e2_lds;
-    }
-    for (int k = threadIdx.x; k < (kRadPlanes + 1) * tile; k += kBlock) hist[k] = 0ull;
-    if (threadIdx.x == 0) { range[0] = INT32_MAX; range[1] = INT32_MIN; }
-    __syncthreads();
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-    int s0 = 0, width = S;
-    bool tiled = true;                         // (workgroup-uniform)
-    if constexpr (!PRIVATE) {
-        int lo = INT32_MAX, hi = INT32_MIN;
-        for (int64_t i = first; i < n; i += stride) {
-            const Real2 pp = pos[i];
-            const double dx = (double)pp.x - ctr.cx, dy = (double)pp.y - ctr.cy;
-            const int s = radial_slot(e2, nb, dx * dx + dy * dy);
-            lo = min(lo, s); hi = max(hi, s);
-        }
-        if (lo <= hi) { atomicMin(&range[0], lo); atomicMax(&range[1], hi); }
-        __syncthreads();
-        s0 = range[0];
-        width = range[1] - s0 + 1;             // (>= 1: the workgroup has a body)
-        tiled = width <= kRadLdsSlots;
-    }
-    for (int64_t i = first; i < n; i += stride) {
+    const SlotHist h = slot_hist(rad_lds, kRadPlanes + 1, nb, PRIVATE ? 0 : kRadLdsSlots, e2_mem, planes, pos, n, ctr);
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         double r2, q[kRadPlanes];
         radial_body<true>(pos, vel, mass, i, ctr, r2, q);
-        const int s = radial_slot(e2, nb, r2);
+        const int s = radial_slot(h.e2, nb, r2);
 #pragma unroll
-        for (int p = 0; p < kRadPlanes; ++p) {
-            const long long v = (long long)rint(ldexp(q[p], ex.e[p]));
-            if (!v) continue;
-            if (tiled) atomicAdd(&hist[p * tile + (s - s0)], (unsigned long long)v);
-            else atomicAdd(reinterpret_cast<unsigned long long *>(planes + (int64_t)p * S + s), (unsigned long long)v);
-        }
-        if (tiled) atomicAdd(&hist[kRadPlanes * tile + (s - s0)], 1ull);
-        else atomicAdd(reinterpret_cast<unsigned long long *>(planes + (int64_t)kRadPlanes * S + s), 1ull);
+        for (int p = 0; p < kRadPlanes; ++p) h.put(p, s, (long long)rint(ldexp(q[p], ex.e[p])));
+        h.put(kRadPlanes, s, 1ll);
     }
-    if (tiled) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < (kRadPlanes + 1) * width; k += kBlock) {
-            const int p = k / width, t = k - p * width;
-            const unsigned long long v = hist[p * tile + t];
-            if (v) atomicAdd(reinterpret_cast<unsigned long long *>(planes + (int64_t)p * S + s0 + t), v);
-        }
-    }
+    h.flush();
 }
 
 // One round of the radix select.  key = the bit pattern of r2; a body belongs to prefix k when key >> hi_shift == prefix[k]

@@ -145,14 +145,28 @@ class BhMomentMap:
     exponents: np.ndarray | None = None   # ... and their exponents: value = planes * 2^-exponent
 
 
-def moment_exponents(maxabs, n_total: int) -> np.ndarray:
-    """The four exponents 62 - E_p - L of a moment map from the maxima max |q_p| (bh_moment_map_max, combined over the
-    ranks with MAX) and the body count of the whole system: max < 2^E_p, L = ceil(log2(max(n, 1))); 0 where the maximum
-    is 0."""
-    m = np.asarray(maxabs, dtype=np.float64).reshape(4)
+def fixed_point_exponents(maxabs, n_total: int) -> np.ndarray:
+    """The rule of every binned sum: the exponents 62 - E_p - L of int64 planes from their maxima max |q_p| (combined over the
+    ranks with MAX) and the body count of the whole system: max < 2^E_p, L = ceil(log2(max(n, 1))); 0 where the maximum is 0."""
+    m = np.asarray(maxabs, dtype=np.float64).reshape(-1)
     L = 0 if n_total <= 1 else (int(n_total) - 1).bit_length()
     _, E = np.frexp(m)
     return np.where(m == 0.0, 0, 62 - E - L).astype(np.int32)
+
+
+def _scaled(planes, exponents, count: int) -> list:
+    """The first `count` int64 planes times 2^-exponent, in fp64."""
+    return [np.ldexp(planes[p].astype(np.float64), -int(exponents[p])) for p in range(count)]
+
+
+def _raw(planes, exponents, raw: bool):
+    """What a result keeps of its sums: (planes, a copy of the exponents as int32) when raw, else (None, None)."""
+    return (planes, np.asarray(exponents, dtype=np.int32).copy()) if raw else (None, None)
+
+
+def moment_exponents(maxabs, n_total: int) -> np.ndarray:
+    """The four exponents of a moment map (fixed_point_exponents) from the maxima of bh_moment_map_max."""
+    return fixed_point_exponents(np.asarray(maxabs, dtype=np.float64).reshape(4), n_total)
 
 
 def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int, raw: bool = False) -> BhMomentMap:
@@ -160,7 +174,7 @@ def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int
     planes = np.asarray(planes, dtype=np.int64)
     _, ny, nx = planes.shape
     box = tuple(float(b) for b in box)
-    mass, px, py, k2 = (np.ldexp(planes[p].astype(np.float64), -int(exponents[p])) for p in range(4))
+    mass, px, py, k2 = _scaled(planes, exponents, 4)
     area = ((box[1] - box[0]) / nx) * ((box[3] - box[2]) / ny)
     with np.errstate(divide="ignore", invalid="ignore"):
         vx, vy = px / mass, py / mass
@@ -168,8 +182,7 @@ def moment_map_from_planes(planes, exponents, box, scheme: str, n_deposited: int
     empty = mass == 0.0
     for a in (vx, vy, disp):
         a[empty] = np.nan
-    return BhMomentMap(mass, px, py, k2, mass / area, vx, vy, disp, box, scheme, int(n_deposited),
-                       planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+    return BhMomentMap(mass, px, py, k2, mass / area, vx, vy, disp, box, scheme, int(n_deposited), *_raw(planes, exponents, raw))
 
 
 RADIAL_MAX_BINS = 4096                  # BH_RADIAL_MAX_BINS
@@ -235,12 +248,8 @@ def radial_edges(r_min: float, r_max: float, nb: int, spacing: str = "log") -> n
 
 
 def radial_exponents(maxabs, n_total: int) -> np.ndarray:
-    """The exponents 62 - E_p - L of the fixed-point planes from the maxima max |q_p| (bh_radial_max, combined over the ranks
-    with MAX) and the body count of the whole system; 0 where the maximum is 0."""
-    m = np.asarray(maxabs, dtype=np.float64).reshape(-1)
-    L = 0 if n_total <= 1 else (int(n_total) - 1).bit_length()
-    _, E = np.frexp(m)
-    return np.where(m == 0.0, 0, 62 - E - L).astype(np.int32)
+    """The exponents of the radial planes (fixed_point_exponents) from the maxima of bh_radial_max."""
+    return fixed_point_exponents(maxabs, n_total)
 
 
 def radial_profile_from_planes(planes, exponents, edges, centre, centre_velocity=(0.0, 0.0), raw: bool = False) -> BhRadialProfile:
@@ -250,8 +259,7 @@ def radial_profile_from_planes(planes, exponents, edges, centre, centre_velocity
     nb = len(edges) - 1
     if planes.shape != (6, nb + 2):
         raise ValueError("planes must be (6, nb + 2)")
-    e = [int(x) for x in exponents]
-    val = [np.ldexp(planes[p].astype(np.float64), -e[p]) for p in range(5)]
+    val = _scaled(planes, exponents, 5)
     mass, pr, pt, kr, kt = (v[1:-1] for v in val)
     e2 = edges * edges
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -262,11 +270,11 @@ def radial_profile_from_planes(planes, exponents, edges, centre, centre_velocity
     empty = mass == 0.0
     for a in (vr, vt, sig_r, sig_t, beta):
         a[empty] = np.nan
-    enclosed = np.ldexp(np.cumsum(planes[0, :-1]).astype(np.float64), -e[0])       # (integer sums: |total| <= 2^62)
+    enclosed = np.ldexp(np.cumsum(planes[0, :-1]).astype(np.float64), -int(exponents[0]))       # (integer sums: |total| <= 2^62)
     return BhRadialProfile(edges, 0.5 * (edges[:-1] + edges[1:]), planes[5, 1:-1].copy(), mass, mass / (np.pi * (e2[1:] - e2[:-1])),
                            vr, vt, sig_r, sig_t, beta, float(val[0][0]), float(val[0][-1]), int(planes[5, 0]), int(planes[5, -1]),
                            enclosed, tuple(float(x) for x in centre), tuple(float(x) for x in centre_velocity),
-                           planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+                           *_raw(planes, exponents, raw))
 
 
 class LagrangianSelect:
@@ -276,7 +284,6 @@ class LagrangianSelect:
     ROUNDS = 64 // RADIAL_DIGIT_BITS
 
     def __init__(self, fractions):
-        import math
         self.fractions = [float(f) for f in np.asarray(fractions, dtype=np.float64).reshape(-1)]
         if not 1 <= len(self.fractions) <= RADIAL_MAX_FRACTIONS:
             raise ValueError(f"1 .. {RADIAL_MAX_FRACTIONS} fractions")
@@ -301,7 +308,6 @@ class LagrangianSelect:
 
     def advance(self, hist) -> None:
         """hist (np, 256, 2) int64: {sum w, count} per digit, for prefixes() in that order."""
-        import math
         pre = self.prefixes()
         h = np.asarray(hist, dtype=np.int64).reshape(len(pre), 1 << RADIAL_DIGIT_BITS, 2).tolist()
         if self.round == 0:
@@ -357,12 +363,11 @@ def modes_planes(m_max: int, rates: bool) -> int:
 
 
 def modes_exponents(maxabs, n_total: int) -> np.ndarray:
-    """The two exponents 62 - E - L of the A- and the D-planes from the maxima {maxA, maxD} (bh_modes_max, combined over the
-    ranks with MAX) and the body count of the whole system; 0 where the maximum is 0."""
+    """The two exponents of the A- and the D-planes (fixed_point_exponents) from the maxima {maxA, maxD} of bh_modes_max."""
     m = np.asarray(maxabs, dtype=np.float64).reshape(-1)
     if len(m) != 2:
         raise ValueError("two maxima")
-    return radial_exponents(m, n_total)
+    return fixed_point_exponents(m, n_total)
 
 
 def _mode_numbers(re_a, im_a, a0, re_d, im_d, k):
@@ -477,8 +482,7 @@ def azimuthal_modes_from_planes(planes, exponents, edges, m_max: int, rates: boo
                                                    d[k].imag if rates else None, k)
     return BhAzimuthalModes(edges, tuple(float(x) for x in centre), tuple(float(x) for x in centre_velocity), M,
                             planes[-1, 1:-1].copy(), mass, float(a_all[0, 0].real), float(a_all[0, -1].real), a.copy(), amp, phase,
-                            d.copy() if rates else None, speed if rates else None, planes if raw else None,
-                            np.array([e_a, e_d], dtype=np.int32) if raw else None, planes, (e_a, e_d))
+                            d.copy() if rates else None, speed if rates else None, *_raw(planes, (e_a, e_d), raw), planes, (e_a, e_d))
 
 
 DISC_MAX_BINS = 1022                    # BH_DISC_MAX_BINS
@@ -537,8 +541,7 @@ def rotation_curve_from_planes(planes, exponents, edges, centre, raw: bool = Fal
     nb = len(edges) - 1
     if planes.shape != (5, nb + 2):
         raise ValueError("planes must be (5, nb + 2)")
-    e = [int(x) for x in exponents]
-    val = [np.ldexp(planes[p].astype(np.float64), -e[p]) for p in range(4)]
+    val = _scaled(planes, exponents, 4)
     mass, mr, mxa, torque = (v[1:-1] for v in val)
     with np.errstate(divide="ignore", invalid="ignore"):
         radius, vc2 = mr / mass, -mxa / mass
@@ -551,10 +554,10 @@ def rotation_curve_from_planes(planes, exponents, edges, centre, raw: bool = Fal
     kappa = np.full(nb, np.nan)
     if good.sum() >= 2:
         kappa[good] = epicyclic_from(radius[good], omega[good])
-    cumulative = np.ldexp(np.cumsum(planes[3, :-1]).astype(np.float64), -e[3])        # (integer sums: |total| <= 2^62)
+    cumulative = np.ldexp(np.cumsum(planes[3, :-1]).astype(np.float64), -int(exponents[3]))        # (integer sums: |total| <= 2^62)
     return BhRotationCurve(edges, planes[4, 1:-1].copy(), mass, radius, vc2, vc, omega, kappa, torque, cumulative, float(val[0][0]),
                            float(val[0][-1]), int(planes[4, 0]), int(planes[4, -1]), tuple(float(x) for x in centre),
-                           planes if raw else None, np.asarray(exponents, dtype=np.int32).copy() if raw else None)
+                           *_raw(planes, exponents, raw))
 
 
 def toomre_q_from(curve: BhRotationCurve, profile: BhRadialProfile, G: float) -> np.ndarray:
@@ -1003,6 +1006,28 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _i64ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _i32ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _edges_arg(edges):
+    """(the edges as a contiguous fp64 array, its pointer -- None without any --, nb) as the radial calls take them."""
+    ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    return ed, (_dptr(ed) if len(ed) else None), len(ed) - 1
+
+
+def _exponents_arg(exponents, count: int, words: str) -> np.ndarray:
+    """A caller's `count` exponents as a contiguous int32 array."""
+    e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
+    if len(e) != count:
+        raise ValueError(words)
+    return e
+
+
 def sample_targets(n: int, sample: int = 65536, seed: int = 0) -> np.ndarray:
     """min(n, sample) distinct caller indices, drawn with numpy.random.default_rng(seed), in drawing order."""
     return np.random.default_rng(seed).choice(n, size=min(n, max(int(sample), 0)), replace=False).astype(np.int64)
@@ -1275,8 +1300,7 @@ class BarnesHutEngine:
         planes = np.zeros((4, ny, nx) if ok else (4, 1, 1), dtype=np.int64)
         e = np.zeros(4, dtype=np.int32)
         nd = C.c_int64()
-        self._check(self._lib.bh_moment_map(self._h, _dptr(b), nx, ny, sch, planes.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nd)))
+        self._check(self._lib.bh_moment_map(self._h, _dptr(b), nx, ny, sch, _i64ptr(planes), _i32ptr(e), C.byref(nd)))
         return moment_map_from_planes(planes, e, b, scheme, nd.value, raw)
 
     def moment_map_max(self) -> np.ndarray:
@@ -1289,12 +1313,9 @@ class BarnesHutEngine:
         """(device pointer of the int64 grid 4 x ny x nx, n_deposited): this context's bodies deposited with the caller's
         exponents (moment_exponents); the grid stays valid until the next moment-map call."""
         b, sch = self._map_args(box, scheme)
-        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
-        if len(e) != 4:
-            raise ValueError("four exponents")
+        e = _exponents_arg(exponents, 4, "four exponents")
         p, nd = C.c_void_p(), C.c_int64()
-        self._check(self._lib.bh_moment_map_deposit(self._h, _dptr(b), int(nx), int(ny), sch,
-                                                    e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p), C.byref(nd)))
+        self._check(self._lib.bh_moment_map_deposit(self._h, _dptr(b), int(nx), int(ny), sch, _i32ptr(e), C.byref(p), C.byref(nd)))
         return p.value, nd.value
 
     # -- radial profiles and Lagrangian radii -----------------------------------------------------
@@ -1324,13 +1345,11 @@ class BarnesHutEngine:
         relative to centre_velocity (default 0); binned on the device in fixed point: the same bodies give the same bits in any
         order.  Reads the state only; the run is not perturbed.  raw: also the int64 planes and their exponents."""
         c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
-        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        nb = len(ed) - 1
+        ed, edp, nb = _edges_arg(edges)
         ok = 1 <= nb <= RADIAL_MAX_BINS                            # (else the call refuses before it writes)
         planes = np.zeros((6, nb + 2) if ok else (6, 3), dtype=np.int64)
         e = np.zeros(5, dtype=np.int32)
-        self._check(self._lib.bh_radial_profile(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, nb,
-                                                planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(self._lib.bh_radial_profile(self._h, _dptr(c), _dptr(u), edp, nb, _i64ptr(planes), _i32ptr(e)))
         return radial_profile_from_planes(planes, e, ed, c, u, raw)
 
     def radial_max(self, centre, centre_velocity=None) -> np.ndarray:
@@ -1344,13 +1363,10 @@ class BarnesHutEngine:
         """Device pointer of the int64 planes 6 x (nb + 2): this context's bodies binned with the caller's exponents
         (radial_exponents); valid until the next radial call."""
         c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
-        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
-        if len(e) != 5:
-            raise ValueError("five exponents")
+        _, edp, nb = _edges_arg(edges)
+        e = _exponents_arg(exponents, 5, "five exponents")
         p = C.c_void_p()
-        self._check(self._lib.bh_radial_deposit(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, len(ed) - 1,
-                                                e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p)))
+        self._check(self._lib.bh_radial_deposit(self._h, _dptr(c), _dptr(u), edp, nb, _i32ptr(e), C.byref(p)))
         return p.value
 
     def lagrangian_radii(self, fractions=(0.01, 0.1, 0.5, 0.9), centre="density") -> BhLagrangian:
@@ -1362,9 +1378,8 @@ class BarnesHutEngine:
         nf = len(f)
         k = max(nf, 1)
         r2, cnt, mass, e = np.zeros(k), np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64), C.c_int32()
-        i64 = C.POINTER(C.c_int64)
-        self._check(self._lib.bh_lagrangian_radii(self._h, _dptr(c), _dptr(f) if nf else None, nf, _dptr(r2), cnt.ctypes.data_as(i64),
-                                                  mass.ctypes.data_as(i64), C.byref(e)))
+        self._check(self._lib.bh_lagrangian_radii(self._h, _dptr(c), _dptr(f) if nf else None, nf, _dptr(r2), _i64ptr(cnt),
+                                                  _i64ptr(mass), C.byref(e)))
         return lagrangian_from(f, r2[:nf], cnt[:nf], mass[:nf], e.value, c)
 
     def radial_select(self, centre, exponent: int, round: int, prefixes) -> int:
@@ -1396,13 +1411,12 @@ class BarnesHutEngine:
         across the edges of a single narrow bin (see BhAzimuthalModes).  Reads the state only; the run is not perturbed.
         raw: also the int64 planes and their two exponents."""
         c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
-        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        nb, M, rates = len(ed) - 1, int(m_max), bool(rates)
+        ed, edp, nb = _edges_arg(edges)
+        M, rates = int(m_max), bool(rates)
         ok = 1 <= nb <= MODES_MAX_BINS and 0 <= M <= MODES_MAX_M   # (else the call refuses before it writes)
         planes = np.zeros((modes_planes(M, rates), nb + 2) if ok else (1, 3), dtype=np.int64)
         e = np.zeros(2, dtype=np.int32)
-        self._check(self._lib.bh_azimuthal_modes(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, nb, M, int(rates),
-                                                 planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(self._lib.bh_azimuthal_modes(self._h, _dptr(c), _dptr(u), edp, nb, M, int(rates), _i64ptr(planes), _i32ptr(e)))
         return azimuthal_modes_from_planes(planes, e, ed, M, rates, c, u, raw)
 
     def modes_max(self, centre, centre_velocity=None, m_max: int = 4, rates: bool = False) -> np.ndarray:
@@ -1417,13 +1431,11 @@ class BarnesHutEngine:
         """Device pointer of the int64 planes modes_planes(m_max, rates) x (nb + 2): this context's bodies summed with the
         caller's two exponents (modes_exponents); valid until the next modes call."""
         c, u = self.centre_of(centre), self._pair_or_zero(centre_velocity)
-        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        e = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1)
-        if len(e) != 2:
-            raise ValueError("two exponents")
+        _, edp, nb = _edges_arg(edges)
+        e = _exponents_arg(exponents, 2, "two exponents")
         p = C.c_void_p()
-        self._check(self._lib.bh_modes_deposit(self._h, _dptr(c), _dptr(u), _dptr(ed) if len(ed) else None, len(ed) - 1, int(m_max),
-                                               int(bool(rates)), e.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(p)))
+        self._check(self._lib.bh_modes_deposit(self._h, _dptr(c), _dptr(u), edp, nb, int(m_max), int(bool(rates)), _i32ptr(e),
+                                               C.byref(p)))
         return p.value
 
     def modes_times(self):
@@ -1448,13 +1460,11 @@ class BarnesHutEngine:
         the same bodies give the same bits in any order.  Reads the state and the forces only; the run is not perturbed.
         raw: also the int64 planes and their exponents."""
         c = self.centre_of(centre)
-        ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-        nb = len(ed) - 1
+        ed, edp, nb = _edges_arg(edges)
         ok = 1 <= nb <= DISC_MAX_BINS                              # (else the call refuses before it writes)
         planes = np.zeros((5, nb + 2) if ok else (5, 3), dtype=np.int64)
         e = np.zeros(4, dtype=np.int32)
-        self._check(self._lib.bh_rotation_curve(self._h, _dptr(c), _dptr(ed) if len(ed) else None, nb,
-                                                planes.ctypes.data_as(C.POINTER(C.c_int64)), e.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(self._lib.bh_rotation_curve(self._h, _dptr(c), edp, nb, _i64ptr(planes), _i32ptr(e)))
         return rotation_curve_from_planes(planes, e, ed, c, raw)
 
     def toomre_q(self, edges, centre="density") -> np.ndarray:

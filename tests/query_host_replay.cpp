@@ -65,6 +65,46 @@ void edges()
     edges_case("too_many_bins", {0.0, 1.0, 2.0, 3.0, 4.0, 5.0}, 5);
 }
 
+// the text a family words a list of edges with, as bh_queries_host.hpp puts it together: edges_fault's, and behind the count's
+// the family's limit
+void fault_case(const char *name, const std::vector<double> &in, const char *limit_name, int32_t limit)
+{
+    std::vector<double> e2;
+    const char *fault = edges_fault(squared_edges(in.data(), (int32_t)in.size() - 1, limit, e2));
+    std::printf("edges_fault %s %s ", limit_name, name);
+    if (!fault) std::printf("-\n");
+    else if (fault == kEdgesCountFault) std::printf("%s%s = %d\n", fault, limit_name, (int)limit);
+    else std::printf("%s\n", fault);
+}
+
+void edge_faults()
+{
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const struct { const char *name; int32_t limit; } families[] = {{"BH_RADIAL_MAX_BINS", 4096}, {"BH_MODES_MAX_BINS", 4096},
+                                                                     {"BH_DISC_MAX_BINS", 1022}};
+    for (const auto &f : families) {
+        std::vector<double> long_list((size_t)f.limit + 2), longest((size_t)f.limit + 1);
+        for (size_t k = 0; k < long_list.size(); ++k) long_list[k] = (double)k;
+        for (size_t k = 0; k < longest.size(); ++k) longest[k] = (double)k;
+        fault_case("good", {0.0, 1.0}, f.name, f.limit);
+        fault_case("longest", longest, f.name, f.limit);
+        fault_case("one_edge", {1.0}, f.name, f.limit);
+        fault_case("no_edge", {}, f.name, f.limit);
+        fault_case("equal", {1.0, 1.0}, f.name, f.limit);
+        fault_case("descending", {2.0, 1.0}, f.name, f.limit);
+        fault_case("negative", {-1.0, 1.0}, f.name, f.limit);
+        fault_case("infinite", {0.0, inf}, f.name, f.limit);
+        fault_case("nan", {0.0, nan}, f.name, f.limit);
+        fault_case("square_overflows", {0.0, 1e200}, f.name, f.limit);
+        fault_case("squares_underflow", {1e-200, 2e-200}, f.name, f.limit);
+        fault_case("too_long", long_list, f.name, f.limit);
+        // two faults on one edge: the precedence
+        fault_case("negative_and_overflowing", {-1e200, 1.0}, f.name, f.limit);
+        fault_case("negative_and_descending", {0.0, -1.0}, f.name, f.limit);
+        fault_case("too_long_and_nan", std::vector<double>((size_t)f.limit + 2, nan), f.name, f.limit);
+    }
+}
+
 void points()
 {
     const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
@@ -166,6 +206,7 @@ int main(int argc, char **argv)
 {
     exponents();
     edges();
+    edge_faults();
     points();
     select_args();
     catalogue();

@@ -155,11 +155,12 @@ def test_thirty_two_fractions_take_four_launches_a_round():
         radii_as_twin(e, pos, mass, [0.9, 0.1, 0.5], "unordered")
 
 
-@pytest.mark.parametrize("span", [1000, 1100])
+@pytest.mark.parametrize("span", [1000, 1024, 1025, 1100])
 def test_more_slots_than_lds_holds(monkeypatch, span):
     """4,096 bins.  600 bodies in three workgroups: the first 256 lie within `span` consecutive bins -- 1,000: the workgroup sums
-    them in LDS at an offset; 1,100: it deposits directly -- two bodies at the ends making sure of it; the second 256 lie in one
-    bin; the rest are spread over all bins, inside and outside."""
+    them in LDS at an offset; 1,100: it deposits directly -- two bodies at the ends making sure of it; 1,024 and 1,025: the last
+    range the 1,024 slots of the LDS histogram hold and the first they do not; the second 256 lie in one bin; the rest are
+    spread over all bins, inside and outside."""
     monkeypatch.delenv("BH_RADIAL_BLOCKS", raising=False)
     rng = np.random.default_rng(span)
     nb = 4096

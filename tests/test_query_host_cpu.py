@@ -1,8 +1,8 @@
 """csrc/bh_query_host.hpp -- the host arithmetic of the analysis queries -- compiles with the plain host compiler, includes nothing
 of HIP, and agrees with the Python side of the project when tests/query_host_replay.cpp runs it on its own: the fixed-point
 exponent rule with engine.moment_exponents / radial_exponents, the squared edges with the conditions of the two callers (a reason
-per case, from reading them), the Lagrangian select with engine.LagrangianSelect round by round, the catalogue's order with
-sorted(), and the block layout with its own counting pass."""
+per case, from reading them), edges_fault with the texts of the three ladders it replaced, the Lagrangian select with
+engine.LagrangianSelect round by round, the catalogue's order with sorted(), and the block layout with its own counting pass."""
 import math
 import os
 import re
@@ -112,6 +112,31 @@ def test_squared_edges(replay):
     assert radial(want["square_underflows"]) == "not ascending" and pairs(want["square_underflows"]) == "squared edges"
     assert radial(want["square_overflows"]) == "not finite" and pairs(want["square_overflows"]) == "squared edges"
     assert radial(want["nan"]) == "not finite" and pairs(want["nan"]) == "edges"
+
+
+def test_edges_fault_texts(replay):
+    """edges_fault words every list of edges of the GPU tests' test_errors as the three callers' own ladders did before they shared
+    it -- in rad_passes, in mod_passes and in bh_rotation_curve, each: the count (with the family's limit), else not finite (the
+    edge or its square), else negative, else not ascending.  The strings below are copied from those ladders, not from the
+    function.  (An empty list reaches the library as a null pointer and is refused as "null edges" before this; the rule itself
+    calls it a count.)"""
+    not_finite, negative = "an edge or its square is not finite", "the edges must be >= 0"
+    ascending = "the edges and their squares must be strictly ascending"
+    limits = {"BH_RADIAL_MAX_BINS": 4096, "BH_MODES_MAX_BINS": 4096, "BH_DISC_MAX_BINS": 1022}
+    rows = {(r[0], r[1]): " ".join(r[2:]) for r in replay["edges_fault"]}
+    assert len(rows) == len(replay["edges_fault"]) == 15 * len(limits)
+    for family, limit in limits.items():
+        count = f"nb must be 1 .. {family} = {limit}"
+        want = {
+            "good": "-", "longest": "-",
+            "one_edge": count, "no_edge": count, "too_long": count,
+            "equal": ascending, "descending": ascending, "squares_underflow": ascending,
+            "negative": negative,
+            "infinite": not_finite, "nan": not_finite, "square_overflows": not_finite,
+            # two faults at once: not finite before negative, negative before not ascending, the count before everything
+            "negative_and_overflowing": not_finite, "negative_and_descending": negative, "too_long_and_nan": count,
+        }
+        assert {case: text for (fam, case), text in rows.items() if fam == family} == want, family
 
 
 def test_points_and_select_arguments(replay):
